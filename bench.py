@@ -11,9 +11,13 @@ A "frame" = one camera view with all its links, forward + backward.  Inputs are 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 200 --warmup 20
 
-Rank 0 prints ONE JSON line (driver contract) with two extra objects: "roofline" (dominant kernel vs HBM peak,
-hipEvent-timed on the launch stream) and "cpu_baseline" (the CPU oracle timed on this box's host cores; a reported
-baseline, not the target).
+Rank 0 prints ONE JSON line (driver contract).  A plain run sets up, warms up, times exactly --steps steps and prints
+the headline; --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.  --full adds the
+measurements beside the headline: "roofline" (dominant kernel vs HBM peak, hipEvent-timed on the launch stream), the
+with-mask leg, the side workloads, the drop-in step, "cpu_baseline" (the CPU oracle timed on the host cores; a reported
+baseline, not the target) and, with N > 1, the exchange latencies:
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
 """
 import argparse
 import json
@@ -188,6 +192,22 @@ def timed_blocks(step, steps, barrier, min_ms, world=1, dev=None, max_blocks=100
     return elapsed / blocks, blocks
 
 
+def dump_outputs(p, d):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy (a few hundred bytes in all): the
+    mean mask loss it returned (evaluated before its update), the per-view losses (launch chain only), the 6-DoF pose
+    after its Adam update, the pose gradient it applied, and the camera-to-base transform of the new pose.  The inputs
+    are seeded (make_views(seed=0), a fixed perturbation of the pose), so equal arguments give equal inputs."""
+    tr, model = p["trainer"], p["model"]
+    torch.cuda.synchronize()
+    arrays = {"loss": tr.last_loss, "dof": model.dof,
+              "dof_grad": tr.fast.grad if tr.fast is not None else model.dof.grad, "Tc_c2b": model.Tc_c2b()}
+    if tr.fast is not None:
+        arrays["loss_per_view"] = tr.fast.loss_b
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.atleast_1d(t.detach().float().cpu().numpy()))
+
+
 def stage_times(p, steps, step_fn=None):
     """hipEvents around each kernel of the chain (eager launches), `steps` more steps of the same optimisation.
     The default chain launches no resolve kernel (the job kernel resolves its own jobs): the event pair that would bracket
@@ -320,6 +340,76 @@ def drop_in_step(p, dev, steps=20):
     return res
 
 
+def roofline(p, args, fps, elapsed, stage_ms, dev):
+    """--full: the dominant kernel and the whole step against the HBM peak (algorithmic bytes over the hipEvent-timed kernel
+    and the driver-timed step), the measured copy ceiling, and the PMC / SQ figures of the committed profiles."""
+    from easyhec_amd import fused
+    bytes_frame = algorithmic_bytes_per_frame(p["robot"], p["H"], p["W"])
+    # the dominant kernel (fused.DOMINANT_KERNEL), bracketed by its own pair of hipEvents on the launch stream
+    # (compare with rocprofv3's average for it in profiles/)
+    tile_ms = stage_ms[fused.DOMINANT_STAGE]
+    bytes_launch = bytes_frame * p["B"]
+    achieved = bytes_launch / (tile_ms * 1e-3) / 1e9 if tile_ms > 0 else 0.0
+    step_gbs = fps * bytes_frame / 1e9  # SURVEY 8d's own definition: frames/s x bytes_frame (whole step, all kernels)
+    copy_gbs = measured_copy_bandwidth(dev)
+    # HBM bytes from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate passes, gfx950 corrections): counters cannot
+    # be read inside this run, so the figures come from profiles/traffic.json -- collected on the SAME launch form
+    # this script times (ehr_solver_step, bound reference, no mask output; tools/gpu_traffic.sh) at the commit it names
+    traffic, traffic_kernel, traffic_src = None, None, None
+    sha_now, stale = csrc_sha16(), False
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath) and args.workload == WORKLOAD:
+        try:
+            tj = json.load(open(tpath))
+            traffic = tj.get("hbm_bytes_whole_op")        # PMC-measured HBM bytes of ALL kernels of one step
+            traffic_kernel = tj.get("hbm_bytes_dominant_kernel")
+            traffic_src = {"file": "profiles/traffic.json", "commit": tj.get("commit"), "launch_form": tj.get("launch_form"),
+                           "csrc_sha16": tj.get("csrc_sha16")}
+            stale = stale or tj.get("csrc_sha16") != sha_now
+        except Exception:
+            traffic = None
+    # what binds the dominant kernel besides bandwidth (it is not HBM-bound at 8 views): VALU issue utilisation from the SQ
+    # counters and the compiler's register / spill figures, carried like `traffic` from a committed profile of this
+    # command (profiles/counters.json, tools/make_counters.py; names its commit)
+    counters = {}
+    cpath = os.path.join(ROOT, "profiles", "counters.json")
+    if os.path.exists(cpath) and args.workload == WORKLOAD:
+        try:
+            cj = json.load(open(cpath))
+            counters = {"valu_util": cj.get("valu_util"), "wave_active_frac": cj.get("wave_active_frac"),
+                        "spilled_sgprs": cj.get("resources", {}).get("spilled_sgprs"),
+                        "spilled_vgprs": cj.get("resources", {}).get("spilled_vgprs"),
+                        "vgprs": cj.get("resources", {}).get("vgprs"), "waves_per_simd": cj.get("resources", {}).get("waves_per_simd"),
+                        "kernel_us_rocprof": cj.get("kernel_us_rocprof"),
+                        "counters_source": {"file": "profiles/counters.json", "commit": cj.get("commit"),
+                                            "csrc_sha16": cj.get("csrc_sha16")}}
+            stale = stale or cj.get("csrc_sha16") != sha_now
+        except Exception:
+            counters = {}
+    out = {"bound": "hbm", "kernel": fused.DOMINANT_KERNEL, "achieved": round(achieved, 2),
+           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+           # the same algorithmic bytes over the WHOLE step (driver-timed value x bytes_frame): the honest
+           # figure for "how close is the step to streaming its images once", next to the per-kernel one
+           "achieved_step": round(step_gbs, 2), "frac_step": round(step_gbs / HBM_PEAK_GBS, 5),
+           "peak_measured_copy": round(copy_gbs, 1), "frac_step_vs_measured_copy": round(step_gbs / copy_gbs, 5),
+           "traffic": traffic, "traffic_dominant_kernel": traffic_kernel, "traffic_source": traffic_src,
+           # real HBM rate of the whole step: counter bytes / driver-timed step (next to the algorithmic one)
+           "hbm_actual_step": round(traffic / (elapsed / args.steps) / 1e9, 2) if traffic else None,
+           # ... and of the dominant kernel: counter bytes / its duration in THIS run / peak.  `frac` above is an
+           # equivalent rate (algorithmic bytes the kernel does not move: no mask is written, the bound reference
+           # is not re-read); this is the bandwidth the kernel really uses
+           "frac_hbm_actual": round(traffic_kernel / (tile_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+           if traffic_kernel and tile_ms > 0 else None,
+           # true when profiles/counters.json or traffic.json were collected on other kernel sources than the
+           # ones in this tree (they name the SHA-256 of easyhec_amd/csrc they were collected on)
+           "counters_stale": bool(stale), "csrc_sha16": sha_now,
+           "algorithmic_bytes_per_launch": bytes_launch, "kernel_ms": round(tile_ms, 5),
+           "stage_ms": {k: round(v, 5) for k, v in stage_ms.items()}}
+    out.update(counters)
+    out["frac_is"] = FRAC_NOTE
+    return out
+
+
 def main():
     # stdout carries exactly ONE line, the JSON: libraries that chat on stdout (RCCL prints a version banner when a
     # communicator is created) go to stderr for the whole run
@@ -331,14 +421,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--min-ms", type=float, default=50.0, help="repeat the timed block of --steps steps until this much "
-                    "timed work has accumulated (0 = exactly one block)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--min-ms", type=float, default=0.0, help="repeat the timed block of --steps steps until this much "
+                    "timed work has accumulated (default 0: exactly one block, i.e. --steps timed steps)")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beside the headline: the with-mask leg, "
+                    "the roofline (per-kernel hipEvents, copy bandwidth, committed counters), the side workloads, the drop-in "
+                    "step, the CPU baseline and, with N > 1, the exchange latencies")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (loss, per-view loss, "
+                    "pose, its gradient, Tc_c2b) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--eager", action="store_true", help="reference-shaped torch autograd step instead of the HIP launch chain")
     ap.add_argument("--workload", default=WORKLOAD, help="side measurements only; the headline is the default")
-    ap.add_argument("--no-with-mask", action="store_true", help="skip the with-mask leg (profiling runs: one launch form per kernel)")
-    ap.add_argument("--no-drop-in", action="store_true", help="skip the drop-in (three ops under autograd, graph replay) step, ~20 s")
-    ap.add_argument("--no-side", action="store_true", help="skip the side workloads (the other BASELINE configs, ~0.5 s each)")
+    ap.add_argument("--no-with-mask", action="store_true", help="--full: skip the with-mask leg (profiling runs: one launch form per kernel)")
+    ap.add_argument("--no-drop-in", action="store_true", help="--full: skip the drop-in (three ops under autograd, graph replay) step, ~20 s")
+    ap.add_argument("--no-side", action="store_true", help="--full: skip the side workloads (the other BASELINE configs, ~0.5 s each)")
     ap.add_argument("--graph", action="store_true", help="replay the launch chain as a natively captured hipGraph (saves host time only)")
     args = ap.parse_args()
 
@@ -396,12 +491,14 @@ def main():
         if int(recovered.item()):
             for _ in range(args.warmup):
                 step()
-    # The timed block is exactly --steps steps between two barriers (driver contract).  One block of a 0.1 ms step is a
-    # thin sample (20 steps = 2 ms), so blocks are repeated -- each bracketed the same way, the optimisation simply
-    # continues -- until at least --min-ms of timed work has accumulated; the reported time per step is the mean over all
-    # timed steps.  Every rank runs the same number of blocks (rank 0's decision is broadcast).
+    # The timed block is exactly --steps steps between two barriers (driver contract).  By default there is one block; with
+    # --min-ms blocks are repeated -- each bracketed the same way, the optimisation simply continues -- until at least that
+    # much timed work has accumulated, and the reported time per step is the mean over all timed steps.  Every rank runs
+    # the same number of blocks (rank 0's decision is broadcast).
     elapsed, blocks = timed_blocks(step, args.steps, barrier, args.min_ms, world, dev)  # mean duration of one block
     fused.check_status(p["glctx"])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(p, args.dump_outputs)
     per_rank_ms, allreduce_us = None, None
     if world > 1:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -409,6 +506,7 @@ def main():
         dist.all_gather(allr, mine)
         per_rank_ms = [round(float(x.item()) / args.steps * 1e3, 4) for x in allr]
         elapsed = max(float(x.item()) for x in allr)  # the job is as slow as its slowest rank
+    if world > 1 and args.full:
         # the step's ONE exchange on its own: 8 floats, latency-bound -- the one the step makes first, then (where
         # they are available) the others beside it: the library's peer-memory exchange (one kernel, Adam not included here),
         # ncclAllReduce on the library's communicator, torch.distributed's all-reduce
@@ -440,18 +538,19 @@ def main():
 
     # the same step WITH the rendered masks written (rb_solver.py:73-77 materialises `rendered_masks` every step): the
     # chain then streams every tile of every view (the bound reference's cached sums do not apply) and writes mask[B,H,W]
+    # (this leg and everything measured below run with --full only: a plain run times the headline and nothing else)
     with_mask_ms, with_mask_stage_ms = None, None
-    if tr.fast is not None and world == 1 and not args.no_with_mask:
+    if args.full and tr.fast is not None and world == 1 and not args.no_with_mask:
         mstep = lambda: tr.fast.step(want_mask=True)  # noqa: E731
         for _ in range(max(2, args.warmup // 4)):
             mstep()
-        el_m, _ = timed_blocks(mstep, args.steps, barrier, min(args.min_ms, 30.0))
+        el_m, _ = timed_blocks(mstep, args.steps, barrier, min(args.min_ms or 30.0, 30.0))
         with_mask_ms = el_m / args.steps * 1e3
         with_mask_stage_ms = stage_times(p, args.steps, mstep)
     # roofline leg: hipEvents around each kernel of the fused op, same K steps again (continuing the optimisation)
-    stage_ms = stage_times(p, args.steps)
+    stage_ms = stage_times(p, args.steps) if args.full else None
     side = None
-    if world == 1 and rank == 0 and not args.no_side and args.workload == WORKLOAD and not args.eager:
+    if args.full and world == 1 and rank == 0 and not args.no_side and args.workload == WORKLOAD and not args.eager:
         side = {}
         for name in ("xarm7_640x480_1view", "franka_1920x1080_16view", "xarm7_1280x720_64view"):
             try:
@@ -461,7 +560,7 @@ def main():
                 side[name] = {"error": f"{type(e).__name__}: {e}"}
 
     drop_in = None
-    if world == 1 and rank == 0 and not args.no_drop_in and args.workload == WORKLOAD and not args.eager:
+    if args.full and world == 1 and rank == 0 and not args.no_drop_in and args.workload == WORKLOAD and not args.eager:
         try:
             drop_in = drop_in_step(p, dev)
         except Exception as e:  # informational: must never cost the headline line
@@ -470,48 +569,6 @@ def main():
     if rank == 0:
         frames = p["n_views"] * args.steps
         fps = frames / elapsed
-        bytes_frame = algorithmic_bytes_per_frame(p["robot"], p["H"], p["W"])
-        # the dominant kernel (fused.DOMINANT_KERNEL), bracketed by its own pair of hipEvents on the launch stream
-        # (compare with rocprofv3's average for it in profiles/)
-        tile_ms = stage_ms[fused.DOMINANT_STAGE]
-        bytes_launch = bytes_frame * p["B"]
-        achieved = bytes_launch / (tile_ms * 1e-3) / 1e9 if tile_ms > 0 else 0.0
-        step_gbs = fps * bytes_frame / 1e9  # SURVEY 8d's own definition: frames/s x bytes_frame (whole step, all kernels)
-        copy_gbs = measured_copy_bandwidth(dev)
-        # HBM bytes from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate passes, gfx950 corrections): counters cannot
-        # be read inside this run, so the figures come from profiles/traffic.json -- collected on the SAME launch form
-        # this script times (ehr_solver_step, bound reference, no mask output; tools/gpu_traffic.sh) at the commit it names
-        traffic, traffic_kernel, traffic_src = None, None, None
-        sha_now, stale = csrc_sha16(), False
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath) and args.workload == WORKLOAD:
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get("hbm_bytes_whole_op")        # PMC-measured HBM bytes of ALL kernels of one step
-                traffic_kernel = tj.get("hbm_bytes_dominant_kernel")
-                traffic_src = {"file": "profiles/traffic.json", "commit": tj.get("commit"), "launch_form": tj.get("launch_form"),
-                               "csrc_sha16": tj.get("csrc_sha16")}
-                stale = stale or tj.get("csrc_sha16") != sha_now
-            except Exception:
-                traffic = None
-        # what binds the dominant kernel besides bandwidth (it is not HBM-bound at 8 views): VALU issue utilisation from the SQ
-        # counters and the compiler's register / spill figures, carried like `traffic` from a committed profile of this
-        # command (profiles/counters.json, tools/make_counters.py; names its commit)
-        counters = {}
-        cpath = os.path.join(ROOT, "profiles", "counters.json")
-        if os.path.exists(cpath) and args.workload == WORKLOAD:
-            try:
-                cj = json.load(open(cpath))
-                counters = {"valu_util": cj.get("valu_util"), "wave_active_frac": cj.get("wave_active_frac"),
-                            "spilled_sgprs": cj.get("resources", {}).get("spilled_sgprs"),
-                            "spilled_vgprs": cj.get("resources", {}).get("spilled_vgprs"),
-                            "vgprs": cj.get("resources", {}).get("vgprs"), "waves_per_simd": cj.get("resources", {}).get("waves_per_simd"),
-                            "kernel_us_rocprof": cj.get("kernel_us_rocprof"),
-                            "counters_source": {"file": "profiles/counters.json", "commit": cj.get("commit"),
-                                                "csrc_sha16": cj.get("csrc_sha16")}}
-                stale = stale or cj.get("csrc_sha16") != sha_now
-            except Exception:
-                counters = {}
         out = {
             "metric": "mask-render fwd+bwd frames/sec, xArm7 50k-tri @1280x720x8-view" if args.workload == WORKLOAD else f"mask-render fwd+bwd frames/sec, {args.workload}",
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -538,28 +595,9 @@ def main():
                        "final_mask_loss": round(final_loss, 3),
                        # device memory the solve's rasterizer context holds (job slots: one per view tile by default)
                        "context_scratch_mb": round(p["glctx"].scratch_bytes() / 1048576.0, 1)},
-            "roofline": {"bound": "hbm", "kernel": fused.DOMINANT_KERNEL, "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         # the same algorithmic bytes over the WHOLE step (driver-timed value x bytes_frame): the honest
-                         # figure for "how close is the step to streaming its images once", next to the per-kernel one
-                         "achieved_step": round(step_gbs, 2), "frac_step": round(step_gbs / HBM_PEAK_GBS, 5),
-                         "peak_measured_copy": round(copy_gbs, 1), "frac_step_vs_measured_copy": round(step_gbs / copy_gbs, 5),
-                         "traffic": traffic, "traffic_dominant_kernel": traffic_kernel, "traffic_source": traffic_src,
-                         # real HBM rate of the whole step: counter bytes / driver-timed step (next to the algorithmic one)
-                         "hbm_actual_step": round(traffic / (elapsed / args.steps) / 1e9, 2) if traffic else None,
-                         # ... and of the dominant kernel: counter bytes / its duration in THIS run / peak.  `frac` above is an
-                         # equivalent rate (algorithmic bytes the kernel does not move: no mask is written, the bound reference
-                         # is not re-read); this is the bandwidth the kernel really uses
-                         "frac_hbm_actual": round(traffic_kernel / (tile_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-                         if traffic_kernel and tile_ms > 0 else None,
-                         # true when profiles/counters.json or traffic.json were collected on other kernel sources than the
-                         # ones in this tree (they name the SHA-256 of easyhec_amd/csrc they were collected on)
-                         "counters_stale": bool(stale), "csrc_sha16": sha_now,
-                         "algorithmic_bytes_per_launch": bytes_launch, "kernel_ms": round(tile_ms, 5),
-                         "stage_ms": {k: round(v, 5) for k, v in stage_ms.items()}},
         }
-        out["roofline"].update(counters)
-        out["roofline"]["frac_is"] = FRAC_NOTE
+        if args.full:
+            out["roofline"] = roofline(p, args, fps, elapsed, stage_ms, dev)
         if with_mask_ms is not None:
             out["with_mask_ms_per_step"] = round(with_mask_ms, 4)
             out["with_mask_value"] = round(p["n_views"] / (with_mask_ms * 1e-3), 1)
@@ -567,6 +605,8 @@ def main():
             # `rendered_masks`): the step the reference's own forward corresponds to
             km = with_mask_stage_ms[fused.DOMINANT_STAGE]
             fps_m = p["n_views"] / (with_mask_ms * 1e-3)
+            bytes_frame = algorithmic_bytes_per_frame(p["robot"], p["H"], p["W"])
+            bytes_launch = bytes_frame * p["B"]
             out["roofline_with_mask"] = {
                 "launch_form": "ehr_solver_step with a mask output: mask[B,H,W] written every step (4 B per pixel: the job tiles by "
                                "their owners, zeros elsewhere), reference read at the job tiles, its sums over the other tiles cached",
@@ -580,9 +620,10 @@ def main():
             out["drop_in"] = drop_in
         if per_rank_ms is not None:
             out["per_rank_ms_per_step"] = per_rank_ms
+        if allreduce_us is not None:
             out["allreduce_8float_us"] = round(allreduce_us, 2)
             out["exchange"] = {"used_by_the_step": exchange_used, "us_per_exchange_of_8_floats": exchange_us}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(p)
         json_out.write(json.dumps(out) + "\n")
         json_out.flush()

@@ -27,7 +27,8 @@ def _run(args, timeout=900):
 
 def test_bench_under_torchrun_matches_the_plain_run():
     port = 29700 + (os.getpid() % 1000)
-    common = ["--gpus", "1", "--steps", "100", "--warmup", "20", "--no-cpu-baseline", "--no-side"]
+    # (--min-ms 50: blocks of 100 steps until 50 ms of timed work, the sample the comparison below was set for)
+    common = ["--gpus", "1", "--steps", "100", "--warmup", "20", "--min-ms", "50"]
     plain = _run([sys.executable, "bench.py"] + common)
     launched = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                      "127.0.0.1", "--master-port", str(port), "bench.py"] + common)
@@ -55,7 +56,8 @@ def test_bench_with_two_ranks_on_one_device_and_the_peer_memory_exchange():
     port = 31900 + (os.getpid() % 1000)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", EHR_BENCH_BACKEND="gloo", EHR_BENCH_DEVICE="0", EHR_COMM="p2p")
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "10", "--no-cpu-baseline"]
+            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "10", "--full",
+            "--no-cpu-baseline"]
     out = subprocess.run(args, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -79,7 +81,8 @@ def test_bench_with_two_ranks_on_one_device_over_gloo(try_rccl):
     if try_rccl:
         env["EHR_TRY_RCCL"] = "1"
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "10", "--no-cpu-baseline"]
+            "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "10", "--full",
+            "--no-cpu-baseline"]
     out = subprocess.run(args, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -26,5 +26,5 @@ python tools/three_op_bench.py --graph --steps 50 >> $out/${tag}_three_op_bench.
 python tools/score_bench.py > $out/${tag}_score_bench.json 2>/dev/null
 cp $out/${tag}_trace/t_kernel_stats.csv $out/${tag}_solver_step_kernel_stats.csv
 rm -rf $out/${tag}_trace $out/${tag}_sq $out/${tag}_traffic1 $out/${tag}_traffic2
-timeout 900 python bench.py > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err
+timeout 900 python bench.py --full > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err
 tail -3 $out/${tag}_prof.log; tail -3 $out/${tag}_traffic.log; head -30 $out/${tag}_counters.json
