@@ -355,12 +355,8 @@ __device__ __forceinline__ int lane_id() { return __lane_id(); }
 // wave reduction): inside a row of 16 lanes by DPP (quad permutes, a shift either way and a select, a half rotation),
 // across rows by gfx950's v_permlane16_swap / v_permlane32_swap (both operands the value itself: one result holds the
 // even rows / lower half twice, the other the odd rows / upper half twice; a lane takes the one it is not in).
-#ifndef EHR_DPP_XOR
-#define EHR_DPP_XOR 1  // 0: __shfl_xor (the A/B reference)
-#endif
 template <int K>
 __device__ __forceinline__ unsigned wave_xor_u32(unsigned v) {
-#if EHR_DPP_XOR
     const int iv = (int)v;
     if (K == 1) return (unsigned)__builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xf, 0xf, false);  // quad_perm:[1,0,3,2]
     if (K == 2) return (unsigned)__builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xf, 0xf, false);  // quad_perm:[2,3,0,1]
@@ -376,9 +372,6 @@ __device__ __forceinline__ unsigned wave_xor_u32(unsigned v) {
     }
     const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
     return (__lane_id() & 32) ? r[0] : r[1];
-#else
-    return (unsigned)__shfl_xor((int)v, K, 64);
-#endif
 }
 template <int K>
 __device__ __forceinline__ float wave_xor(float v) { return __uint_as_float(wave_xor_u32<K>(__float_as_uint(v))); }

@@ -32,7 +32,9 @@
 //   vb_composite_kernel one wave per tile that holds a job (every tile without a bound reference mask): sums the links'
 //                       values in link order, clamps, frame loss, mask write, back-propagates the tile's blended pairs
 //                       to 12 numbers per link in the view's fixed-point accumulators; its last-arriving workgroup runs
-//                       the finish stage (accumulators -> loss / grad_mvp [-> pose backward -> Adam]).
+//                       the finish stage (accumulators -> loss / grad_mvp [-> pose backward -> Adam]).  (Run at the end of
+//                       the job kernel's launch instead, behind a grid-wide barrier, it was no faster: DESIGN.md section 6,
+//                       profiles/experiments/r06_merged_job_composite.patch.)
 //
 // What runs once per rasterizer round or once per candidate cluster inside vb_job_kernel is kept free of LDS shuffles,
 // integer divisions and searches: wave scans and reductions by DPP / v_permlane*_swap,
@@ -78,8 +80,7 @@ constexpr u64 VB_EMPTY = ~0ull;
 
 // Counters that many waves hit with atomics each get a 128-byte line of their own behind the meta block (atomics on
 // one line serialise memory-side at ~12 ns each): line xcd = job cursor of that XCD.
-#define VB_LINES 36   // 0-7 job cursors of the XCDs, 8-15 composite arrival tickets of the XCDs, 16 the top ticket, 17 jobs put aside for vb_slow_kernel;
-                      // merged kernel: 18-25 "this XCD's workgroups are through their jobs", 26 the same over the XCDs, 27-34 the XCDs' go flags (= generation)
+#define VB_LINES 18   // 0-7 job cursors of the XCDs, 8-15 composite arrival tickets of the XCDs, 16 the top ticket, 17 jobs put aside for vb_slow_kernel
 __host__ __device__ __forceinline__ int* vb_line(int* meta, int k) {
     return (int*)((((uintptr_t)(meta + EHR_META_INTS)) + 127) & ~(uintptr_t)127) + 32 * k;
 }
@@ -135,75 +136,6 @@ __device__ __forceinline__ float4 vb_readlane(const float4& v, int lane) {
 }
 __device__ __forceinline__ int vb_mbcnt(u64 m) {  // set bits of m below this lane
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// ---- accesses that are coherent between the eight XCDs INSIDE one launch ------------------------------------------
-// The XCDs' L2s are not coherent with each other; between two launches the kernel boundary writes back and invalidates.
-// The merged job + composite kernel (round 6) hands job slots from the wave that resolved a job to whichever wave
-// composites its tile, possibly through another XCD's L2, in the middle of a launch: those words are written and read at
-// AGENT scope (relaxed atomics: the stores write through, the loads miss the non-coherent levels), ordered by the arrival
-// counters of the grid-wide barrier in between.  COH = false: plain accesses (the separate-launch forms).
-template <bool COH>
-__device__ __forceinline__ void vb_st_u64(void* p, u64 v) {
-    if (COH)
-        __hip_atomic_store((u64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        *(u64*)p = v;
-}
-template <bool COH>
-__device__ __forceinline__ u64 vb_ld_u64(const void* p) {
-    return COH ? __hip_atomic_load((const u64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *(const u64*)p;
-}
-template <bool COH>
-__device__ __forceinline__ void vb_st_i32(int* p, int v) {
-    if (COH)
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        *p = v;
-}
-template <bool COH>
-__device__ __forceinline__ int vb_ld_i32(const int* p) {
-    return COH ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-template <bool COH>
-__device__ __forceinline__ void vb_st_f4(float* p, const float4& v) {  // (16-byte aligned)
-    if (COH) {
-        vb_st_u64<true>(p, (u64)__float_as_uint(v.x) | ((u64)__float_as_uint(v.y) << 32));
-        vb_st_u64<true>(p + 2, (u64)__float_as_uint(v.z) | ((u64)__float_as_uint(v.w) << 32));
-    } else {
-        *reinterpret_cast<float4*>(p) = v;
-    }
-}
-template <bool COH>
-__device__ __forceinline__ float4 vb_ld_f4(const float* p) {
-    if (COH) {
-        const u64 a = vb_ld_u64<true>(p), b = vb_ld_u64<true>(p + 2);
-        return make_float4(__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b),
-                           __uint_as_float((unsigned)(b >> 32)));
-    }
-    return *reinterpret_cast<const float4*>(p);
-}
-template <bool COH>
-__device__ __forceinline__ void vb_st_item(VbItem* p, const VbItem& it) {
-    if (COH) {
-        vb_st_u64<true>(p, (u64)(unsigned)it.packed | ((u64)(unsigned)it.v1 << 32));
-        vb_st_u64<true>((char*)p + 8, (u64)(unsigned)it.v2 | ((u64)__float_as_uint(it.alpha) << 32));
-    } else {
-        *p = it;
-    }
-}
-template <bool COH>
-__device__ __forceinline__ VbItem vb_ld_item(const VbItem* p) {
-    if (COH) {
-        const u64 a = vb_ld_u64<true>(p), b = vb_ld_u64<true>((const char*)p + 8);
-        VbItem it;
-        it.packed = (int)(unsigned)a;
-        it.v1 = (int)(unsigned)(a >> 32);
-        it.v2 = (int)(unsigned)b;
-        it.alpha = __uint_as_float((unsigned)(b >> 32));
-        return it;
-    }
-    return *p;
 }
 
 // ---- stage 1: vertices, screen boxes of triangles / clusters / links ---------------------------------------------
@@ -650,26 +582,14 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
 __device__ __forceinline__ int vb_div_rw(int i) { return (int)(__umul24((unsigned)i, 1928u) >> 16); }
 static_assert(VB_RW == 34, "vb_div_rw");
 // ---- wave scans without LDS (DPP): four shifts inside the rows of 16 lanes, then the rows' totals into the rows above
-#ifndef VB_FAST_SEARCH
-#define VB_FAST_SEARCH 1  // 0: the scans as six ds_bpermute steps and the walkers' start as a binary search over the prefix table
-#endif
 #define VB_DPP_(v, ctrl, rows) __builtin_amdgcn_update_dpp(0, (v), (ctrl), (rows), 0xf, false)
 __device__ __forceinline__ int vb_scan_add(int v) {  // inclusive sum
-#if VB_FAST_SEARCH
     v += VB_DPP_(v, 0x111, 0xf);  // row_shr:1
     v += VB_DPP_(v, 0x112, 0xf);  // row_shr:2
     v += VB_DPP_(v, 0x114, 0xf);  // row_shr:4
     v += VB_DPP_(v, 0x118, 0xf);  // row_shr:8
     v += VB_DPP_(v, 0x142, 0xa);  // row_bcast:15 -> rows 1 and 3
     v += VB_DPP_(v, 0x143, 0xc);  // row_bcast:31 -> rows 2 and 3
-#else
-    const int lane = lane_id();
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-#endif
     return v;
 }
 __device__ __forceinline__ int vb_scan_max(int v) {  // inclusive maximum of values >= 0
@@ -1029,9 +949,7 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
     const int incl = vb_scan_add(packed);
     const int Ptot = vb_readlane(incl, 63);
     const int Stot = Ptot & 0xffff, Wtot = Ptot >> 16;
-#if VB_FAST_SEARCH
     const u64 nzu = __ballot(units > 0), nzs = __ballot(srows > 0);  // triangles with units / with span rows
-#endif
     cost += Stot + 3 * Wtot + 256;  // what the job costs a wave: a step per 64 units, three per 64 span rows, about four per round
 #ifdef VB_TIMELINE
     if (lane == 0) {
@@ -1050,7 +968,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
         int j = 0, bw = 1, bh = 1, gw = 1, gx = 0, dy = 0, crow = 0, ccol0 = 0;
         unsigned eb = 0, lastm = 15u;  // lastm: the pixels of a row's last unit that lie inside the box
         int e0 = -1, e1 = -1, e2 = -1, sx0 = 0, sx1 = 0, sx2 = 0, sy0 = 0, sy1 = 0, sy2 = 0, er0 = 0, er1 = 0, er2 = 0;
-#if VB_FAST_SEARCH
         // Which triangle does a lane start in?  Asked the other way round: triangle j's units begin at pre[j]; the first
         // lane to start at or after that is ceil(pre[j] / K), and if that start still lies inside the triangle, j puts its
         // number there.  A lane's triangle is the last number at or below its own place: a max-scan.  (One LDS round
@@ -1067,19 +984,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
             j = vb_scan_max((int)own[lane]) - 1;
         }
         if (start < end) {
-#else
-        if (start < end) {
-            int lo = 0, hi = 63;
-#pragma unroll
-            for (int it = 0; it < 6; it++) {
-                const int mid = (lo + hi + 1) >> 1;
-                if ((R.pre[mid] & 0xffff) <= start)
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
-            j = lo;
-#endif
             const unsigned b4 = R.box[j];
             ccol0 = b4 & 255;
             const int y0r = (b4 >> 8) & 255;
@@ -1093,11 +997,7 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
             sx1 = -16 * (int)(short)(w1 >> 16); sy1 = 16 * (int)(short)(w1 & 0xffffu);
             sx2 = -16 * (int)(short)(w2 >> 16); sy2 = 16 * (int)(short)(w2 & 0xffffu);
             const int o = start - (R.pre[j] & 0xffff);
-#if VB_FAST_SEARCH
             dy = vb_div_small(o, __builtin_amdgcn_rcpf((float)gw));
-#else
-            dy = o / gw;
-#endif
             gx = o - __mul24(dy, gw);  // (|s*| < 2^20, dy < 2^7, gx < 4: 24-bit operands, full-rate multiplies)
             er0 = R.e[j][0] + __mul24(dy, sy0);
             er1 = R.e[j][1] + __mul24(dy, sy1);
@@ -1168,13 +1068,7 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
                         e1 = er1;
                         e2 = er2;
                         if (dy == bh) {  // next job with a non-empty box
-#if VB_FAST_SEARCH
                             j = vb_next_set(nzu, j);
-#else
-                            do {
-                                j++;
-                            } while (((R.pre[j + 1] ^ R.pre[j]) & 0xffff) == 0);
-#endif
                             const unsigned b4 = R.box[j];
                             ccol0 = b4 & 255;
                             crow = (b4 >> 8) & 255;
@@ -1228,7 +1122,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
                 er2 = R.e[jj][2];
                 dy = 0;
             };
-#if VB_FAST_SEARCH
             {
                 const float invK = __builtin_amdgcn_rcpf((float)K2);
                 const int pj = (incl - packed) >> 16, uj = packed >> 16;
@@ -1240,19 +1133,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
                 j = vb_scan_max((int)own[lane]) - 1;
             }
             if (s2 < e2) {
-#else
-            if (s2 < e2) {
-                int lo = 0, hi = 63;
-#pragma unroll
-                for (int it = 0; it < 6; it++) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if ((R.pre[mid] >> 16) <= s2)
-                        lo = mid;
-                    else
-                        hi = mid - 1;
-                }
-                j = lo;
-#endif
                 load_tri(j);
                 dy = s2 - (R.pre[j] >> 16);
                 er0 += __mul24(dy, sy0);
@@ -1300,13 +1180,7 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
                         er1 += sy1;
                         er2 += sy2;
                         if (dy == bh) {
-#if VB_FAST_SEARCH
                             j = vb_next_set(nzs, j);
-#else
-                            do {
-                                j++;
-                            } while ((R.pre[j + 1] >> 16) == (R.pre[j] >> 16));
-#endif
                             load_tri(j);
                         }
                     }
@@ -1339,13 +1213,7 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
                     er1 += sy1;
                     er2 += sy2;
                     if (dy == bh) {  // next triangle of this class
-#if VB_FAST_SEARCH
                         j = vb_next_set(nzs, j);
-#else
-                        do {
-                            j++;
-                        } while ((R.pre[j + 1] >> 16) == (R.pre[j] >> 16));
-#endif
                         load_tri(j);
                     }
                 }
@@ -1568,32 +1436,27 @@ __device__ __forceinline__ int vb_job_raster(const VbJobArgs& A, VbWaveLds& W_, 
     return drawn ? 1 : 0;
 }
 
-// A drawn job leaves, in its slot, the coverage rows of its region and the triangle id of every pixel the depth test ran
-// for (all-ones elsewhere), then its descriptor; the resolve kernel takes it from there (an undrawn job's descriptor is
-// -1).  No list of drawn jobs: appending to one costs every job a returning atomic (~3 us under load), and three
-// quarters of the jobs are drawn anyway.
-// (part / nparts: the words this wave writes -- 0 / 1 for a job of its own; the four waves of a heavy job share them)
+// A job vb_job_slow drew leaves, in its slot, the coverage rows of its region and the triangle id of every pixel the depth
+// test ran for (all-ones elsewhere), then its descriptor; vb_resolve_kernel takes it from there.
 __device__ __forceinline__ void vb_publish(const VbJobArgs& A, const u64* key_, const u64* cov_, int job, int u, int tx,
-                                           int ty, int part = 0, int nparts = 1) {
+                                           int ty) {
     const int lane = lane_id();
     VB_WAVE_SYNC();
     unsigned* const dst = A.jid + (size_t)job * VB_RN;
 #pragma unroll
     for (int k = 0; k < VB_WORDS; k++) {
-        if (nparts > 1 && (k % nparts) != part) continue;
         const unsigned i = 64u * k + lane;
         if (i < (unsigned)VB_RN) dst[i] = (unsigned)key_[i];  // low word = triangle id; all-ones stays all-ones
     }
     // coverage in region-linear order (bit i = region pixel i), what the resolve kernel's bit arithmetic works on
 #pragma unroll
     for (int k = 0; k < VB_WORDS; k++) {
-        if (nparts > 1 && (k % nparts) != part) continue;
         const unsigned i = 64u * k + lane;
         const unsigned row = (unsigned)vb_div_rw((int)i), col = i - row * VB_RW;
         const u64 w = __ballot(i < (unsigned)VB_RN && ((cov_[row < (unsigned)VB_RH ? row : 0] >> col) & 1ull));
         if (lane == 0) A.jcov[(size_t)job * VB_WORDS + k] = w;
     }
-    if (lane == 0 && part == 0) A.jdesc[job] = u | (tx << 9) | (ty << 19);
+    if (lane == 0) A.jdesc[job] = u | (tx << 9) | (ty << 19);
 }
 
 // A whole job on one wave with the general triangle path compiled in (near-plane clipping, 64-bit edge functions): what a
@@ -1642,14 +1505,13 @@ __device__ __forceinline__ void vb_job_slow(const VbJobArgs& A, VbWaveLds& S, in
 // overflow bit 4, so loss and gradient come out NaN and the optimiser state stays as it was; ehr_fused_status() returns
 // EHR_ERR_RETRY and switches the pass on for the context's later calls.
 #define VB_FLAG_NEED_SLOW 4
-template <bool COH = false>
 __device__ __forceinline__ void vb_put_aside(int4* __restrict__ slow_list, int* __restrict__ meta, int* __restrict__ jn,
                                              int* __restrict__ jdesc, int job, int u, int tx, int ty) {
     if (slow_list) {
         slow_list[atomicAdd(vb_line(meta, 17), 1)] = make_int4(job, u, tx, ty);
     } else {
         atomicOr(&meta[EHR_META_OVERFLOW], VB_FLAG_NEED_SLOW);
-        vb_st_i32<COH>(&jn[job], -1);
+        jn[job] = -1;
         jdesc[job] = -1;
     }
 }
@@ -1679,7 +1541,7 @@ struct VbResolveArgs {
 // (jitems) and their number (jn; -1 = the link contributes nothing here).  pairA [2 * VB_RN] and hits [2 * VB_RN] are the
 // wave's LDS work areas.  Called by the job kernel right after a job's depth tests (the ids never leave LDS) and by
 // vb_resolve_kernel for the jobs vb_slow_kernel drew.
-template <bool COH = false, bool LAZY = false>
+template <bool LAZY = false>
 __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const unsigned* ids, float* pairA,
                                                unsigned short* hits, const u64 (&C)[VB_WORDS], size_t slot, int b,
                                                int l, int rx0, int ry0) {
@@ -1764,12 +1626,12 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
         const VbVertsT<LAZY> pv = vb_verts<LAZY>(pvz);
         for (int hbase = 0; hbase < nh; hbase += 64) {
             const int h = hbase + lane;
+            bool keep = false;
             VbItem it;
             it.packed = 0;
             it.v1 = 0;
             it.v2 = 0;
             it.alpha = 0.f;
-            bool keep = false;
             if (h < nh) {
                 const int hq = hits[h];
                 const int d = hq >> 15, q = hq & 0x7fff;
@@ -1820,11 +1682,9 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
                 if (spill_base >= 0 && spill_base < spill_cap) room += min(VB_SPILL_BLOCK, spill_cap - spill_base);
                 if (keep) {
                     if (at < VB_JOB_ITEMS)
-                        vb_st_item<COH>(&jitems[slot * VB_JOB_ITEMS + at], it);
+                        jitems[slot * VB_JOB_ITEMS + at] = it;
                     else if (at < room)
-                        vb_st_item<COH>(&spill[spill_base + (at - VB_JOB_ITEMS)], it);
-                    else if (COH)
-                        atomicOr(&meta[EHR_META_OVERFLOW], 1);
+                        spill[spill_base + (at - VB_JOB_ITEMS)] = it;
                     else
                         meta[EHR_META_OVERFLOW] = 1;  // reported through loss = NaN, never silent
                 }
@@ -1861,10 +1721,11 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
     }
     // ---- publish: the link's value at the tile's pixels (tile-local row-major), the number of blended pairs
     const bool nz = __ballot(val[0] != 0.f || val[1] != 0.f || val[2] != 0.f || val[3] != 0.f) != 0;
-    if (nz) vb_st_f4<COH>(jval + slot * 256 + r * EHR_TILE_W + c4, make_float4(val[0], val[1], val[2], val[3]));
+    if (nz) *reinterpret_cast<float4*>(jval + slot * 256 + r * EHR_TILE_W + c4) = make_float4(val[0], val[1], val[2], val[3]);
     if (lane == 0) {
-        vb_st_i32<COH>(&jn[slot], nz ? nitems : -1);
-        if (nitems > VB_JOB_ITEMS) vb_st_i32<COH>(&jspill[slot], spill_base);
+        int* const n_out = &jn[slot];
+        *n_out = nz ? nitems : -1;
+        if (nitems > VB_JOB_ITEMS) jspill[slot] = spill_base;
     }
 #undef KT
 }
@@ -1874,7 +1735,7 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
 // Nothing of the job's region goes through global memory, and the resolve stage needs no launch of its own: it was a
 // 10 us kernel of one dependent chain per job behind a boundary; here the chain runs while other waves still rasterize.
 // (Resolve and rasterizer never overlap inside a wave: the live ranges of the two are disjoint, unlike round 2's fusion.)
-template <bool COH = false, bool LAZY = false>
+template <bool LAZY = false>
 __device__ __forceinline__ void vb_resolve_from_lds(const VbResolveArgs& Q, VbWaveLds& S, u64* key, const u64* cov, size_t slot,
                                                     int b, int l, int rx0, int ry0) {
     const int lane = lane_id();
@@ -1900,7 +1761,7 @@ __device__ __forceinline__ void vb_resolve_from_lds(const VbResolveArgs& Q, VbWa
         const unsigned i = 64u * k + lane;
         if (i < (unsigned)VB_RN) ids[i] = idw[k];
     }
-    vb_resolve_job<COH, LAZY>(Q, ids, reinterpret_cast<float*>(key), reinterpret_cast<unsigned short*>(&S.R), C, slot, b, l, rx0, ry0);
+    vb_resolve_job<LAZY>(Q, ids, reinterpret_cast<float*>(key), reinterpret_cast<unsigned short*>(&S.R), C, slot, b, l, rx0, ry0);
     VB_WAVE_SYNC();
 }
 
@@ -1940,9 +1801,7 @@ struct VbCompArgs {  // what the composite stage needs besides its LDS tables
 
 // The composite stage's work items of ONE wave (slot `wslot` of the `nslots` wave slots its XCD has; `nwg` workgroups in
 // all): see vb_composite_kernel.  s_jbase / s_utile: the (view, link) tables in LDS; gpix: 256 floats of LDS of this wave.
-// COH: the job slots are read at agent scope (the merged kernel: they were written earlier in the SAME launch, possibly
-// through another XCD's L2).
-template <bool COH, bool FILL>
+template <bool FILL>
 __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const int* s_jbase, const unsigned* s_utile, float* gpix,
                                                    int xcd, int wslot, int nslots, int nwg) {
     const BinGeom& g = C.g;
@@ -2026,7 +1885,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
             const int tx0 = ut & 1023u, ty0 = (ut >> 10) & 4095u, nx = ut >> 22;
             if (n > 0 && tx >= tx0 && tx < tx0 + nx && ty >= ty0 && (ty - ty0) * nx < n) {
                 myslot = j0 + (ty - ty0) * nx + (tx - tx0);
-                if (myslot < jcap) myn = vb_ld_i32<COH>(&jn[myslot]);
+                if (myslot < jcap) myn = jn[myslot];
             }
         }
         tmask = (unsigned)__ballot(myn >= 0);  // links that contribute a value here
@@ -2061,7 +1920,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         const int l = __ffs(todo) - 1;
         todo &= todo - 1;
         const size_t slot = (size_t)vb_readlane(myslot, l);
-        const float4 v4 = vb_ld_f4<COH>(jval + slot * 256 + r * EHR_TILE_W + c4);
+        const float4 v4 = *reinterpret_cast<const float4*>(jval + slot * 256 + r * EHR_TILE_W + c4);
         acc[0] += v4.x;
         acc[1] += v4.y;
         acc[2] += v4.z;
@@ -2116,7 +1975,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         int n = vb_readlane(myn, l);
         int sbase = 0;
         if (n > VB_JOB_ITEMS) {  // the rest of the list lives in the spill pool; never read outside it
-            sbase = vb_ld_i32<COH>(&jspill[slot]);
+            sbase = jspill[slot];
             if (sbase < 0 || sbase >= spill_cap) n = VB_JOB_ITEMS;
             else n = min(n, VB_JOB_ITEMS + (spill_cap - sbase));
         }
@@ -2125,7 +1984,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
 #pragma unroll
         for (int k = 0; k < 12; k++) G[k] = 0.f;
         for (int i = lane; i < n; i += 64) {
-            const VbItem itm = vb_ld_item<COH>((i < VB_JOB_ITEMS) ? &jitems[slot * VB_JOB_ITEMS + i] : &spill[sbase + (i - VB_JOB_ITEMS)]);
+            const VbItem itm = *((i < VB_JOB_ITEMS) ? &jitems[slot * VB_JOB_ITEMS + i] : &spill[sbase + (i - VB_JOB_ITEMS)]);
             const int q = itm.packed & 1023, d = (itm.packed >> 10) & 1;
             const int tri1 = (itm.packed >> 13) & 1;
             const float dc = ((itm.packed >> 14) & 1) ? 1.f : -1.f;
@@ -2186,17 +2045,11 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
 #ifndef VB_JOB_WAVES
 #define VB_JOB_WAVES 4
 #endif
-#ifndef VB_INLINE_RESOLVE
-#define VB_INLINE_RESOLVE 1   // 0: the round-4 chain (jobs publish ids + coverage, vb_resolve_kernel resolves every slot)
-#endif
-// The job kernel's parameters, ONE struct in the kernarg segment.  VB_PARAM_BLOCK = 1: the kernel does not name its
-// parameter; it reads the fields through the kernarg segment pointer, made opaque to the optimiser at every use
-// (vb_job_params), so that a field is a scalar load where it is needed instead of one of ~60 scalar registers filled at
-// kernel entry and kept -- i.e. spilled to vector-register lanes and reloaded -- across the whole job loop (round 4: 237
-// spilled SGPRs in this kernel).  VB_PARAM_BLOCK = 0: ordinary by-value use of the same struct (the A/B reference).
-#ifndef VB_PARAM_BLOCK
-#define VB_PARAM_BLOCK 1
-#endif
+// The job kernel's parameters, ONE struct in the kernarg segment.  The kernel does not name its parameter; it reads the
+// fields through the kernarg segment pointer, made opaque to the optimiser at every use (vb_job_params), so that a field
+// is a scalar load where it is needed instead of one of ~60 scalar registers filled at kernel entry and kept -- i.e.
+// spilled to vector-register lanes and reloaded -- across the whole job loop (by-value use, round 4: 237 spilled SGPRs
+// in this kernel).
 struct VbJobParams {
     BinGeom g;
     int B;
@@ -2222,14 +2075,6 @@ struct VbJobParams {
     int4* slow_list;
     int heavy_t, med_t0;
     VbResolveArgs rq;
-    // MERGE (round 6): the composite + finish stages run at the end of this launch
-    VbCompArgs ca;
-    const long long* vtot;
-    const int* ref_flag;
-    float* loss;
-    float* grad_mvp;
-    int* lbox_all;
-    StepTail tail;
 };
 typedef const VbJobParams __attribute__((address_space(4)))* VbJobParamsPtr;
 __device__ __forceinline__ VbJobParamsPtr vb_job_params() {
@@ -2237,19 +2082,6 @@ __device__ __forceinline__ VbJobParamsPtr vb_job_params() {
     asm volatile("" : "+s"(p));  // (what the optimiser cannot see through it cannot hoist to the kernel's entry)
     return p;
 }
-// a whole parameter sub-struct out of the kernarg segment (word by word: the segment's address space has no copy constructor)
-template <class T>
-__device__ __forceinline__ T vb_load_pod(const T __attribute__((address_space(4)))* p) {
-    static_assert(sizeof(T) % 4 == 0, "vb_load_pod");
-    T out;
-    const int __attribute__((address_space(4)))* const src = (const int __attribute__((address_space(4)))*)p;
-    int* const dst = reinterpret_cast<int*>(&out);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 4; i++) dst[i] = src[i];
-    return out;
-}
-template <class T>
-__device__ __forceinline__ T vb_load_pod(const T* p) { return *p; }
 template <class P>
 __device__ __forceinline__ VbResolveArgs vb_load_rq(P p) {
     VbResolveArgs q;
@@ -2261,29 +2093,13 @@ __device__ __forceinline__ VbResolveArgs vb_load_rq(P p) {
 }
 // COVER (the scoring op): jcov = the (view, tile) coverage words [B][nt][4] the jobs OR their tile's interior into, jn = one
 // sticky flag raised by a job that met a triangle whose depth class does not let coverage decide; no slots, no lists.
-// MERGE (round 6, solver step with a bound reference mask and no mask output, one chunk of views, general-triangle pass off):
-// the composite and finish stages run at the END OF THIS LAUNCH instead of in a launch of their own.  All workgroups of the
-// grid are resident together (four per CU by registers and LDS, the grid is four per CU), so a grid-wide arrival counter is
-// safe: a workgroup whose waves have run out of jobs waits until its slots' stores have been performed, arrives (a ticket per
-// XCD, then one over the XCDs), sleeps on its XCD's go flag, and then takes composite items like a workgroup of
-// vb_composite_kernel would -- tables already in LDS, no launch boundary (cache write-back + invalidate, dispatch, tables:
-// 13 of that launch's 18 us were not tile work).  Job slots travel at agent scope (vb_st_* / vb_ld_*<true>).  A wait that
-// does not end (a grid that is not resident after all) is REPORTED through the overflow flag after ~50 ms, never a hang.
-template <bool COVER, bool MERGE = false, bool LAZY = false>
+template <bool COVER, bool LAZY = false>
 __global__ void __launch_bounds__(256, VB_JOB_WAVES)
-vb_job_kernel(VbJobParams prm_) {
+vb_job_kernel(VbJobParams) {
     __shared__ VbWaveLds lds_all[4];
     // PRM(field): a kernel parameter, read where it is used (see VbJobParams)
-#if VB_PARAM_BLOCK
 #define PRM(f) (vb_job_params()->f)
 #define VB_RQ() vb_load_rq(vb_job_params())
-#else
-#define PRM(f) (prm_.f)
-#define VB_RQ() vb_load_rq(&prm_)
-#endif
-#ifdef VB_MERGE_TL
-    const long long tl_start0 = wall_clock64();
-#endif
     const int W = PRM(g.W), H = PRM(g.H), L = PRM(g.L), gnt = PRM(g.nt), gntx = PRM(g.ntx);
     const int B = PRM(B), V = PRM(V), dbg = PRM(dbg);
     int heavy_t = max(PRM(heavy_t), PRM(hv.gen)[6]);  // (the value in force: the vertex kernel adapts it, see VbHeavy)
@@ -2473,7 +2289,6 @@ vb_job_kernel(VbJobParams prm_) {
         if (!(any_drawn & 2) && dln > 0)
             vb_flush<false, LAZY>(S, S0.key, S0.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
         __syncthreads();
-#if VB_INLINE_RESOLVE
         if (!COVER && any_drawn == 1) {
             hres_job = job;
             hres_b = b;
@@ -2481,15 +2296,12 @@ vb_job_kernel(VbJobParams prm_) {
             hres_rx0 = rx0;
             hres_ry0 = ry0;
         }
-#else
-        if (any_drawn == 1) vb_publish(A, S0.key, S0.cov, job, u, tx, ty, wave, 4);  // every wave its share of the words
-#endif
         if (wave == 0) {
             if (any_drawn & 2) {  // put aside for vb_slow_kernel
-                if (lane == 0) vb_put_aside<MERGE>(PRM(slow_list), PRM(meta), PRM(jn), PRM(jdesc), job, u, tx, ty);
+                if (lane == 0) vb_put_aside(PRM(slow_list), PRM(meta), PRM(jn), PRM(jdesc), job, u, tx, ty);
             } else if (any_drawn) {
             } else if (lane == 0) {
-                vb_st_i32<MERGE>(&PRM(jn)[job], -1);
+                PRM(jn)[job] = -1;
                 PRM(jdesc)[job] = -1;
             }
             if (lane == 0) {
@@ -2507,10 +2319,8 @@ vb_job_kernel(VbJobParams prm_) {
         __syncthreads();
     }
 
-#if VB_INLINE_RESOLVE
     // (the loop's last barrier is behind us: waves 1-3 go on to their own jobs, nobody touches wave 0's LDS but wave 0)
-    if (!COVER && wave == 0 && hres_job >= 0) vb_resolve_from_lds<MERGE, LAZY>(VB_RQ(), S, S.key, S.cov, (size_t)hres_job, hres_b, hres_l, hres_rx0, hres_ry0);
-#endif
+    if (!COVER && wave == 0 && hres_job >= 0) vb_resolve_from_lds<LAZY>(VB_RQ(), S, S.key, S.cov, (size_t)hres_job, hres_b, hres_l, hres_rx0, hres_ry0);
 #if VB_PRIO_HEAVY
     __builtin_amdgcn_s_setprio(0);
 #endif
@@ -2654,7 +2464,7 @@ vb_job_kernel(VbJobParams prm_) {
             continue;
         }
         if (drawn < 0) {  // a triangle for the general path (near-plane clipping, huge extent): put the job aside
-            if (lane == 0) vb_put_aside<MERGE>(PRM(slow_list), PRM(meta), PRM(jn), PRM(jdesc), job, u, tx, ty);
+            if (lane == 0) vb_put_aside(PRM(slow_list), PRM(meta), PRM(jn), PRM(jdesc), job, u, tx, ty);
             continue;
         }
         if (dln > 0) vb_flush<false, LAZY>(S, S.key, S.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
@@ -2672,7 +2482,7 @@ vb_job_kernel(VbJobParams prm_) {
         }
         if (drawn == 0) {  // the link's box touches this tile, its triangles do not
             if (lane == 0) {
-                vb_st_i32<MERGE>(&PRM(jn)[slot], -1);
+                PRM(jn)[slot] = -1;
                 PRM(jdesc)[slot] = -1;
             }
             continue;
@@ -2680,11 +2490,7 @@ vb_job_kernel(VbJobParams prm_) {
 #ifdef VB_TIMELINE
         const long long tl_j2 = __builtin_readcyclecounter();
 #endif
-#if VB_INLINE_RESOLVE
-        vb_resolve_from_lds<MERGE, LAZY>(VB_RQ(), S, S.key, S.cov, slot, b, l, rx0, ry0);
-#else
-        vb_publish(A, S.key, S.cov, job, u, tx, ty);
-#endif
+        vb_resolve_from_lds<LAZY>(VB_RQ(), S, S.key, S.cov, slot, b, l, rx0, ry0);
 #ifdef VB_TIMELINE
         tl_last[3] = wall_clock64();  // resolved
         if (lane == 0) {
@@ -2718,72 +2524,6 @@ vb_job_kernel(VbJobParams prm_) {
         ty[4] = tl_dry;
     }
 #endif
-    if (MERGE && !COVER) {
-        // ---- the grid-wide hand-over.  Every wave first waits until its own slot stores have been performed (agent scope:
-        //      written through), the workgroup arrives, then sleeps on its XCD's go flag (= this step's generation).
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* const meta = PRM(meta);
-#ifdef VB_MERGE_TL  // profiling build: when this workgroup arrived, was let go, finished its items, [finished the finish stage]
-        long long* const mtl = PRM(timeline) + 8 * (size_t)blockIdx.x;
-        if (tid == 0) {
-            mtl[0] = tl_start0;
-            mtl[1] = wall_clock64();
-        }
-#endif
-        if (tid == 0) {
-            if (atomicAdd(vb_line(meta, 18 + xcd), 1) == G8 - 1 && atomicAdd(vb_line(meta, 26), 1) == 7)
-                for (int k = 0; k < 8; k++) __hip_atomic_store(vb_line(meta, 27 + k), gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int spins = 0;
-            while (__hip_atomic_load(vb_line(meta, 27 + xcd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gen) {
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > (1 << 16)) {  // (~50-100 ms: the grid is not resident together after all -- reported, never a hang)
-                    atomicOr(&meta[EHR_META_OVERFLOW], 8);
-                    break;
-                }
-            }
-        }
-        __syncthreads();
-#ifdef VB_MERGE_TL
-        if (tid == 0) mtl[2] = wall_clock64();
-#endif
-        // ---- composite stage (vb_composite_kernel's items, this XCD's eighth of them dealt over its waves)
-        const VbCompArgs C = vb_load_pod(&PRM(ca));
-        {   // the links' screen boxes start "empty" in the next step (nobody reads them after the prologue above)
-            int* const lbox_all = PRM(lbox_all);
-            for (int i = (int)blockIdx.x * 256 + tid; i < 16 * B * L; i += (int)gridDim.x * 256) lbox_all[i] = (i & 2) ? INT_MIN : INT_MAX;
-        }
-        // (items beyond a wave's first one claimed from a per-XCD cursor instead of dealt: measured, 72.2 -> 75.3 us at 8 views and
-        //  278 -> 326 us at 64 -- every wave ends on a claim, 512 same-address atomics per XCD at ~12 ns each)
-        vb_composite_items<true, false>(C, upre, utile, reinterpret_cast<float*>(S.key), xcd, kx * 4 + wave, G8 * 4, (int)gridDim.x);
-        // ---- the workgroup whose atomics are performed last runs the finish stage (as in vb_composite_kernel)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#ifdef VB_MERGE_TL
-        if (tid == 0) {
-            mtl[3] = wall_clock64();
-            mtl[4] = 0;
-        }
-#endif
-        if (tid == 0) {
-            int last = 0;
-            if (atomicAdd(vb_line(meta, 8 + xcd), 1) == G8 - 1) last = atomicAdd(vb_line(meta, 16), 1) == 7;
-            s_heavy[0] = last;  // (the heavy phase's flag word: idle since that phase)
-        }
-        __syncthreads();
-        if (!s_heavy[0]) return;
-        const int* const ref_flag = PRM(ref_flag);
-        if (ref_flag && tid == 0 && ref_flag[0]) atomicOr(&meta[EHR_META_OVERFLOW], 1);  // the bound reference's own sums overflowed
-        __syncthreads();
-        const StepTail tail = vb_load_pod(&PRM(tail));
-        finish_body<true>(C.g, B, C.facc, PRM(vtot), PRM(loss), PRM(grad_mvp), meta, tail, C.nls, nullptr, VB_LOSS_STRIDE,
-                          reinterpret_cast<float*>(lds_all[0].key), reinterpret_cast<double(*)[17]>(lds_all[1].key),
-                          reinterpret_cast<float*>(lds_all[2].key), reinterpret_cast<float(*)[16]>(lds_all[3].key));
-#ifdef VB_MERGE_TL
-        __syncthreads();
-        if (tid == 0) mtl[4] = wall_clock64();
-#endif
-    }
 }
 #undef PRM
 #undef VB_RQ
@@ -2824,12 +2564,10 @@ vb_slow_kernel(BinGeom g, VbClusters cl, VbRecs rc, const float* __restrict__ ve
     }
 }
 
-// Stage 2b, as a kernel of its own: one WAVE per drawn job whose coverage and triangle ids were PUBLISHED to its slot
-// (jid / jcov / jdesc) instead of being resolved by the wave that drew it.  Since round 5 the job kernel resolves its jobs
-// itself, straight from LDS (vb_resolve_job above); what is left for this kernel are the jobs vb_slow_kernel redrew with
-// the general triangle path (slow_list != NULL: exactly those), i.e. normally nothing -- the solver step only launches it
-// together with vb_slow_kernel.  slow_list == NULL: every job slot of the chunk (the round-4 form of the chain, kept as
-// the A/B reference: -DVB_INLINE_RESOLVE=0).
+// Stage 2b (normally empty): the resolve stage of the jobs vb_slow_kernel redrew with the general triangle path, one WAVE
+// per entry of slow_list.  Those jobs PUBLISHED their coverage and triangle ids to their slot (jid / jcov / jdesc); every
+// other job was resolved by the job kernel's wave that drew it, straight from LDS (vb_resolve_from_lds).  The solver step
+// launches this kernel only together with vb_slow_kernel.
 __global__ void __launch_bounds__(256)
 vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float* __restrict__ mvp,
                   const float4* __restrict__ posc, int V, int T, const int4* __restrict__ tri4,
@@ -2843,16 +2581,9 @@ vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float
     VbResolveLds& S = lds_all[wave];
     const int W = g.W, H = g.H, L = g.L;
     (void)B;
-    // XCD-aware like the job kernel (workgroup w runs on XCD w % 8; the slots of an eighth of the job list were written
-    // through that XCD's L2), one job per wave and turn
-    const bool listed = slow_list != nullptr;
-    const int total = min(meta[5], jcap), per_xcd = (total + 7) >> 3, xcd = blockIdx.x & 7;
-    const int jbeg = xcd * per_xcd, jend = min(jbeg + per_xcd, total);
-    const int it0 = listed ? (int)blockIdx.x * 4 + wave : jbeg + (int)(blockIdx.x >> 3) * 4 + wave;
-    const int it1 = listed ? *vb_line(meta, 17) : jend;
-    const int step = listed ? (int)gridDim.x * 4 : (int)(gridDim.x >> 3) * 4;
-    for (int it = it0; it < it1; it += step) {
-        const int job = listed ? slow_list[it].x : it;
+    const int n = *vb_line(meta, 17);  // jobs put aside (vb_put_aside)
+    for (int it = (int)blockIdx.x * 4 + wave; it < n; it += (int)gridDim.x * 4) {
+        const int job = slow_list[it].x;
         if (job >= jcap) continue;
         const size_t slot = (size_t)job;
         // the ids are requested together with the descriptor (one round trip; an undrawn slot holds stale ids, unused)
@@ -2891,9 +2622,9 @@ vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float
         Q.spill = spill; Q.meta = meta; Q.V = V; Q.T = T; Q.W = W; Q.H = H; Q.spill_cap = spill_cap; Q.want_grad = want_grad;
         Q.dbg = dbg;
         if (posc)
-            vb_resolve_job<false, false>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
+            vb_resolve_job<false>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
         else
-            vb_resolve_job<false, true>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
+            vb_resolve_job<true>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
     }
 }
 
@@ -2993,7 +2724,7 @@ vb_composite_kernel(BinGeom g, int B, const float* __restrict__ mvp, int V, cons
     C.jcap = jcap; C.ref = ref; C.mask = mask; C.facc = facc; C.nls = nls; C.want_grad = want_grad; C.vec_ok = vec_ok;
     C.spill = spill; C.spill_cap = spill_cap; C.meta = meta; C.dbg = dbg; C.tsum = tsum;
     const int nwg = gridDim.x, xcd = blockIdx.x & 7;
-    vb_composite_items<false, FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> 3) * 4 + wave, (nwg >> 3) * 4, nwg);
+    vb_composite_items<FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> 3) * 4 + wave, (nwg >> 3) * 4, nwg);
     // ---- the workgroup whose atomics are performed last runs the finish stage.  Every wave first waits until its own
     //      atomics have been performed (vmcnt covers them), then one lane takes a ticket on the XCD's counter and the
     //      last of an XCD one on the top counter: two levels, because a few thousand arrivals on ONE address serialise
@@ -3368,27 +3099,6 @@ int ehr::vbuf_meta_read(ehr_ctx* ctx, int* meta4) {
         for (int k = 0; k < 8; k++)
             EHR_HIP(hipMemcpy(&cur[k], vb_line((int*)((char*)ctx->vb_acc.ptr + off), k), sizeof(int), hipMemcpyDeviceToHost));
         fprintf(stderr, "[ehr vbuf] job cursors %d %d %d %d %d %d %d %d\n", cur[0], cur[1], cur[2], cur[3], cur[4], cur[5], cur[6], cur[7]);
-#ifdef VB_MERGE_TL
-        {   // merged kernel: per workgroup [start, arrived, let go, items done, finish done] on the 100 MHz clock
-            const int nwg = ((ctx->num_cus * 4) + 7) & ~7;
-            std::vector<long long> tl((size_t)8 * nwg);
-            EHR_HIP(hipMemcpy(tl.data(), ctx->vb_spill.ptr, tl.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            long long t0 = tl[0], a_last = 0, go_first = 1ll << 62, go_last = 0, it_last = 0, fin = 0;
-            double a_mean = 0, it_mean = 0;
-            for (int i = 0; i < nwg; i++) t0 = std::min(t0, tl[8 * i]);
-            for (int i = 0; i < nwg; i++) {
-                a_last = std::max(a_last, tl[8 * i + 1] - t0);
-                a_mean += (double)(tl[8 * i + 1] - t0) / nwg;
-                go_first = std::min(go_first, tl[8 * i + 2] - t0);
-                go_last = std::max(go_last, tl[8 * i + 2] - t0);
-                it_last = std::max(it_last, tl[8 * i + 3] - t0);
-                it_mean += (double)(tl[8 * i + 3] - tl[8 * i + 2]) / nwg;
-                if (tl[8 * i + 4]) fin = tl[8 * i + 4] - t0;
-            }
-            fprintf(stderr, "[ehr merge] workgroups arrive: mean %.1f last %.1f us; let go: first %.1f last %.1f us; items done: last %.1f us (mean %.1f us of work); finish done %.1f us\n",
-                    a_mean * 0.01, a_last * 0.01, go_first * 0.01, go_last * 0.01, it_last * 0.01, it_mean * 0.01, fin * 0.01);
-        }
-#endif
 #ifdef VB_TIMELINE
         {
             // Timeline of the job kernel's waves (100 MHz clock), written into the (otherwise idle) spill pool: when
@@ -3571,11 +3281,8 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     hv.heavy_max = ((((ctx->num_cus * std::max(1, job_grid)) + 7) & ~7)) / 2;
     static const int vertex_grid = getenv("EHR_VB_VERTEX_GRID") ? atoi(getenv("EHR_VB_VERTEX_GRID")) : 5;  // tuning knob
     static const int xcd_align = getenv("EHR_VB_XCD") ? atoi(getenv("EHR_VB_XCD")) : 1;  // tuning knob
-    static const int res_grid = getenv("EHR_VB_RESOLVE_GRID") ? atoi(getenv("EHR_VB_RESOLVE_GRID")) : 5;  // tuning knob (5 workgroups per CU are resident)
-    static const int no_sparse = getenv("EHR_VB_NO_SPARSE") ? atoi(getenv("EHR_VB_NO_SPARSE")) : 0;  // A/B aid
-    static const int no_sparse_mask = getenv("EHR_VB_NO_SPARSE_MASK") ? atoi(getenv("EHR_VB_NO_SPARSE_MASK")) : 0;  // A/B aid
     static const int comp_grid = getenv("EHR_VB_COMPOSITE_GRID") ? atoi(getenv("EHR_VB_COMPOSITE_GRID")) : 6;  // tuning knob (6 resident per CU)
-    const bool sparse = !no_sparse && (!mask || no_sparse_mask == 0) && ctx->vb_ref != nullptr && ctx->vb_ref == ref;
+    const bool sparse = ctx->vb_ref != nullptr && ctx->vb_ref == ref;
     const long long* const tsum_all = sparse ? (const long long*)ctx->vb_refsum.ptr : nullptr;
     const long long* const vtot_all = sparse ? tsum_all + (size_t)B * g.nt : nullptr;
     const int* const ref_flag = sparse ? (const int*)(vtot_all + B) : nullptr;
@@ -3682,34 +3389,8 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         jp.heavy_t = heavy_t;
         jp.med_t0 = med_t;
         jp.rq = rq;
-        // Merged form (round 6, EHR_VB_MERGE=1; OFF by default): the composite + finish stages at the end of the job kernel's
-        // launch, for the solver step's default chain -- bound reference, no mask output, one chunk, general-triangle pass off.
-        // Measured (profiles/r06_merged_composite_ab.txt): the same step time as the launch of its own at 8 views (72.2 us both),
-        // 3 % slower at 64 views -- what follows the last job is a tile's chain of dependent round trips, two levels of arrival
-        // tickets and the finish stage's own chain, none of which a launch boundary adds to; and the merged grid has fewer waves
-        // than there are items.  Kept as the A/B record and as the carrier of the grid-wide hand-over (agent-scope job slots).
-        static const int merge_env = getenv("EHR_VB_MERGE") ? atoi(getenv("EHR_VB_MERGE")) : 0;
-        const bool merged = merge_env && !lazy && tail && sparse && !mask_k && Bk == B && !with_slow && (job_wgs & 7) == 0;
-        if (merged) {
-            VbCompArgs& C = jp.ca;
-            C.g = g; C.B = Bk; C.mvp = mvp_k; C.V = V; C.verts = verts; C.jn = jn; C.jval = jval; C.jitems = jitems;
-            C.jspill = jspill; C.jcap = ctx->vb_jcap; C.ref = ref_k; C.mask = nullptr; C.facc = facc; C.nls = VB_LOSS_SLOTS;
-            C.want_grad = grad_mvp ? 1 : 0; C.vec_ok = vec_ok; C.spill = spill; C.spill_cap = ctx->vb_spill_cap; C.meta = meta;
-            C.dbg = dbg; C.tsum = tsum_all;
-            jp.vtot = vtot_all;
-            jp.ref_flag = ref_flag;
-            jp.loss = loss;
-            jp.grad_mvp = grad_mvp;
-            jp.lbox_all = lbox_all;
-            jp.tail = *tail;
-            vb_job_kernel<false, true><<<job_wgs, 256, 0, stream>>>(jp);
-            EHR_LAUNCH_CHECK();
-            if (time_it)
-                for (int k = 2; k <= 4; k++) EHR_HIP(hipEventRecord(ev[k], stream));
-            continue;
-        }
         if (lazy)
-            vb_job_kernel<false, false, true><<<job_wgs, 256, 0, stream>>>(jp);
+            vb_job_kernel<false, true><<<job_wgs, 256, 0, stream>>>(jp);
         else
             vb_job_kernel<false><<<job_wgs, 256, 0, stream>>>(jp);
         EHR_LAUNCH_CHECK();
@@ -3722,21 +3403,12 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         if (time_it) EHR_HIP(hipEventRecord(ev[2], stream));
         // stage 1b: drawn jobs -> per-link values and blended pairs.  The job kernel has done that for the jobs it drew itself;
         // only the jobs vb_slow_kernel redrew are left (none, normally: a launch of 32 workgroups that read a counter)
-#if VB_INLINE_RESOLVE
         if (with_slow) {
             vb_resolve_kernel<<<std::max(8, slow_grid), 256, 0, stream>>>(g, Bk, verts, mvp_k, posc, V, T, rq.tri4, rq.opp4, jid, jcov, jdesc, jn, jval,
                                                                           jitems, jspill, ctx->vb_jcap, rq.want_grad, spill,
                                                                           ctx->vb_spill_cap, meta, dbg, slow_list);
             EHR_LAUNCH_CHECK();
         }
-        (void)res_grid;
-#else
-        const int res_wgs = ((ctx->num_cus * std::max(1, res_grid)) + 7) & ~7;
-        vb_resolve_kernel<<<res_wgs, 256, 0, stream>>>(g, Bk, verts, mvp_k, posc, V, T, (const int4*)ctx->vb_idx.ptr,
-                                                       (const int4*)ctx->vb_idx.ptr + T, jid, jcov, jdesc, jn, jval, jitems, jspill,
-                                                       ctx->vb_jcap, grad_mvp ? 1 : 0, spill, ctx->vb_spill_cap, meta, dbg, nullptr);
-        EHR_LAUNCH_CHECK();
-#endif
         if (time_it) {
             for (int k = 3; k <= 4; k++) EHR_HIP(hipEventRecord(ev[k], stream));
         }

@@ -14,7 +14,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-KERNEL = "vb_job_kernel<false, false, false>"  # (COVER, MERGE, LAZY)
+KERNEL = "vb_job_kernel<false, false>"  # (COVER, LAZY)
 SIMDS, CLOCK_GHZ = 1024, 2.4
 
 
@@ -37,7 +37,7 @@ def main():
         if m:
             res[m.group(1)] = {"vgprs": int(m.group(2)), "spilled_vgprs": int(m.group(4)), "spilled_sgprs": int(m.group(5)),
                                "scratch_bytes_per_lane": int(m.group(6)), "lds_bytes": int(m.group(7)), "waves_per_simd": int(m.group(8))}
-    job = next((v for k, v in res.items() if k.startswith("vb_job_kernelILb0ELb0ELb0E")), {})
+    job = next((v for k, v in res.items() if k.startswith("vb_job_kernelILb0ELb0EE")), {})
     cycles = dur * 1e-6 * CLOCK_GHZ * 1e9
     from bench import csrc_sha16
     out = {"commit": commit, "csrc_sha16": csrc_sha16(), "kernel": KERNEL, "workload": "xarm7_1280x720_8view",
