@@ -208,6 +208,7 @@ __global__ void __launch_bounds__(EHR_TILE_THREADS) raster_tile_kernel(ClipSourc
 //   walked by a whole wave, 8 x 8 pixels per step.
 constexpr int RD_OWN = 96;     // the four lanes of a triangle walk a (band-clipped) box of up to this many pixels themselves
 constexpr int RD_LIST = 128;   // larger boxes staged in LDS per workgroup, walked by a wave each, 8 x 8 pixels per step
+constexpr int RD_BLOCKS = 16384;  // target number of workgroups of a launch (bands of at least 8 rows x blocks of 64 triangles)
 
 struct RdEntry {  // one (sub-)triangle's finished setup: edge functions at its box origin, the box, the parent triangle
     i64 e[3], sx[3], sy[3];
@@ -682,8 +683,7 @@ int ehr_rasterize_fwd(ehr_ctx* ctx, const float* pos, const int32_t* tri, const 
             u64* key = (u64*)ctx->rkeys.ptr;
             if (tmax > 0) {
                 const int nbx = (tmax + 63) / 64;
-                static const int rd_blocks = getenv("EHR_RD_BLOCKS") ? atoi(getenv("EHR_RD_BLOCKS")) : 16384;  // (tuning hook; bands are at least 8 rows)
-                int Z = std::max(1, std::min(rd_blocks / std::max(1, nbx * B), (H + 7) / 8));
+                int Z = std::max(1, std::min(RD_BLOCKS / std::max(1, nbx * B), (H + 7) / 8));
                 const int band_rows = (H + Z - 1) / Z;
                 Z = (H + band_rows - 1) / band_rows;
                 raster_direct_kernel<<<dim3(nbx, Z, B), 256, 0, stream>>>(src, W, H, band_rows, key);

@@ -59,24 +59,28 @@ constexpr int VB_RH = EHR_TILE_H + 2;
 constexpr int VB_RN = VB_RW * VB_RH;   // 340
 constexpr int VB_WORDS = (VB_RN + 63) / 64;  // 6 coverage words
 constexpr int VB_LBOX_STRIDE = 16;     // ints per (view, link) box: min x, min y, max x, max y, padding to a 64-byte line
-#define VB_HEAVY_T_DEFAULT 3000        // cost (4-pixel units walked + 256 per rasterizer round) from which a job counts as
-                                      // heavy: next step a whole workgroup takes it.  Units, not triangles: a tile of 130 long
-                                      // thin triangles (7000 units) keeps a wave busy for 60 us, one of 380 small ones for 25
+constexpr int VB_HEAVY_T_DEFAULT = 3000;  // cost (4-pixel units walked + 256 per rasterizer round) from which a job counts
+                                          // as heavy: next step a whole workgroup takes it.  Units, not triangles: a tile of
+                                          // 130 long thin triangles (7000 units) keeps a wave busy for 60 us, one of 380 small
+                                          // ones for 25
 constexpr int VB_HEAVY_CAP = 4096;    // heavy jobs remembered per step
 constexpr int VB_MED_CAP = 2048;      // long single-wave jobs remembered per step (they are started first)
-#define VB_MED_T_DEFAULT 1500          // cost from which a single-wave job counts as long
+constexpr int VB_MED_T_DEFAULT = 1500;    // cost from which a single-wave job counts as long
 // Issue priority (s_setprio) of the waves on the jobs the kernel ends on: a long job started first runs beside three
 // siblings per SIMD for most of its life (41 us instead of 30); with priority 48.5 instead of 50.0 us at 8 views.
-#ifndef VB_PRIO_LONG
-#define VB_PRIO_LONG 3
-#endif
-#ifndef VB_PRIO_HEAVY
-#define VB_PRIO_HEAVY 2
-#endif
+constexpr int VB_PRIO_LONG = 3;
+constexpr int VB_PRIO_HEAVY = 2;
 constexpr int VB_JOB_ITEMS = 64;       // blended pairs kept in LDS per tile; the rest spills to a global pool
 constexpr int VB_SPILL_BLOCK = 2048;   // items per spill allocation (one per overflowing tile)
 constexpr u64 VB_EMPTY = ~0ull;
-#define VB_FAST_EXTENT 8192            // snapped extent (1/16 px) up to which 32-bit edge functions are exact
+// Launch shapes: workgroups per CU of the chain's kernels, as many as stay resident together
+constexpr int VB_VERTEX_GRID = 5;      // (VB_VERTEX_WAVES)
+constexpr int VB_JOB_GRID = 4;         // (VB_JOB_WAVES: four workgroups' LDS fit a CU)
+constexpr int VB_COMPOSITE_GRID = 6;
+constexpr int VB_SCORE_COUNT_GRID = 4; // the scoring op's count kernel
+constexpr int VB_SLOW_GRID = 32;       // in total: the general-triangle kernel and the resolve of its jobs (normally idle)
+constexpr bool VB_XCD_SPLIT = true;    // vertex kernel: a chunk of 8k views gives every XCD the views its jobs go to (L2)
+constexpr int VB_FAST_EXTENT = 8192;   // snapped extent (1/16 px) up to which 32-bit edge functions are exact
 
 // Counters that many waves hit with atomics each get a 128-byte line of their own behind the meta block (atomics on
 // one line serialise memory-side at ~12 ns each): line xcd = job cursor of that XCD.
@@ -86,13 +90,6 @@ __host__ __device__ __forceinline__ int* vb_line(int* meta, int k) {
 }
 
 #define VB_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#ifdef VB_TIMELINE
-#define VB_TL_BEGIN() const long long tl_t0_ = __builtin_readcyclecounter()
-#define VB_TL_END(S_, i) do { if (lane_id() == 0) (S_).tl_c[i] += __builtin_readcyclecounter() - tl_t0_; } while (0)
-#else
-#define VB_TL_BEGIN() do { } while (0)
-#define VB_TL_END(S_, i) do { } while (0)
-#endif
 
 struct VbItem {
     int packed;  // bits 0-9 q (region index of pixel0) | 10 d | 11-12 di | 13 tri1 | 14 (c1 - c0 > 0)
@@ -273,14 +270,10 @@ __device__ __forceinline__ unsigned vb_pk_max_u16(unsigned a, unsigned b) {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(vb_u16x2, a), __builtin_bit_cast(vb_u16x2, b)));
 }
 
-#ifndef VB_SMALL_BOX
-#define VB_SMALL_BOX 3  // boxes of up to this many pixel centres a side are tested exactly by the vertex kernel (4: the fourth
-                        // row and column cost the VALU-bound kernel 7 % at Franka 16 x 1080p and drop nothing the job kernel
-                        // notices; 2: the job kernel pays 2.3 us at 8 views for the 3 x 3 boxes that cover nothing)
-#endif
-#ifndef VB_VERTEX_WAVES
-#define VB_VERTEX_WAVES 5  // (five workgroups per CU stay resident: the launch deals the work accordingly)
-#endif
+constexpr int VB_SMALL_BOX = 3;  // boxes of up to this many pixel centres a side are tested exactly by the vertex kernel (4: the
+                                 // fourth row and column cost the VALU-bound kernel 7 % at Franka 16 x 1080p and drop nothing the
+                                 // job kernel notices; 2: the job kernel pays 2.3 us at 8 views for the 3 x 3 boxes that cover nothing)
+constexpr int VB_VERTEX_WAVES = 5;  // (five workgroups per CU stay resident: the launch deals the work accordingly)
 template <bool HEAD>
 __global__ void __launch_bounds__(256, VB_VERTEX_WAVES)
 vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ vert_link,
@@ -678,11 +671,7 @@ __device__ __forceinline__ VbVertsT<false> vb_verts<false>(const VbLazy& z) {
 // of the camera.  The others (kind 2: edge-on slivers, geometry at the far plane) take the same walker, but their
 // units do not enter the bitmap: they are always depth tested, and a pixel that passes sets its coverage bit then.
 #define VB_SPAN_GW 4                   // boxes from this many 4-pixel units per row are walked by rows (solved spans), not by units
-#ifdef VB_TIMELINE
-constexpr int VB_DL = 576;             // (profiling build: its per-wave counters need the room -- four workgroups per CU must still fit)
-#else
 constexpr int VB_DL = 640;             // deferred units per wave (LDS); a full list is flushed against the partial coverage
-#endif
 constexpr int VB_SQ = 256;             // ring of culling survivors per wave (LDS): a whole group of candidate clusters' worth
 constexpr unsigned VB_ID_COVERED = 0xfffffffeu;  // published id of a covered pixel whose triangle nobody will ask for
 constexpr u64 VB_ROW_MASK = (1ull << VB_RW) - 1ull;
@@ -704,12 +693,6 @@ struct alignas(16) VbWaveLds {   // per wave of the job kernel
     unsigned dl[VB_DL];          // deferred units: pixel (9 bits) | 4-bit coverage << 9 | R.ent
     unsigned sq[VB_SQ];          // survivors of the box culling waiting for a full round: record slots (ring)
     int bad;                     // scoring op: a flagged unit's pixel was drawn with a depth <= 0 (coverage cannot decide)
-#ifdef VB_TIMELINE
-    int tl_units, tl_rounds;     // profiling build: 4-pixel units walked / rounds run by this wave
-    int tl_flushes, tl_tested, tl_deferred;
-    int tl_cands, tl_groups;     // candidate clusters / groups of them (one round trip each)
-    long long tl_c[8];           // cycles: staging, prefix + search, walk, flush, job total, claim + set-up, publish, -
-#endif
 };
 
 // z/w at the centre of pixel (ix, iy) from the triangle's clip-space vertices, the oracle's arithmetic
@@ -784,7 +767,6 @@ template <bool COVER = false, bool LAZY = false>
 __device__ __forceinline__ void vb_flush(VbWaveLds& S, u64* key, u64* cov, int n, const VbLazy& pvz,
                                       const int4* __restrict__ cvidx_link, int W, int H, int rx0, int ry0) {
     const int lane = lane_id();
-    VB_TL_BEGIN();
     VB_WAVE_SYNC();
     if (lane < VB_RH) {
         const u64 c = cov[lane];
@@ -836,14 +818,6 @@ __device__ __forceinline__ void vb_flush(VbWaveLds& S, u64* key, u64* cov, int n
         }
     }
     VB_WAVE_SYNC();
-#ifdef VB_TIMELINE
-    if (lane == 0) {
-        S.tl_flushes += 1;
-        S.tl_tested += nk;
-        S.tl_deferred += n;
-    }
-#endif
-    VB_TL_END(S, 3);
 }
 
 // One round of the wave-level rasterizer: up to 64 candidate triangles (lane `sv` holds one: record slot `slot` of the
@@ -863,7 +837,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
                                                int& cost, int qh) {
     VbRaster& R = S.R;
     const int lane = lane_id();
-    VB_TL_BEGIN();
     int units = 0, srows = 0;
     bool wide = false;
     uint2 bx = VB_BOX_EMPTY;
@@ -951,15 +924,7 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
     const int Stot = Ptot & 0xffff, Wtot = Ptot >> 16;
     const u64 nzu = __ballot(units > 0), nzs = __ballot(srows > 0);  // triangles with units / with span rows
     cost += Stot + 3 * Wtot + 256;  // what the job costs a wave: a step per 64 units, three per 64 span rows, about four per round
-#ifdef VB_TIMELINE
-    if (lane == 0) {
-        S.tl_units += Stot;
-        S.tl_rounds += 1;
-    }
-#endif
-    VB_TL_END(S, 0);
     if (Ptot > 0) {
-        VB_TL_BEGIN();
         R.pre[lane] = incl - packed;
         if (lane == 63) R.pre[64] = Ptot;
         VB_WAVE_SYNC();
@@ -1007,10 +972,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
             e2 = er2 + __mul24(4 * gx, sx2);
             crow = y0r + dy;
         }
-        VB_TL_END(S, 1);
-#ifdef VB_TIMELINE
-        const long long tl_w0 = __builtin_readcyclecounter();
-#endif
         for (int it0 = 0; it0 < K;) {
             // the deferred list takes at most 64 entries per step: walk as many steps as it has room for
             const int room = (VB_DL - n) >> 6;
@@ -1221,9 +1182,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
             }
         }
         VB_WAVE_SYNC();  // the staging area is rewritten by the next round
-#ifdef VB_TIMELINE
-        if (lane == 0) S.tl_c[2] += __builtin_readcyclecounter() - tl_w0;
-#endif
     }
     if (WIDE) {  // rare: near-plane clipping / very large extents, one triangle at a time, depth tested at once
         u64 wm = __ballot(wide);
@@ -1258,12 +1216,8 @@ __device__ __forceinline__ bool vb_unit_tiles(const int* __restrict__ bx, int W,
 }
 
 // Kernel-wide arguments of a job (what the job kernel's helpers need besides the job itself).
-#ifndef VB_CULL_BATCHES
-#define VB_CULL_BATCHES 2  // batches of 64 cluster boxes requested together
-#endif
-#ifndef VB_CULL_GROUP
-#define VB_CULL_GROUP 8  // candidate clusters whose triangle boxes are requested together
-#endif
+constexpr int VB_CULL_BATCHES = 2;  // batches of 64 cluster boxes requested together
+constexpr int VB_CULL_GROUP = 8;    // candidate clusters whose triangle boxes are requested together
 struct VbJobArgs {
     VbRecs rc;
     const float* verts;   // [V][3] object-space vertices
@@ -1347,9 +1301,6 @@ __device__ __forceinline__ int vb_job_raster(const VbJobArgs& A, VbWaveLds& W_, 
                 // (lane k: entry k) and go in one by one, a round whenever 64 are waiting.
                 int ccv = 0, ng = 0, knext = 0;
                 unsigned mlo = 0, mhi = 0;
-#ifdef VB_TIMELINE
-                const long long tl_g0 = __builtin_readcyclecounter();
-#endif
                 {
                     int cks[VB_CULL_GROUP];
                     uint2 tb[VB_CULL_GROUP];
@@ -1375,13 +1326,6 @@ __device__ __forceinline__ int vb_job_raster(const VbJobArgs& A, VbWaveLds& W_, 
                             total += __popcll(mk[k]);
                         }
                     }
-#ifdef VB_TIMELINE
-                    if (lane == 0) {
-                        W_.tl_c[7] += __builtin_readcyclecounter() - tl_g0;
-                        W_.tl_cands += ng;
-                        W_.tl_groups += 1;
-                    }
-#endif
                     if (total == 0) continue;
                     drawn = true;
                     if (qn + total <= VB_SQ) {
@@ -1530,7 +1474,7 @@ struct VbResolveArgs {
     int* jspill;
     VbItem* spill;
     int* meta;
-    int V, T, W, H, spill_cap, want_grad, dbg;
+    int V, T, W, H, spill_cap, want_grad;
 };
 
 // The resolve stage of ONE drawn job, by one wave, from LDS: `ids` = triangle id of every region pixel (all-ones =
@@ -1554,7 +1498,7 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
     int* const jspill = Q.jspill;
     VbItem* const spill = Q.spill;
     int* const meta = Q.meta;
-    const int V = Q.V, T = Q.T, W = Q.W, H = Q.H, spill_cap = Q.spill_cap, want_grad = Q.want_grad, dbg = Q.dbg;
+    const int V = Q.V, T = Q.T, W = Q.W, H = Q.H, spill_cap = Q.spill_cap, want_grad = Q.want_grad;
 #define KT(i) (ids[i])
     const int r = lane >> 3, c4 = (lane & 7) * 4;
     const int myq = (r + 1) * VB_RW + (c4 + 1);
@@ -1606,7 +1550,6 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
     float val[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) val[j] = (KT(myq + j) != 0xffffffffu) ? 1.f : 0.f;
-    if (dbg & 2) nh = 0;
     if (nh != 0) {
         // ---- dense hit list, ordered by (direction, region index)
         {
@@ -1795,7 +1738,6 @@ struct VbCompArgs {  // what the composite stage needs besides its LDS tables
     const VbItem* spill;
     int spill_cap;
     int* meta;
-    int dbg;
     const long long* tsum;
 };
 
@@ -1808,7 +1750,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const int W = g.W, H = g.H, L = g.L, B = C.B, U = B * L;
     const bool sparse = C.tsum != nullptr;
-    const int jcap = C.jcap, dbg = C.dbg, nls = C.nls, want_grad = C.want_grad, vec_ok = C.vec_ok, V = C.V, spill_cap = C.spill_cap;
+    const int jcap = C.jcap, nls = C.nls, want_grad = C.want_grad, vec_ok = C.vec_ok, V = C.V, spill_cap = C.spill_cap;
     const float* const mvpc = C.mvp;
     const float* const verts = C.verts;
     const int* const jn = C.jn;
@@ -1878,7 +1820,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     unsigned tmask;
     int myn = -1, myslot = 0;
     {
-        if (lane < L && !(dbg & 1)) {
+        if (lane < L) {
             const int u = b * L + lane;
             const unsigned ut = s_utile[u];
             const int j0 = s_jbase[u], n = s_jbase[u + 1] - j0;
@@ -1960,7 +1902,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         }
     }
     const unsigned bmask = (unsigned)__ballot(myn > 0);  // links with blended pairs to back-propagate
-    if (!want_grad || bmask == 0 || (dbg & 4)) continue;
+    if (!want_grad || bmask == 0) continue;
 
     // ---- backward: blended pairs -> rows (x, y, w) of d loss / d MVP, per link
     VB_WAVE_SYNC();  // the previous tile's reads of gpix are complete
@@ -2042,9 +1984,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     }
 }
 
-#ifndef VB_JOB_WAVES
-#define VB_JOB_WAVES 4
-#endif
+constexpr int VB_JOB_WAVES = 4;
 // The job kernel's parameters, ONE struct in the kernarg segment.  The kernel does not name its parameter; it reads the
 // fields through the kernarg segment pointer, made opaque to the optimiser at every use (vb_job_params), so that a field
 // is a scalar load where it is needed instead of one of ~60 scalar registers filled at kernel entry and kept -- i.e.
@@ -2063,9 +2003,8 @@ struct VbJobParams {
     unsigned* jutile;
     int jcap;
     int* meta;
-    int dbg;
+    int use_hint;  // 1: deal the previous step's heavy and long jobs (the hint names jobs by their dense id in a chunk)
     VbHeavy hv;
-    long long* timeline;
     const float* verts;  // object-space vertices and the chunk's matrices: clip-space vertices are computed on demand (VbLazy) ...
     const float* mvp;
     const float4* posc;  // ... or kept per view ([B][V]) by the eager instantiations (NULL: lazy)
@@ -2088,7 +2027,6 @@ __device__ __forceinline__ VbResolveArgs vb_load_rq(P p) {
     q.verts = p->rq.verts; q.mvp = p->rq.mvp; q.posc = p->rq.posc; q.L = p->rq.L; q.tri4 = p->rq.tri4; q.opp4 = p->rq.opp4; q.jn = p->rq.jn; q.jval = p->rq.jval;
     q.jitems = p->rq.jitems; q.jspill = p->rq.jspill; q.spill = p->rq.spill; q.meta = p->rq.meta; q.V = p->rq.V;
     q.T = p->rq.T; q.W = p->rq.W; q.H = p->rq.H; q.spill_cap = p->rq.spill_cap; q.want_grad = p->rq.want_grad;
-    q.dbg = p->rq.dbg;
     return q;
 }
 // COVER (the scoring op): jcov = the (view, tile) coverage words [B][nt][4] the jobs OR their tile's interior into, jn = one
@@ -2101,14 +2039,11 @@ vb_job_kernel(VbJobParams) {
 #define PRM(f) (vb_job_params()->f)
 #define VB_RQ() vb_load_rq(vb_job_params())
     const int W = PRM(g.W), H = PRM(g.H), L = PRM(g.L), gnt = PRM(g.nt), gntx = PRM(g.ntx);
-    const int B = PRM(B), V = PRM(V), dbg = PRM(dbg);
+    const int B = PRM(B), V = PRM(V);
     int heavy_t = max(PRM(heavy_t), PRM(hv.gen)[6]);  // (the value in force: the vertex kernel adapts it, see VbHeavy)
     const float* const pverts = PRM(verts);
     const float* const pmvp = PRM(mvp);
     const float4* const posc = LAZY ? nullptr : PRM(posc);
-#ifdef VB_TIMELINE  // profiling build only (-DVB_TIMELINE): a record per wave, printed by vbuf_meta_read under EHR_VB_PRINT
-    const long long tl_start = wall_clock64();
-#endif
     // the scheduling hint of the previous step is requested before anything else, in ONE round trip: which of the two
     // lists is the one to consume follows from the generation, so both lists' counts and this workgroup's entry of either are
     // requested together with it (they were a second, dependent round trip on every wave's way to its first job)
@@ -2192,9 +2127,9 @@ vb_job_kernel(VbJobParams) {
     // XCD-aware order: workgroup w runs on XCD w % 8 (observed, used for L2 locality only): every XCD takes a contiguous
     // eighth of the job list, so that a view's vertices, boxes and records stay in one L2.  Inside that eighth every wave
     // takes one job statically; the jobs beyond that are claimed (one returning atomic on the XCD's cursor) by whichever
-    // wave finishes first.  Jobs differ by two orders of magnitude in cost: dealt statically (EHR_VB_DEBUG & 8) the kernel
-    // waits for a wave that got a heavy SECOND job; claimed from the start, 500 waves hit each cursor at once (~12 ns per
-    // same-address atomic) and the kernel is 20 % slower.
+    // wave finishes first.  Jobs differ by two orders of magnitude in cost: dealt statically, the kernel waits for a wave
+    // that got a heavy SECOND job; claimed from the start, 500 waves hit each cursor at once (~12 ns per same-address
+    // atomic) and the kernel is 20 % slower.
     const int per_xcd = (total + 7) >> 3, xcd = blockIdx.x & 7;
     const int jbeg = xcd * per_xcd, jend = min(jbeg + per_xcd, total);
     int* const cursor = vb_line(PRM(meta), xcd);
@@ -2227,8 +2162,8 @@ vb_job_kernel(VbJobParams) {
     // Likewise when heavy jobs are the rule rather than the exception (more than one per two workgroups: the Franka
     // meshes at 1080p have ~3000 of them in 8100 jobs and run 17 % slower with the heavy phase; the 8-view xArm7
     // workload has ~220 in 5000).
-    const int hmax = (dbg >> 8) ? (dbg >> 8) : (int)gridDim.x / 2;  // (EHR_VB_DEBUG bits 8..: experiment with the limit)
-    const int nheavy = ((dbg & 64) || total > 2 * 4 * (int)gridDim.x || nheavy_prev > hmax) ? 0 : min(nheavy_prev, min(VB_HEAVY_CAP, (int)gridDim.x));  // (<= one heavy job per workgroup)
+    const int use_hint = PRM(use_hint);
+    const int nheavy = (!use_hint || total > 2 * 4 * (int)gridDim.x || nheavy_prev > (int)gridDim.x / 2) ? 0 : min(nheavy_prev, min(VB_HEAVY_CAP, (int)gridDim.x));  // (<= one heavy job per workgroup)
     // ... and when there are fewer jobs than waves (one view, small images) most workgroups are idle anyway: jobs count as
     // heavy from a proportionally lower cost (down to an eighth: a few rounds), so that the longest ones are shared
     {
@@ -2244,7 +2179,7 @@ vb_job_kernel(VbJobParams) {
     // one per wave, in the next step.  Only when the machine is short of jobs (at most 1.5 per wave): with more, claiming
     // balances the waves anyway and the jobs are better off in their own XCD's eighth of the list (L2).
     const int med_t = max(PRM(med_t0), 1);
-    const int nmed = ((dbg & (64 | 128)) || total > 6 * (int)gridDim.x) ? 0 : min(hcur ? hm5 : hm4, PRM(hv.mcap));
+    const int nmed = (!use_hint || total > 6 * (int)gridDim.x) ? 0 : min(hcur ? hm5 : hm4, PRM(hv.mcap));
     auto remember_long = [&](int id) {
         const int at = atomicAdd(&PRM(hv.gen)[4 + hnxt], 1);
         if (at < VB_MED_CAP) PRM(hv.mlist)[hnxt * VB_MED_CAP + at] = id;
@@ -2253,9 +2188,7 @@ vb_job_kernel(VbJobParams) {
         if (tid < 2) s_heavy[tid] = 0;
         __syncthreads();
     }
-#if VB_PRIO_HEAVY
     if ((int)blockIdx.x < nheavy) __builtin_amdgcn_s_setprio(VB_PRIO_HEAVY);
-#endif
     int hres_job = -1, hres_b = 0, hres_l = 0, hres_rx0 = 0, hres_ry0 = 0;  // the heavy job wave 0 resolves once the workgroup has split up again
     for (int hj = blockIdx.x; hj < nheavy; hj += gridDim.x) {  // workgroup-uniform (at most one turn: nheavy <= gridDim.x)
         const int id = (hj == (int)blockIdx.x) ? hid_first : PRM(hv.list)[hcur * VB_HEAVY_CAP + hj];
@@ -2311,9 +2244,6 @@ vb_job_kernel(VbJobParams) {
                     remember_heavy(id);
                 else if (tot_surv >= med_t)
                     remember_long(id);
-#ifdef VB_TIMELINE
-                S0.tl_flushes = tot_surv;  // (profiling build: wave 0's counters are reset after the heavy phase; parked here)
-#endif
             }
         }
         __syncthreads();
@@ -2321,27 +2251,12 @@ vb_job_kernel(VbJobParams) {
 
     // (the loop's last barrier is behind us: waves 1-3 go on to their own jobs, nobody touches wave 0's LDS but wave 0)
     if (!COVER && wave == 0 && hres_job >= 0) vb_resolve_from_lds<LAZY>(VB_RQ(), S, S.key, S.cov, (size_t)hres_job, hres_b, hres_l, hres_rx0, hres_ry0);
-#if VB_PRIO_HEAVY
     __builtin_amdgcn_s_setprio(0);
-#endif
     // workgroups that just spent their time on a heavy job take no static job: the first hk of this XCD's workgroups
     const int nhw = min(nheavy, (int)gridDim.x);
     const int hk = (nhw > xcd) ? (nhw - xcd + 7) >> 3 : 0;
     const int kx = blockIdx.x >> 3;                      // this workgroup's index inside its XCD
     const int G8 = (int)gridDim.x >> 3;                  // workgroups per XCD
-#ifdef VB_TIMELINE
-    const long long tl_heavy = wall_clock64();
-    int tl_jobs = 0, tl_maxsurv = 0, tl_sumsurv = 0;
-    long long tl_last[4] = {0, 0, 0, 0}, tl_dry = 0;  // the wave's LAST job: start, rounds done, depth tests done, resolved
-#endif
-#ifdef VB_TIMELINE
-    const int tl_hcost = (wave == 0) ? lds_all[0].tl_flushes : 0;
-    VB_WAVE_SYNC();
-    if (lane == 0) {
-        S.tl_units = S.tl_rounds = S.tl_flushes = S.tl_tested = S.tl_deferred = S.tl_cands = S.tl_groups = 0;
-        for (int k = 0; k < 8; k++) S.tl_c[k] = 0;
-    }
-#endif
     // static first jobs: wave rx of this XCD's static waves (global rank 8 rx + xcd) takes long job number <rank> of the
     // previous step if there is one, else the (rx - nmx)-th job of the XCD's eighth; the rest of the eighth is claimed
     const int nmx = (nmed > xcd) ? (nmed - xcd + 7) >> 3 : 0;  // long jobs that go to this XCD's waves (<= the static waves, see mcap)
@@ -2353,15 +2268,10 @@ vb_job_kernel(VbJobParams) {
     const int nsn = (G8 - hk) * 4 - nmx;                       // static jobs of the eighth itself
     int sjob = jbeg + rx - nmx;
     for (;;) {
-#ifdef VB_TIMELINE
-        const long long tl_j0 = __builtin_readcyclecounter();
-#endif
         int job = 0, u = -1, tx = 0, ty = 0;
         if (list_first) {
             list_first = false;
-#if VB_PRIO_LONG
             __builtin_amdgcn_s_setprio(VB_PRIO_LONG);
-#endif
             const int id = PRM(hv.mlist)[hcur * VB_MED_CAP + 8 * rx + xcd];
             u = min((int)((unsigned)id >> 22), U - 1);
             tx = id & 1023;
@@ -2371,22 +2281,17 @@ vb_job_kernel(VbJobParams) {
             job = upre[u] + (ty - ty0) * nx + (tx - tx0);
             if (n <= 0 || tx < tx0 || tx >= tx0 + nx || ty < ty0 || (ty - ty0) * nx >= n || job >= total) continue;  // the link moved away
         } else {
-#if VB_PRIO_LONG
             __builtin_amdgcn_s_setprio(0);
-#endif
-            if (first_job || (dbg & 8)) {
+            if (first_job) {
                 job = sjob;
                 sjob += max(nsn, 1);
                 first_job = false;
-                if (job >= jbeg + nsn && !(dbg & 8)) job = jend;  // (more static waves than jobs)
+                if (job >= jbeg + nsn) job = jend;  // (more static waves than jobs)
             } else {  // whoever is done first takes the next one: the waves stuck with a heavy first job take no second
                 if (lane == 0) job = jbeg + nsn + atomicAdd(cursor, 1);
                 job = __builtin_amdgcn_readfirstlane(job);
             }
             if (job >= jend) {
-#ifdef VB_TIMELINE
-                tl_dry = wall_clock64();  // this wave found its XCD's list of jobs empty
-#endif
                 break;
             }
             if (U <= 64) {  // the last (view, link) whose first job is <= job: one LDS read per lane and a ballot
@@ -2433,15 +2338,8 @@ vb_job_kernel(VbJobParams) {
         if (lane < VB_RH) S.cov[lane] = 0ull;
         if (COVER && lane == 0) S.bad = 0;
         VB_WAVE_SYNC();
-#ifdef VB_TIMELINE
-        const long long tl_j1 = __builtin_readcyclecounter();
-        tl_last[0] = wall_clock64();
-#endif
         int nsurv = 0, dln = 0;
         const int drawn = vb_job_raster<false, COVER, LAZY>(A, S, S.key, S.cov, b, l, rg, rx0, ry0, 0, 1, nsurv, dln);
-#ifdef VB_TIMELINE
-        tl_last[1] = tl_last[2] = tl_last[3] = wall_clock64();  // culling + rasterizer rounds done
-#endif
         if (COVER) {
             // flagged units (their depth range must be tested per pixel: edge-on slivers mostly) are the only deferred ones
             if (drawn >= 0 && dln > 0)
@@ -2468,12 +2366,6 @@ vb_job_kernel(VbJobParams) {
             continue;
         }
         if (dln > 0) vb_flush<false, LAZY>(S, S.key, S.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
-#ifdef VB_TIMELINE
-        tl_last[2] = tl_last[3] = wall_clock64();  // depth tests done
-        tl_jobs++;
-        tl_maxsurv = max(tl_maxsurv, nsurv);
-        tl_sumsurv += nsurv;
-#endif
         if (lane == 0) {
             if (nsurv >= heavy_t)
                 remember_heavy(hint_id);
@@ -2487,43 +2379,8 @@ vb_job_kernel(VbJobParams) {
             }
             continue;
         }
-#ifdef VB_TIMELINE
-        const long long tl_j2 = __builtin_readcyclecounter();
-#endif
         vb_resolve_from_lds<LAZY>(VB_RQ(), S, S.key, S.cov, slot, b, l, rx0, ry0);
-#ifdef VB_TIMELINE
-        tl_last[3] = wall_clock64();  // resolved
-        if (lane == 0) {
-            const long long now = __builtin_readcyclecounter();
-            S.tl_c[4] += now - tl_j0;
-            S.tl_c[5] += tl_j1 - tl_j0;
-            S.tl_c[6] += now - tl_j2;
-        }
-#endif
     }
-#ifdef VB_TIMELINE
-    if (lane == 0 && PRM(timeline)) {
-        const size_t gw = (size_t)blockIdx.x * 4 + wave;
-        const unsigned hwid = __builtin_amdgcn_s_getreg(4 | (31 << 11));    // HW_ID: wave slot, SIMD, CU, SH, SE
-        const unsigned xccid = __builtin_amdgcn_s_getreg(20 | (31 << 11));  // XCC_ID
-        PRM(timeline)[4 * gw] = tl_start;
-        PRM(timeline)[4 * gw + 1] = wall_clock64();
-        PRM(timeline)[4 * gw + 2] = tl_heavy;
-        PRM(timeline)[4 * gw + 3] = (long long)(tl_jobs & 0xff) | ((long long)(tl_maxsurv & 0xfff) << 8) | ((long long)(tl_sumsurv & 0xfff) << 20) |
-                               ((long long)(hwid & 0xffff) << 32) | ((long long)(xccid & 0xf) << 48);
-        long long* const tx = PRM(timeline) + 4 * (size_t)gridDim.x * 4 + 12 * gw;
-        tx[0] = S.tl_units;
-        tx[1] = S.tl_rounds;
-        tx[2] = (long long)S.tl_flushes | ((long long)S.tl_tested << 16) | ((long long)S.tl_deferred << 40);
-        for (int k = 0; k < 4; k++) tx[3 + k] = S.tl_c[k];
-        tx[7] = tl_hcost;
-        for (int k = 0; k < 3; k++) tx[8 + k] = S.tl_c[4 + k];
-        tx[11] = (S.tl_c[7] & 0xffffffffll) | ((long long)S.tl_cands << 32) | ((long long)S.tl_groups << 48);
-        long long* const ty = PRM(timeline) + 16 * (size_t)gridDim.x * 4 + 5 * gw;
-        for (int k = 0; k < 4; k++) ty[k] = tl_last[k];
-        ty[4] = tl_dry;
-    }
-#endif
 }
 #undef PRM
 #undef VB_RQ
@@ -2575,7 +2432,7 @@ vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float
                   const int* __restrict__ jdesc,
                   int* __restrict__ jn, float* __restrict__ jval, VbItem* __restrict__ jitems,
                   int* __restrict__ jspill, int jcap, int want_grad, VbItem* __restrict__ spill, int spill_cap,
-                  int* __restrict__ meta, int dbg, const int4* __restrict__ slow_list) {
+                  int* __restrict__ meta, const int4* __restrict__ slow_list) {
     __shared__ VbResolveLds lds_all[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     VbResolveLds& S = lds_all[wave];
@@ -2620,7 +2477,6 @@ vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float
         VbResolveArgs Q;  // (wave-uniform; the compiler keeps what it needs in scalar registers)
         Q.verts = verts; Q.mvp = mvp; Q.posc = posc; Q.L = L; Q.tri4 = tri4; Q.opp4 = opp4; Q.jn = jn; Q.jval = jval; Q.jitems = jitems; Q.jspill = jspill;
         Q.spill = spill; Q.meta = meta; Q.V = V; Q.T = T; Q.W = W; Q.H = H; Q.spill_cap = spill_cap; Q.want_grad = want_grad;
-        Q.dbg = dbg;
         if (posc)
             vb_resolve_job<false>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
         else
@@ -2696,7 +2552,7 @@ vb_composite_kernel(BinGeom g, int B, const float* __restrict__ mvp, int V, cons
                     const VbItem* __restrict__ jitems, const int* __restrict__ jspill, const int* __restrict__ jbase,
                     const unsigned* __restrict__ jutile, int jcap, const float* __restrict__ ref,
                     float* __restrict__ mask, long long* __restrict__ facc, int nls, int want_grad, int vec_ok,
-                    const VbItem* __restrict__ spill, int spill_cap, int* __restrict__ meta, int dbg,
+                    const VbItem* __restrict__ spill, int spill_cap, int* __restrict__ meta,
                     const long long* __restrict__ tsum, const long long* __restrict__ vtot,
                     const int* __restrict__ ref_flag, float* __restrict__ loss,
                     float* __restrict__ grad_mvp, StepTail tail, int do_finish, int B_all,
@@ -2722,7 +2578,7 @@ vb_composite_kernel(BinGeom g, int B, const float* __restrict__ mvp, int V, cons
     VbCompArgs C;
     C.g = g; C.B = B; C.mvp = mvp; C.V = V; C.verts = verts; C.jn = jn; C.jval = jval; C.jitems = jitems; C.jspill = jspill;
     C.jcap = jcap; C.ref = ref; C.mask = mask; C.facc = facc; C.nls = nls; C.want_grad = want_grad; C.vec_ok = vec_ok;
-    C.spill = spill; C.spill_cap = spill_cap; C.meta = meta; C.dbg = dbg; C.tsum = tsum;
+    C.spill = spill; C.spill_cap = spill_cap; C.meta = meta; C.tsum = tsum;
     const int nwg = gridDim.x, xcd = blockIdx.x & 7;
     vb_composite_items<FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> 3) * 4 + wave, (nwg >> 3) * 4, nwg);
     // ---- the workgroup whose atomics are performed last runs the finish stage.  Every wave first waits until its own
@@ -2746,11 +2602,9 @@ vb_composite_kernel(BinGeom g, int B, const float* __restrict__ mvp, int V, cons
     __syncthreads();
     __shared__ double S[4][17];
     __shared__ float red_lds[8];
-#ifndef VB_NO_FINISH
     __shared__ float Js[6][16];
     finish_body<TAIL>(g, B_all, facc_all, sparse ? vtot_all : nullptr, loss, grad_mvp, meta, tail, nls, nullptr, VB_LOSS_STRIDE,
                       gpix_all[0], S, red_lds, Js);
-#endif
 }
 
 // Content hash of the scoring op's mesh arrays: the cluster index holds copies of the vertex positions, so a mesh edited
@@ -2998,6 +2852,36 @@ static int vb_build_clusters(Scratch& out, int& nc_out, int L, int V, int T, con
     return EHR_OK;
 }
 
+// The device view of a cluster index vb_build_clusters wrote into `scratch` (NC clusters, L links; NC = 0: one padding
+// cluster's room)
+static std::pair<VbClusters, VbSlotIdx> vb_cluster_index(const Scratch& scratch, int NC, int L) {
+    const int NC1 = std::max(NC, 1);
+    VbClusters cl;
+    cl.ctri = (const int32_t*)scratch.ptr;
+    cl.clink = cl.ctri + (size_t)NC1 * 64;
+    cl.coff = cl.clink + NC1;
+    cl.laabb = (const float*)(cl.coff + L + 1);
+    cl.cvert = (const float4*)(((uintptr_t)(cl.laabb + 6 * (size_t)L) + 15) & ~(uintptr_t)15);
+    cl.NC = NC;
+    VbSlotIdx si;
+    si.cvidx = (const int4*)(cl.cvert + 3 * (size_t)NC1 * 64);
+    return {cl, si};
+}
+
+// The vertex kernel's grid for Bk views of `nitems` work items: gx workgroups per view, as many as stay resident together,
+// every one with the same number of work items; xcd_views as vb_vertex_kernel takes it
+struct VbVertexGrid {
+    int gx, xcd_views;
+};
+static VbVertexGrid vb_vertex_grid(int num_cus, int nitems, int Bk) {
+    const int per_view_cap = std::max(8, (num_cus * VB_VERTEX_GRID) / std::max(Bk, 1));
+    const int items_per_wg = (nitems + per_view_cap - 1) / per_view_cap;
+    VbVertexGrid v;
+    v.gx = std::max(1, (nitems + items_per_wg - 1) / std::max(items_per_wg, 1));
+    v.xcd_views = (VB_XCD_SPLIT && (Bk % 8) == 0) ? Bk / 8 : 0;
+    return v;
+}
+
 int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float slack, const float* verts,
                    const int32_t* tris, const int32_t* tri_link, const int32_t* opp) {
     if (H > 32760 || W > 32736)  // tile counts are packed into 10 (columns) and 12 (rows) bits
@@ -3045,7 +2929,7 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
     {  // pool of blended pairs for jobs that exceed their slot (EHR_VB_SPILL_ITEMS: test hook for the overflow path)
         const char* e = getenv("EHR_VB_SPILL_ITEMS");
         ctx->vb_spill_cap = e ? std::max(0, atoi(e)) : VB_SPILL_ITEMS;
-        // (the -DVB_TIMELINE profiling build parks its per-wave records here: keep room for them)
+        // (the 1 MB floor: room for the per-wave records of the timeline build, profiles/experiments/job_kernel_instruments.patch)
         if ((rc = ctx->vb_spill.reserve(std::max((size_t)ctx->vb_spill_cap * sizeof(VbItem), (size_t)1 << 20)))) return rc;
     }
     if ((rc = ctx->vb_units.reserve((size_t)VB_LBOX_STRIDE * B * L * sizeof(int)))) return rc;  // link boxes (one 64-byte line each), all views
@@ -3088,145 +2972,6 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
 int ehr::vbuf_meta_read(ehr_ctx* ctx, int* meta4) {
     const size_t off = (size_t)ctx->pB * (12 * (size_t)ctx->pL + VB_LOSS_SLOTS * VB_LOSS_STRIDE) * sizeof(long long);
     EHR_HIP(hipMemcpy(meta4, (char*)ctx->vb_acc.ptr + off, 4 * sizeof(int), hipMemcpyDeviceToHost));
-    if (getenv("EHR_VB_PRINT")) {  // diagnostics
-        int m8[8];
-        EHR_HIP(hipMemcpy(m8, (char*)ctx->vb_acc.ptr + off, sizeof(m8), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ehr vbuf] overflow %d spill %d jobs %d\n", m8[EHR_META_OVERFLOW], m8[EHR_META_SPILL], m8[5]);
-        int hg[3];
-        EHR_HIP(hipMemcpy(hg, ctx->vb_heavy.ptr, sizeof(hg), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ehr vbuf] heavy jobs: generation %d, lists %d / %d\n", hg[0], hg[1], hg[2]);
-        int cur[8];
-        for (int k = 0; k < 8; k++)
-            EHR_HIP(hipMemcpy(&cur[k], vb_line((int*)((char*)ctx->vb_acc.ptr + off), k), sizeof(int), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ehr vbuf] job cursors %d %d %d %d %d %d %d %d\n", cur[0], cur[1], cur[2], cur[3], cur[4], cur[5], cur[6], cur[7]);
-#ifdef VB_TIMELINE
-        {
-            // Timeline of the job kernel's waves (100 MHz clock), written into the (otherwise idle) spill pool: when
-            // they started, left the heavy phase and ended; what their single-wave jobs amounted to; where they ran.
-            const int nw = 4 * (((ctx->num_cus * 4) + 7) & ~7);
-            std::vector<long long> tl((size_t)21 * nw);
-            EHR_HIP(hipMemcpy(tl.data(), ctx->vb_spill.ptr, tl.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            long long t0 = tl[0], t1 = tl[1];
-            for (int i = 0; i < nw; i++) {
-                t0 = std::min(t0, tl[4 * i]);
-                t1 = std::max(t1, tl[4 * i + 1]);
-            }
-            int hs[16] = {0}, he[16] = {0}, hh[16] = {0};
-            double busy = 0;
-            std::vector<std::pair<long long, int>> order;
-            std::vector<long long> per(8 * 8 * 2 * 16 * 4, 0);  // survivors per SIMD
-            for (int i = 0; i < nw; i++) {
-                hs[std::min<long long>((tl[4 * i] - t0) / 500, 15)]++;
-                he[std::min<long long>((tl[4 * i + 1] - t0) / 500, 15)]++;
-                hh[std::min<long long>((tl[4 * i + 2] - t0) / 500, 15)]++;
-                busy += (double)(tl[4 * i + 1] - tl[4 * i]);
-                order.push_back(std::make_pair(-tl[4 * i + 1], i));
-                const long long x = tl[4 * i + 3];
-                const unsigned hw = (unsigned)(x >> 32) & 0xffff;
-                per[((((size_t)((x >> 48) & 7) * 8 + ((hw >> 13) & 7)) * 2 + ((hw >> 12) & 1)) * 16 + ((hw >> 8) & 15)) * 4 + ((hw >> 4) & 3)] += (x >> 20) & 0xfff;
-            }
-            std::sort(order.begin(), order.end());
-            fprintf(stderr, "[ehr timeline] job kernel: %d waves, span %.1f us, mean wave life %.1f us\n", nw, (t1 - t0) * 0.01, busy / nw * 0.01);
-            fprintf(stderr, "[ehr timeline] starts per 5 us:");
-            for (int i = 0; i < 16; i++) fprintf(stderr, " %d", hs[i]);
-            fprintf(stderr, "\n[ehr timeline] heavy phase left per 5 us:");
-            for (int i = 0; i < 16; i++) fprintf(stderr, " %d", hh[i]);
-            fprintf(stderr, "\n[ehr timeline] ends per 5 us:");
-            for (int i = 0; i < 16; i++) fprintf(stderr, " %d", he[i]);
-            fprintf(stderr, "\n[ehr timeline] last waves: wave (workgroup): start, heavy phase left, end [us]; single-wave jobs, max / sum survivors; place\n");
-            for (int k = 0; k < 12 && k < nw; k++) {
-                const int i = order[k].second;
-                const long long x = tl[4 * i + 3];
-                const unsigned hw = (unsigned)(x >> 32) & 0xffff;
-                const long long* tx = &tl[4 * (size_t)nw + 12 * i];
-                fprintf(stderr, "   %5d (%4d): %5.1f %5.1f %5.1f ; %lld jobs, %lld / %lld ; %lld units in %lld rounds ; %lld flushes: %lld of %lld units tested ; kcycles stage %.0f search %.0f walk %.0f flush %.0f resolve %.0f total %.0f cull-wait %.0f (%lld clusters, %lld groups) ; xcc %lld cu %u simd %u\n", i, i / 4,
-                        (tl[4 * i] - t0) * 0.01, (tl[4 * i + 2] - t0) * 0.01, (tl[4 * i + 1] - t0) * 0.01, x & 0xff, (x >> 8) & 0xfff,
-                        (x >> 20) & 0xfff, tx[0], tx[1], tx[2] & 0xffff, (tx[2] >> 16) & 0xffffff, tx[2] >> 40, tx[3] * 1e-3, tx[4] * 1e-3, tx[5] * 1e-3,
-                        tx[6] * 1e-3, tx[10] * 1e-3, tx[8] * 1e-3, (tx[11] & 0xffffffffll) * 1e-3, (tx[11] >> 32) & 0xffff, (tx[11] >> 48) & 0xffff, (x >> 48) & 0xf, (hw >> 8) & 15, (hw >> 4) & 3);
-            }
-            {   // where the waves' cycles go, all waves together (single-wave jobs; the phases nest as in the per-wave lines)
-                double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int i = 0; i < nw; i++) {
-                    const long long* tx = &tl[4 * (size_t)nw + 12 * i];
-                    ph[0] += (double)tx[3]; ph[1] += (double)tx[4]; ph[2] += (double)tx[5]; ph[3] += (double)tx[6];
-                    ph[4] += (double)tx[10]; ph[5] += (double)tx[8]; ph[6] += (double)(tx[11] & 0xffffffffll);
-                    ph[7] += (double)tx[9];
-                }
-                fprintf(stderr, "[ehr timeline] all waves, Mcycles: stage %.1f search %.1f walk %.1f flush %.1f resolve %.1f total %.1f claim + cull %.1f (cull-wait %.1f) ; wave life %.1f\n",
-                        ph[0] * 1e-6, ph[1] * 1e-6, ph[2] * 1e-6, ph[3] * 1e-6, ph[4] * 1e-6, ph[5] * 1e-6, ph[7] * 1e-6, ph[6] * 1e-6, busy * 24.0 * 1e-6);
-            }
-            {   // Where a late helper could still help: the last job of the waves the kernel ends on, against the moment the
-                // lists of jobs ran dry (task 1b: late sharing inside a workgroup)
-                std::vector<long long> dry;
-                for (int i = 0; i < nw; i++)
-                    if (tl[16 * (size_t)nw + 5 * i + 4]) dry.push_back(tl[16 * (size_t)nw + 5 * i + 4] - t0);
-                std::sort(dry.begin(), dry.end());
-                const double d10 = dry.empty() ? 0.0 : dry[dry.size() / 10] * 0.01, d50 = dry.empty() ? 0.0 : dry[dry.size() / 2] * 0.01;
-                fprintf(stderr, "[ehr timeline] waves find their list of jobs empty: first %.1f, 10 %% %.1f, median %.1f us (%zu waves)\n",
-                        dry.empty() ? 0.0 : dry[0] * 0.01, d10, d50, dry.size());
-                fprintf(stderr, "[ehr timeline] last job of the last waves: start, rounds done, depth tests done, resolved [us]; rounds still to run when 10 %% / half of the waves were idle\n");
-                double left10 = 0, left50 = 0, tail10 = 0, tail50 = 0;
-                const int NL = std::min(64, nw);
-                for (int k = 0; k < NL; k++) {
-                    const int i = order[k].second;
-                    const long long* ty = &tl[16 * (size_t)nw + 5 * i];
-                    if (!ty[0]) continue;  // (a wave without a single-wave job)
-                    const double a = (ty[0] - t0) * 0.01, b = (ty[1] - t0) * 0.01, c = (ty[2] - t0) * 0.01, d = (ty[3] - t0) * 0.01;
-                    if (k < 12) fprintf(stderr, "   %5d: %5.1f %5.1f %5.1f %5.1f ; %4.1f / %4.1f us\n", i, a, b, c, d, std::max(0.0, b - std::max(a, d10)), std::max(0.0, b - std::max(a, d50)));
-                    left10 += std::max(0.0, b - std::max(a, d10)) / NL;
-                    left50 += std::max(0.0, b - std::max(a, d50)) / NL;
-                    tail10 += std::max(0.0, d - std::max(b, d10)) / NL;
-                    tail50 += std::max(0.0, d - std::max(b, d50)) / NL;
-                }
-                fprintf(stderr, "[ehr timeline] mean over the %d last waves: rounds still to run %.1f / %.1f us, depth tests + resolve after that %.1f / %.1f us\n", NL, left10, left50, tail10, tail50);
-            }
-            long long mx = 0, sum = 0;
-            int used = 0;
-            for (size_t k = 0; k < per.size(); k++) {
-                mx = std::max(mx, per[k]);
-                sum += per[k];
-                used += per[k] > 0;
-            }
-            fprintf(stderr, "[ehr timeline] single-wave survivors per SIMD: %d SIMDs with work, mean %.0f, max %lld\n", used, used ? (double)sum / used : 0.0, mx);
-            {
-                long long us = 0, rs = 0, umax = 0;
-                long long fl = 0, te = 0, de = 0;
-                double cyc[4] = {0, 0, 0, 0}, jc[3] = {0, 0, 0}, cw = 0;
-                long long ncand = 0, ngrp = 0;
-                for (int i = 0; i < nw; i++) {
-                    const long long* tx = &tl[4 * (size_t)nw + 12 * i];
-                    us += tx[0];
-                    rs += tx[1];
-                    umax = std::max(umax, tx[0]);
-                    fl += tx[2] & 0xffff;
-                    te += (tx[2] >> 16) & 0xffffff;
-                    de += tx[2] >> 40;
-                    for (int k = 0; k < 4; k++) cyc[k] += (double)tx[3 + k];
-                    for (int k = 0; k < 3; k++) jc[k] += (double)tx[8 + k];
-                    cw += (double)(tx[11] & 0xffffffffll);
-                    ncand += (tx[11] >> 32) & 0xffff;
-                    ngrp += (tx[11] >> 48) & 0xffff;
-                }
-                fprintf(stderr, "[ehr timeline] single-wave jobs: %lld units in %lld rounds (%.0f units per round), at most %lld units on one wave\n", us, rs, rs ? (double)us / rs : 0.0, umax);
-                {   // heavy phase: cost of the job a workgroup shared vs the time it took
-                    std::vector<std::pair<long long, long long>> hp;
-                    for (int i = 0; i < nw; i += 4) {
-                        const long long* tx = &tl[4 * (size_t)nw + 12 * i];
-                        if (tx[7] > 0) hp.push_back(std::make_pair(tl[4 * i + 2] - tl[4 * i], tx[7]));
-                    }
-                    std::sort(hp.begin(), hp.end());
-                    fprintf(stderr, "[ehr timeline] heavy phase: %zu workgroups; (us, cost) of every 16th by duration:", hp.size());
-                    for (size_t k = 0; k < hp.size(); k += std::max<size_t>(1, hp.size() / 16)) fprintf(stderr, " (%.1f, %lld)", hp[k].first * 0.01, hp[k].second);
-                    if (!hp.empty()) fprintf(stderr, " (%.1f, %lld)", hp.back().first * 0.01, hp.back().second);
-                    fprintf(stderr, "\n");
-                }
-                fprintf(stderr, "[ehr timeline] single-wave jobs (drawn ones): %.1f wave-Mcycles in total, claim + set-up %.1f, publish / resolve %.1f; triangle boxes of %lld candidate clusters in %lld groups: %.1f waiting\n", jc[0] * 1e-6, jc[1] * 1e-6, jc[2] * 1e-6, ncand, ngrp, cw * 1e-6);
-                fprintf(stderr, "[ehr timeline] flushes %lld, deferred units %lld, depth-tested units %lld; wave-Mcycles: staging %.1f, prefix+search %.1f, walk %.1f, flush %.1f (of %.1f in total)\n",
-                        fl, de, te, cyc[0] * 1e-6, cyc[1] * 1e-6, cyc[2] * 1e-6, cyc[3] * 1e-6, busy * 0.01 * 2100.0 * 1e-6);
-            }
-        }
-#endif
-    }
     return EHR_OK;
 }
 
@@ -3244,15 +2989,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     int* const lbox_all = (int*)ctx->vb_units.ptr;
     VbItem* spill = (VbItem*)ctx->vb_spill.ptr;
     const int NC = ctx->vb_nc, NC1 = std::max(NC, 1);
-    VbClusters cl;
-    cl.ctri = (const int32_t*)ctx->vb_clus.ptr;
-    cl.clink = cl.ctri + (size_t)NC1 * 64;
-    cl.coff = cl.clink + NC1;
-    cl.laabb = (const float*)(cl.coff + L + 1);
-    cl.cvert = (const float4*)(((uintptr_t)(cl.laabb + 6 * (size_t)L) + 15) & ~(uintptr_t)15);
-    cl.NC = NC;
-    VbSlotIdx si;
-    si.cvidx = (const int4*)(cl.cvert + 3 * (size_t)NC1 * 64);
+    const auto [cl, si] = vb_cluster_index(ctx->vb_clus, NC, L);
     VbHeavy hv;
     hv.gen = (int*)ctx->vb_heavy.ptr;
     hv.list = hv.gen + 8;
@@ -3272,23 +3009,15 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         EHR_HIP(hipEventRecord(ev[0], stream));
     }
     const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0) && (!mask || ((uintptr_t)mask & 15) == 0);
-    static const int dbg_env = getenv("EHR_VB_DEBUG") ? atoi(getenv("EHR_VB_DEBUG")) : 0;  // measurement aid only
-    static const int job_grid = getenv("EHR_VB_JOB_GRID") ? atoi(getenv("EHR_VB_JOB_GRID")) : 4;   // tuning knob
-    static const int heavy_t = getenv("EHR_VB_HEAVY_T") ? atoi(getenv("EHR_VB_HEAVY_T")) : VB_HEAVY_T_DEFAULT;  // tuning knob
-    static const int med_t = getenv("EHR_VB_MED_T") ? atoi(getenv("EHR_VB_MED_T")) : VB_MED_T_DEFAULT;        // tuning knob
-    hv.mcap = std::min(VB_MED_CAP, 2 * (((ctx->num_cus * std::max(1, job_grid)) + 7) & ~7));
-    hv.heavy_base = heavy_t;
-    hv.heavy_max = ((((ctx->num_cus * std::max(1, job_grid)) + 7) & ~7)) / 2;
-    static const int vertex_grid = getenv("EHR_VB_VERTEX_GRID") ? atoi(getenv("EHR_VB_VERTEX_GRID")) : 5;  // tuning knob
-    static const int xcd_align = getenv("EHR_VB_XCD") ? atoi(getenv("EHR_VB_XCD")) : 1;  // tuning knob
-    static const int comp_grid = getenv("EHR_VB_COMPOSITE_GRID") ? atoi(getenv("EHR_VB_COMPOSITE_GRID")) : 6;  // tuning knob (6 resident per CU)
+    const int job_wgs = ((ctx->num_cus * VB_JOB_GRID) + 7) & ~7;
+    hv.mcap = std::min(VB_MED_CAP, 2 * job_wgs);
+    hv.heavy_base = VB_HEAVY_T_DEFAULT;
+    hv.heavy_max = job_wgs / 2;
     const bool sparse = ctx->vb_ref != nullptr && ctx->vb_ref == ref;
     const long long* const tsum_all = sparse ? (const long long*)ctx->vb_refsum.ptr : nullptr;
     const long long* const vtot_all = sparse ? tsum_all + (size_t)B * g.nt : nullptr;
     const int* const ref_flag = sparse ? (const int*)(vtot_all + B) : nullptr;
     const int Bc = std::max(1, std::min(ctx->vb_chunk, B));
-    // (the heavy-job hint names jobs by their dense id inside a chunk: with more than one chunk it is switched off)
-    const int dbg = dbg_env | (Bc < B ? 64 : 0);
     const size_t nslot = (size_t)ctx->vb_jcap;
     float* jval = (float*)ctx->vb_jobs.ptr;
     VbItem* jitems = (VbItem*)(jval + nslot * 256);
@@ -3319,28 +3048,23 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         recs.tbox = (uint2*)(recs.trec + recs.n * 2);
         recs.cbox = recs.tbox + recs.n;
         // stage 0: [pose forward] + vertices + screen boxes
-        // workgroups per view: as many as stay resident together (5 per CU), every one with the same number of work items
-        const int per_view_cap = std::max(8, (ctx->num_cus * std::max(1, vertex_grid)) / std::max(Bk, 1));
-        const int items_per_wg = (nitems + per_view_cap - 1) / per_view_cap;
-        const int gx = std::max(1, (nitems + items_per_wg - 1) / std::max(items_per_wg, 1));
-        const int xcd_views = (xcd_align && (Bk % 8) == 0) ? Bk / 8 : 0;
-        const dim3 vgrid(gx * Bk);
+        const VbVertexGrid vg = vb_vertex_grid(ctx->num_cus, nitems, Bk);
+        const dim3 vgrid(vg.gx * Bk);
         const int nacc_ints = 2 * Bk * acc_stride;
         const int role = first_chunk ? 1 : 2;
         if (head) {
             StepHead hk = *head;
             hk.link_poses = head->link_poses + (size_t)b0 * L * 16;
             vb_vertex_kernel<true><<<vgrid, 256, 0, stream>>>(verts, vert_link, tris, cl, hk, mvp_k, V, nvb, g, posc, recs, lbox,
-                                                             (int*)facc, nacc_ints, meta, Bk, gx, xcd_views, hv, role);
+                                                             (int*)facc, nacc_ints, meta, Bk, vg.gx, vg.xcd_views, hv, role);
         } else {
             StepHead none = {};
             vb_vertex_kernel<false><<<vgrid, 256, 0, stream>>>(verts, vert_link, tris, cl, none, mvp_k, V, nvb, g, posc, recs,
-                                                              lbox, (int*)facc, nacc_ints, meta, Bk, gx, xcd_views, hv, role);
+                                                              lbox, (int*)facc, nacc_ints, meta, Bk, vg.gx, vg.xcd_views, hv, role);
         }
         EHR_LAUNCH_CHECK();
         if (time_it) EHR_HIP(hipEventRecord(ev[1], stream));
         // stage 1: jobs = (view, link, tile) -> coverage and the triangle ids the silhouette analysis will ask for
-        const int job_wgs = ((ctx->num_cus * std::max(1, job_grid)) + 7) & ~7;
         // stage 1a (below) is launched by the stateless render call always, by the solver step only once a step needed it
         const bool with_slow = !tail || ctx->vb_slow_needed;
         VbResolveArgs rq;  // the resolve stage runs inside the job kernel, on the wave that drew the job
@@ -3362,7 +3086,6 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         rq.H = H;
         rq.spill_cap = ctx->vb_spill_cap;
         rq.want_grad = grad_mvp ? 1 : 0;
-        rq.dbg = dbg;
         VbJobParams jp;
         jp.g = g;
         jp.B = Bk;
@@ -3376,9 +3099,8 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         jp.jutile = jutile;
         jp.jcap = ctx->vb_jcap;
         jp.meta = meta;
-        jp.dbg = dbg;
+        jp.use_hint = Bc == B;  // (the heavy-job hint names jobs by their dense id inside a chunk: off with more than one)
         jp.hv = hv;
-        jp.timeline = (long long*)ctx->vb_spill.ptr;
         jp.verts = verts;
         jp.mvp = mvp_k;
         jp.posc = posc;
@@ -3386,8 +3108,8 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         jp.si = si;
         jp.jcov = jcov;
         jp.slow_list = with_slow ? slow_list : nullptr;
-        jp.heavy_t = heavy_t;
-        jp.med_t0 = med_t;
+        jp.heavy_t = VB_HEAVY_T_DEFAULT;
+        jp.med_t0 = VB_MED_T_DEFAULT;
         jp.rq = rq;
         if (lazy)
             vb_job_kernel<false, true><<<job_wgs, 256, 0, stream>>>(jp);
@@ -3395,18 +3117,17 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
             vb_job_kernel<false><<<job_wgs, 256, 0, stream>>>(jp);
         EHR_LAUNCH_CHECK();
         // stage 1a: jobs with a triangle that crosses the near plane or spans > 512 pixels (normally none: the kernel returns at once)
-        static const int slow_grid = getenv("EHR_VB_SLOW_GRID") ? atoi(getenv("EHR_VB_SLOW_GRID")) : 32;  // tuning knob
         if (with_slow) {
-            vb_slow_kernel<<<std::max(1, slow_grid), 256, 0, stream>>>(g, cl, recs, verts, mvp_k, posc, V, si, jid, jcov, jdesc, jn, slow_list, meta);
+            vb_slow_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(g, cl, recs, verts, mvp_k, posc, V, si, jid, jcov, jdesc, jn, slow_list, meta);
             EHR_LAUNCH_CHECK();
         }
         if (time_it) EHR_HIP(hipEventRecord(ev[2], stream));
         // stage 1b: drawn jobs -> per-link values and blended pairs.  The job kernel has done that for the jobs it drew itself;
         // only the jobs vb_slow_kernel redrew are left (none, normally: a launch of 32 workgroups that read a counter)
         if (with_slow) {
-            vb_resolve_kernel<<<std::max(8, slow_grid), 256, 0, stream>>>(g, Bk, verts, mvp_k, posc, V, T, rq.tri4, rq.opp4, jid, jcov, jdesc, jn, jval,
+            vb_resolve_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(g, Bk, verts, mvp_k, posc, V, T, rq.tri4, rq.opp4, jid, jcov, jdesc, jn, jval,
                                                                           jitems, jspill, ctx->vb_jcap, rq.want_grad, spill,
-                                                                          ctx->vb_spill_cap, meta, dbg, slow_list);
+                                                                          ctx->vb_spill_cap, meta, slow_list);
             EHR_LAUNCH_CHECK();
         }
         if (time_it) {
@@ -3415,7 +3136,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         // stage 2: composite, loss, mask, backward.  In the call's last chunk its last-arriving workgroup runs the finish
         // stage over ALL views (accumulators -> loss / grad_mvp, + pose backward and Adam in the solver-step form; re-arms
         // the link boxes).  With a bound reference mask and no mask output only tiles that hold a job are visited.
-        int nwg = ctx->num_cus * std::max(1, comp_grid);
+        int nwg = ctx->num_cus * VB_COMPOSITE_GRID;
         if (!sparse) nwg = std::min(nwg, (Bk * g.nt + 3) / 4);
         nwg = std::max(8, (nwg + 7) & ~7);  // a multiple of 8: the XCD split and the two-level arrival ticket rely on it
         const long long* tsum = sparse ? tsum_all + (size_t)b0 * g.nt : nullptr;
@@ -3426,7 +3147,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
 #define VB_COMPOSITE(TAILV, FILLV, tailarg)                                                                                  \
     vb_composite_kernel<TAILV, FILLV><<<nwg, 256, dyn, stream>>>(                                                            \
         g, Bk, mvp_k, V, verts, lbox, jn, jval, jitems, jspill, jbase, jutile, ctx->vb_jcap, ref_k, mask_k, facc,            \
-        VB_LOSS_SLOTS, grad_mvp ? 1 : 0, vec_ok, spill, ctx->vb_spill_cap, meta, dbg, tsum, vtot, ref_flag, loss, grad_mvp,  \
+        VB_LOSS_SLOTS, grad_mvp ? 1 : 0, vec_ok, spill, ctx->vb_spill_cap, meta, tsum, vtot, ref_flag, loss, grad_mvp,       \
         tailarg, last_chunk ? 1 : 0, B, facc_all, vtot_all, lbox_all)
         StepTail none = {};
         if (tail) {
@@ -3497,15 +3218,7 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         return must ? fail(EHR_ERR_INVALID, "ehr_mask_variance: EHR_SCORE_PATH=chain, but the mesh's links are not grouped") : EHR_OK;
     const BinGeom g = make_geom(H, W, L);
     const int NC = ctx->sc_nc;
-    VbClusters cl;
-    cl.ctri = (const int32_t*)ctx->sc_clus.ptr;
-    cl.clink = cl.ctri + (size_t)NC * 64;
-    cl.coff = cl.clink + NC;
-    cl.laabb = (const float*)(cl.coff + L + 1);
-    cl.cvert = (const float4*)(((uintptr_t)(cl.laabb + 6 * (size_t)L) + 15) & ~(uintptr_t)15);
-    cl.NC = NC;
-    VbSlotIdx si;
-    si.cvidx = (const int4*)(cl.cvert + 3 * (size_t)NC * 64);
+    const auto [cl, si] = vb_cluster_index(ctx->sc_clus, NC, L);
     // candidates per chunk: (view, link) units of a chunk fit the job kernel's LDS tables; scratch bounded like the solver's
     const double view_bytes = (double)NC * (64 * 40 + 8) + (double)V * 16 + (double)g.nt * 32;
     int Qc = std::max(1, (VB_MAX_UNITS / L) / S);
@@ -3537,11 +3250,9 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     EHR_HIP(hipMemsetAsync(sacc0, 0, 2 * 16 * (size_t)Qc * sizeof(unsigned long long), stream));
     EHR_HIP(hipMemsetAsync(score, 0, (size_t)Q * sizeof(long long), stream));
     if (count) EHR_HIP(hipMemsetAsync(count, 0, (size_t)Q * H * W, stream));
-    static const int vertex_grid = getenv("EHR_VB_VERTEX_GRID") ? atoi(getenv("EHR_VB_VERTEX_GRID")) : 5;
-    static const int job_grid = getenv("EHR_VB_JOB_GRID") ? atoi(getenv("EHR_VB_JOB_GRID")) : 4;
     const int nvb = (std::max(V, 1) + 255) / 256;
     const int nitems = nvb + (NC + 3) / 4;
-    const int job_wgs = ((ctx->num_cus * std::max(1, job_grid)) + 7) & ~7;
+    const int job_wgs = ((ctx->num_cus * VB_JOB_GRID) + 7) & ~7;
     // link boxes start empty (afterwards the count kernel re-arms them)
     vb_score_count_kernel<<<64, 256, 0, stream>>>(g, 0, S, tcov, sacc0, nullptr, lbox, VB_LBOX_STRIDE * Bc * L, sacc0, score, 0);
     EHR_LAUNCH_CHECK();
@@ -3555,14 +3266,11 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         recs.trec = (int4*)ctx->sc_entries.ptr;
         recs.tbox = (uint2*)(recs.trec + recs.n * 2);
         recs.cbox = recs.tbox + recs.n;
-        const int per_view_cap = std::max(8, (ctx->num_cus * std::max(1, vertex_grid)) / std::max(Bk, 1));
-        const int items_per_wg = (nitems + per_view_cap - 1) / per_view_cap;
-        const int gx = std::max(1, (nitems + items_per_wg - 1) / std::max(items_per_wg, 1));
-        const int xcd_views = ((Bk % 8) == 0) ? Bk / 8 : 0;
+        const VbVertexGrid vg = vb_vertex_grid(ctx->num_cus, nitems, Bk);
         StepHead none = {};
-        vb_vertex_kernel<false><<<dim3(gx * Bk), 256, 0, stream>>>(verts, vert_link, tris, cl, none, const_cast<float*>(mvp) + (size_t)q0 * S * L * 16,
-                                                                V, nvb, g, posc, recs, lbox, (int*)tcov, Bk * g.nt * 8, meta, Bk, gx,
-                                                                xcd_views, hv, 1 | 4);
+        vb_vertex_kernel<false><<<dim3(vg.gx * Bk), 256, 0, stream>>>(verts, vert_link, tris, cl, none, const_cast<float*>(mvp) + (size_t)q0 * S * L * 16,
+                                                                   V, nvb, g, posc, recs, lbox, (int*)tcov, Bk * g.nt * 8, meta, Bk, vg.gx,
+                                                                   vg.xcd_views, hv, 1 | 4);
         EHR_LAUNCH_CHECK();
         VbJobParams jp = {};
         jp.g = g;
@@ -3573,7 +3281,7 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         jp.jn = sticky;
         jp.jcap = S;
         jp.meta = meta;
-        jp.dbg = 64 | 128;
+        jp.use_hint = 0;
         jp.hv = hv;
         jp.verts = verts;
         jp.mvp = mvp + (size_t)q0 * S * L * 16;
@@ -3585,9 +3293,8 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         jp.med_t0 = 0x7fffffff;
         vb_job_kernel<true><<<job_wgs, 256, 0, stream>>>(jp);
         EHR_LAUNCH_CHECK();
-        static const int count_grid = getenv("EHR_SCORE_COUNT_GRID") ? atoi(getenv("EHR_SCORE_COUNT_GRID")) : 4;  // tuning knob
         unsigned long long* const sacc = sacc0 + (size_t)flip * 16 * Qc;
-        vb_score_count_kernel<<<std::min((nq * g.nt + 3) / 4, std::max(1, count_grid) * ctx->num_cus), 256, 0, stream>>>(
+        vb_score_count_kernel<<<std::min((nq * g.nt + 3) / 4, VB_SCORE_COUNT_GRID * ctx->num_cus), 256, 0, stream>>>(
             g, nq, S, tcov, sacc, count ? count + (size_t)q0 * H * W : nullptr, lbox, VB_LBOX_STRIDE * Bc * L, prev_sacc, prev_score, prev_nq);
         EHR_LAUNCH_CHECK();
         prev_sacc = sacc;
