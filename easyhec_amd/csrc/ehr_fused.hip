@@ -59,7 +59,7 @@ static int fused_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, co
         return fail(EHR_ERR_INVALID, "fused op: NULL tensor");
     if (ctx->pB != B || ctx->pL != L || ctx->pV != V || ctx->pT != T || ctx->pH != H || ctx->pW != W)
         return fail(EHR_ERR_INVALID, "fused op: shape differs from the planned one; call ehr_fused_plan first");
-    return vbuf_chain(ctx, verts, tris, tri_link, vert_link, opp, mvp, ref, B, L, V, T, H, W, mask, loss, grad_mvp, head,
+    return vbuf_chain(ctx, verts, tris, vert_link, opp, mvp, ref, B, L, V, T, H, W, mask, loss, grad_mvp, head,
                       tail, (hipStream_t)stream_);
 }
 
@@ -142,10 +142,10 @@ int ehr_fused_status(ehr_ctx* ctx) {
     int m4[4] = {0, 0, 0, 0};
     int rc0 = vbuf_meta_read(ctx, m4);
     if (rc0) return rc0;
-    if (m4[EHR_META_OVERFLOW] & 4) ctx->vb_slow_needed = true;  // (VB_FLAG_NEED_SLOW; a captured chain must be re-captured)
-    if (m4[EHR_META_OVERFLOW] & ~4)
+    if (m4[EHR_META_OVERFLOW] & VB_FLAG_NEED_SLOW) ctx->vb_slow_needed = true;  // (a captured chain must be re-captured)
+    if (m4[EHR_META_OVERFLOW] & ~VB_FLAG_NEED_SLOW)
         return fail(EHR_ERR_OVERFLOW, "fused path: an accumulator or the blended-pair spill pool overflowed");
-    if (m4[EHR_META_OVERFLOW] & 4)
+    if (m4[EHR_META_OVERFLOW] & VB_FLAG_NEED_SLOW)
         return fail(EHR_ERR_RETRY, "fused path: the step met triangles for the general-triangle pass (near-plane clipping or "
                     "more than 512 pixels wide), which the solver step had not been launching; it is switched on now: run the "
                     "step again (its NaN left the optimiser state untouched; re-capture a captured chain)");

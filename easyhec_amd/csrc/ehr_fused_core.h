@@ -40,6 +40,12 @@ __device__ __forceinline__ long long acc_load(const long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Layout of the accumulators (ehr_ctx::vb_acc): per view 12 numbers per link, then `nls` partial sums of the frame loss,
+// VB_LOSS_STRIDE i64 apart (several slots, one 128-byte line each, so that thousands of tiles do not serialise on one
+// address; integer sums, so the split does not change the result); behind the B views of a call, the meta block.
+__host__ __device__ constexpr int vb_acc_stride(int L, int nls = VB_LOSS_SLOTS) { return 12 * L + nls * VB_LOSS_STRIDE; }
+__host__ __device__ __forceinline__ int* vb_acc_meta(long long* acc, int B, int L) { return (int*)(acc + (size_t)B * vb_acc_stride(L)); }
+
 // Last stage, ONE workgroup: fixed-point accumulators -> loss[B] and grad_mvp[B,L,16]; with TAIL also the rest of a
 // solver step (d sum(loss) / d dof = the 8 floats a data-parallel job all-reduces, then Adam unless deferred).
 struct StepTail {  // what the solver-step form needs (all device pointers)
@@ -57,9 +63,7 @@ struct StepTail {  // what the solver-step form needs (all device pointers)
     int defer_adam;
 };
 
-// facc: per view 12 numbers per link, then `nls` partial sums of the frame loss, `lstride` i64 apart (several slots, one
-// 128-byte line each, so that thousands of tiles do not serialise on one address; integer sums, so the split does not
-// change the result).  vtot (optional): per view a constant that belongs to the frame loss (the bound reference mask's
+// facc: see vb_acc_stride (lstride = VB_LOSS_STRIDE).  vtot (optional): per view a constant that belongs to the frame loss (the bound reference mask's
 // cached part).  Called by all 256 threads of one workgroup after every other workgroup's atomics were performed.
 template <bool TAIL>
 __device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long long* __restrict__ facc,
@@ -69,7 +73,7 @@ __device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long 
                                             double (*S)[17] /* LDS [4][17] */, float* red_lds /* LDS [8] */,
                                             float (*Js)[16] /* LDS [6][16] */) {
     const int tid = threadIdx.x, L = g.L;
-    const int acc_stride = 12 * L + nls * lstride;
+    const int acc_stride = vb_acc_stride(L, nls);
     if (lbox)  // the links' screen boxes start "empty" in the next step
         for (int i = tid; i < 16 * B * L; i += 256) lbox[i] = (i & 2) ? INT_MIN : INT_MAX;  // 16 ints (one line) per box
     AdamState st;

@@ -58,6 +58,7 @@ struct RasterShape {  // what makes two drop-in rasterize calls "the same frame 
 };
 #define VB_LOSS_SLOTS 32          // partial frame-loss sums per view (spreads same-address atomics)
 #define VB_LOSS_STRIDE 16         // i64 between two of them: one 128-byte line each (atomics on one line serialise)
+#define VB_FLAG_NEED_SLOW 4       // meta[EHR_META_OVERFLOW] bit: a solver step met a triangle for vb_slow_kernel, which it had not launched
 #define VB_MAX_UNITS 512          // views x links one context plans for
 #define VB_SPILL_ITEMS (1 << 20)  // pool of blended-pair items for tiles that overflow their LDS list (16 MB)
 int vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float slack, const float* verts,
@@ -66,7 +67,7 @@ int vbuf_meta_read(ehr_ctx* ctx, int* meta4);
 int vbuf_bind_ref(ehr_ctx* ctx, const float* ref, hipStream_t stream);
 int vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp, int Q, int S,
                int L, int V, int T, int H, int W, long long* score, unsigned char* count, hipStream_t stream, int* handled);
-int vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link, const int32_t* vert_link,
+int vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
                const int32_t* opp, float* mvp, const float* ref, int B, int L, int V, int T, int H, int W, float* mask,
                float* loss, float* grad_mvp, const StepHead* head, const StepTail* tail, hipStream_t stream);
 
@@ -100,7 +101,7 @@ struct ehr_ctx {
     int num_cus = 256;
     // launch chain of the fused op (ehr_vbuf.hip); its own scratch, never shared with the drop-in ops
     ehr::Scratch vb_clus;    // i32 cluster index: ctri [NC][64] | clink [NC] | coff [L + 1] (static, built by the plan)
-    ehr::Scratch vb_heavy;   // heavy-job scheduling hint carried from step to step (generation, lists, stamps)
+    ehr::Scratch vb_heavy;   // heavy-job scheduling hint carried from step to step: gen | list | mlist | stamp (VbHeavy, vb_heavy)
     ehr::Scratch vb_idx;     // int4 [T] padded triangle indices | int4 [T] padded edge topology (static)
     const void* vb_plan_tris = nullptr;  // the scene the static index was built for
     const void* vb_plan_opp = nullptr;
@@ -108,12 +109,16 @@ struct ehr_ctx {
     int vb_nc = 0;           // number of clusters
     int vb_jcap = 0;         // job slots (of one chunk of views)
     int vb_chunk = 0;        // views per pass of the chain (plan time: LDS tables of the job kernel, scratch budget)
-    ehr::Scratch vb_boxes;   // uint2 pixel boxes of the current step: tbox [B][NC][64] | cbox [B][NC]
-    ehr::Scratch vb_units;   // i32 [B][L][4] pixel boxes of the links (re-armed by the finish kernel)
-    ehr::Scratch vb_acc;     // i64 [B][12 L + VB_LOSS_SLOTS * VB_LOSS_STRIDE] fixed-point sums, then the meta words
+    ehr::Scratch vb_boxes;   // raster records of the current chunk: trec int4 [Bc][NC][64][2] | tbox uint2 [Bc][NC][64] | cbox uint2
+                             // [Bc][NC] (VbRecs, vb_recs)
+    ehr::Scratch vb_units;   // i32 [B][L][VB_LBOX_STRIDE] pixel boxes of the links, one 64-byte line each (re-armed by the call's
+                             // last composite launch)
+    ehr::Scratch vb_acc;     // i64 [B][vb_acc_stride(L)] fixed-point sums, then the meta block (vb_acc_meta: meta words, then
+                             // the VB_LINES counter lines)
     ehr::Scratch vb_posc;    // float4 [B][V] clip-space vertices (eager plans only)
     bool vb_lazy = false;    // the plan computes clip-space vertices where they are looked up (VbLazy in ehr_vbuf.hip): V > 1.5 T
-    ehr::Scratch vb_jobs;    // per (view, link, tile) job slot: value tile | blended pairs | count | spill base
+    ehr::Scratch vb_jobs;    // job slots of a chunk and their tables: jval | jitems | jcov | jn | jspill | jid | jdesc | jbase |
+                             // jutile | slow_list (VbSlots, vb_slots)
     ehr::Scratch vb_spill;   // blended pairs of jobs that exceed their slot
     int vb_spill_cap = 0;    // ... in items
     ehr::Scratch vb_refsum;  // cached sums of the bound reference mask: tsum i64 [B][nt] | vtot i64 [B] | flag
@@ -124,7 +129,7 @@ struct ehr_ctx {
     ehr::Scratch sc_counts, sc_offsets, sc_entries, sc_posc;
     size_t sc_entries_cap = 0;
     // ... and, for the coverage-only chain of the scoring op (ehr_vbuf.hip: vbuf_score), the static cluster index of its mesh
-    ehr::Scratch sc_clus, sc_misc;
+    ehr::Scratch sc_clus, sc_misc;  // (sc_misc: link boxes | meta block | hint lists | sticky flag | sums | coverage words, VbScoreMisc)
     int sc_nc = 0;
     const void* sc_key[3] = {nullptr, nullptr, nullptr};  // (verts, tris, vert_link) the index was built for
     int sc_key_n[3] = {0, 0, 0};                          // (V, T, L)

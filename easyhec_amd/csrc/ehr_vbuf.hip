@@ -79,15 +79,30 @@ constexpr int VB_JOB_GRID = 4;         // (VB_JOB_WAVES: four workgroups' LDS fi
 constexpr int VB_COMPOSITE_GRID = 6;
 constexpr int VB_SCORE_COUNT_GRID = 4; // the scoring op's count kernel
 constexpr int VB_SLOW_GRID = 32;       // in total: the general-triangle kernel and the resolve of its jobs (normally idle)
-constexpr bool VB_XCD_SPLIT = true;    // vertex kernel: a chunk of 8k views gives every XCD the views its jobs go to (L2)
+constexpr bool VB_XCD_SPLIT = true;    // vertex kernel: a chunk of VB_XCDS x k views gives every XCD the views its jobs go to (L2)
 constexpr int VB_FAST_EXTENT = 8192;   // snapped extent (1/16 px) up to which 32-bit edge functions are exact
 
+// The part's XCDs: workgroup w of a 1-D grid runs on XCD w % VB_XCDS (observed, used for L2 locality only)
+constexpr int VB_XCDS = 8;
+constexpr int VB_XCD_BITS = __builtin_ctz(VB_XCDS);
+static_assert(VB_XCDS == 1 << VB_XCD_BITS, "a workgroup finds its XCD with a mask and a shift");
+__host__ __device__ constexpr int vb_xcd_share(int n) { return (n + VB_XCDS - 1) >> VB_XCD_BITS; }  // ceil(n / XCDs)
+__host__ __device__ constexpr int vb_xcd_round_up(int n) { return (n + VB_XCDS - 1) & ~(VB_XCDS - 1); }
+
 // Counters that many waves hit with atomics each get a 128-byte line of their own behind the meta block (atomics on
-// one line serialise memory-side at ~12 ns each): line xcd = job cursor of that XCD.
-#define VB_LINES 18   // 0-7 job cursors of the XCDs, 8-15 composite arrival tickets of the XCDs, 16 the top ticket, 17 jobs put aside for vb_slow_kernel
+// one line serialise memory-side at ~12 ns each).
+enum VbLine {
+    VB_LINE_JOB_CURSOR = 0,                               // + xcd: job cursor of that XCD
+    VB_LINE_COMP_TICKET = VB_LINE_JOB_CURSOR + VB_XCDS,   // + xcd: composite arrival ticket of that XCD
+    VB_LINE_TOP_TICKET = VB_LINE_COMP_TICKET + VB_XCDS,   // the ticket over the XCDs
+    VB_LINE_SLOW_COUNT,                                   // jobs put aside for vb_slow_kernel
+    VB_LINES
+};
 __host__ __device__ __forceinline__ int* vb_line(int* meta, int k) {
     return (int*)((((uintptr_t)(meta + EHR_META_INTS)) + 127) & ~(uintptr_t)127) + 32 * k;
 }
+// bytes of a meta block: the meta words, then the lines vb_line finds behind them (one more for its alignment)
+constexpr size_t VB_META_BYTES = EHR_META_INTS * sizeof(int) + (VB_LINES + 1) * 128;
 
 #define VB_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
@@ -96,6 +111,56 @@ struct VbItem {
     int v1, v2;  // the two vertices of the crossing silhouette edge (global ids)
     float alpha;
 };
+
+// Scratch layouts.  Every scratch buffer of the chain is described ONCE, by a host function that carves its arrays, in
+// order, from a base pointer (vb_recs, vb_heavy, vb_slots, vb_score_misc below); over a null base the end of the last
+// array is the byte size the plan reserves.  (The bases come from hipMalloc: aligned beyond anything asked for here.)
+struct VbCarve {
+    uintptr_t at;
+    template <class T>
+    T* take(size_t n, size_t align = alignof(T)) {
+        at = (at + align - 1) & ~(uintptr_t)(align - 1);
+        T* const p = (T*)at;
+        at += n * sizeof(T);
+        return p;
+    }
+};
+
+// Job slots of a chunk of views, compact (numbered like the jobs: a (view, link, tile) slot is found from the link's first
+// job), and the tables that go with them.
+struct VbSlots {
+    float* jval;       // [jcap][256] the link's antialiased values of the tile
+    VbItem* jitems;    // [jcap][VB_JOB_ITEMS] blended pairs for the backward pass
+    u64* jcov;         // [jcap][VB_WORDS] coverage bitmap of the region (region-linear)
+    int* jn;           // [jcap] number of blended pairs (-1: the link contributes nothing to the tile)
+    int* jspill;       // [jcap] the job's first item in the spill pool
+    unsigned* jid;     // [jcap][VB_RN] triangle ids of the region's pixels
+    int* jdesc;        // [jcap] (view, link) | tile column << 9 | tile row << 19, -1: nothing drawn
+    int* jbase;        // [units + 1] first job of every (view, link) of the chunk
+    unsigned* jutile;  // [units] its tile range
+    int4* slow_list;   // [jcap] jobs put aside for vb_slow_kernel (NULL: that kernel is not launched, see vb_put_aside)
+    int jcap;
+};
+constexpr size_t VB_SLOT_BYTES = 256 * sizeof(float) + VB_JOB_ITEMS * sizeof(VbItem) + VB_WORDS * sizeof(u64) + 2 * sizeof(int) +
+                                 VB_RN * sizeof(unsigned) + sizeof(int) + sizeof(int4);  // the [jcap] arrays of vb_slots
+static_assert(VB_SLOT_BYTES == 1024 + 1024 + 48 + 8 + 1360 + 4 + 16, "job slot: 3484 bytes");
+static VbSlots vb_slots(void* base, size_t jcap, size_t units, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbSlots s;
+    s.jval = c.take<float>(jcap * 256);
+    s.jitems = c.take<VbItem>(jcap * VB_JOB_ITEMS);
+    s.jcov = c.take<u64>(jcap * VB_WORDS);
+    s.jn = c.take<int>(jcap);
+    s.jspill = c.take<int>(jcap);
+    s.jid = c.take<unsigned>(jcap * VB_RN);
+    s.jdesc = c.take<int>(jcap);
+    s.jbase = c.take<int>(units + 1);
+    s.jutile = c.take<unsigned>(units);
+    s.slow_list = c.take<int4>(jcap, 16);
+    s.jcap = (int)jcap;
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return s;
+}
 
 // ---- compile-time bitmaps over the 34x10 region (bit i = region pixel i, row-major) ------------------------------
 constexpr bool vb_interior(int i) {
@@ -154,6 +219,18 @@ struct VbHeavy {
                      // being switched off (the Franka meshes at 1080p: 3000 jobs above 2500 in 8100; 112 instead of 124 us
                      // with the ~500 heaviest shared); it sinks back when fewer than half as many are recorded
 };
+
+// gen | list | mlist | stamp [nstamp]; the scheduling fields are the caller's (zero: the hint is off)
+static VbHeavy vb_heavy(void* base, size_t nstamp, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbHeavy hv = {};
+    hv.gen = c.take<int>(8);
+    hv.list = c.take<int>(2 * VB_HEAVY_CAP);
+    hv.mlist = c.take<int>(2 * VB_MED_CAP);
+    hv.stamp = c.take<int>(nstamp);
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return hv;
+}
 
 // A remembered job in the hint lists: tile column | tile row << 10 | (view, link) << 22 -- no division on the way from a
 // list entry to the first cluster box (the long jobs the kernel ends on start from these).
@@ -229,6 +306,20 @@ struct VbRecs {
     int4* trec;    // [B][NC][64][2]: the two halves of a record side by side
     size_t n;      // B * NC * 64 (component stride)
 };
+constexpr size_t VB_REC_BYTES = sizeof(int4) * 2 + sizeof(uint2);              // a cluster slot: raster record + pixel box
+constexpr size_t VB_CLUSTER_REC_BYTES = 64 * VB_REC_BYTES + sizeof(uint2);     // a (view, cluster): its 64 slots + its box
+static_assert(VB_CLUSTER_REC_BYTES == 2568, "raster records: 64 x (32 + 8) + 8 bytes per (view, cluster)");
+// trec | tbox | cbox of `views` views x NC clusters
+static VbRecs vb_recs(void* base, size_t views, size_t NC, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbRecs r;
+    r.n = views * NC * 64;
+    r.trec = c.take<int4>(r.n * 2);
+    r.tbox = c.take<uint2>(r.n);
+    r.cbox = c.take<uint2>(views * NC);
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return r;
+}
 
 // True if every pixel centre the triangle's SNAPPED outline can cover evaluates to a depth z/w inside [-1, 1] in
 // vb_depth_test's arithmetic, so that coverage = the integer edge test alone.  All w > 0 (no near-plane crossing).
@@ -274,6 +365,14 @@ constexpr int VB_SMALL_BOX = 3;  // boxes of up to this many pixel centres a sid
                                  // fourth row and column cost the VALU-bound kernel 7 % at Franka 16 x 1080p and drop nothing the
                                  // job kernel notices; 2: the job kernel pays 2.3 us at 8 views for the 3 x 3 boxes that cover nothing)
 constexpr int VB_VERTEX_WAVES = 5;  // (five workgroups per CU stay resident: the launch deals the work accordingly)
+// vb_vertex_kernel's chunk_role.  The views of a step go through the chain in chunks (one, unless views x links exceeds
+// what a job kernel handles):
+enum VbRole {
+    VB_ROLE_FIRST_CHUNK = 1,  // the per-step housekeeping happens here
+    VB_ROLE_LATER_CHUNK = 2,  // only the per-chunk counters are re-armed
+    VB_ROLE_CHUNK_MASK = 3,
+    VB_ROLE_POS_ONLY = 4,     // flag: the scoring op's chain (depth class "coverage decides")
+};
 template <bool HEAD>
 __global__ void __launch_bounds__(256, VB_VERTEX_WAVES)
 vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ vert_link,
@@ -282,12 +381,12 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
                  int nzacc, int* __restrict__ meta, int B, int gx, int xcd_views, VbHeavy hv, int chunk_role) {
     __shared__ float Tc[16];
     __shared__ float M[32][16];
-    // 1-D grid of B * gx workgroups.  xcd_views > 0 (B a multiple of 8): workgroup w runs on XCD w % 8 (observed, used
-    // for L2 locality only) and that XCD takes views [xcd * B / 8, (xcd + 1) * B / 8) -- the same views whose jobs stage 2
-    // gives to that XCD, so the records it reads were written through the same L2.
+    // 1-D grid of B * gx workgroups.  xcd_views > 0 (B a multiple of VB_XCDS): workgroup w runs on XCD w % VB_XCDS and
+    // that XCD takes views [xcd * xcd_views, (xcd + 1) * xcd_views) -- the same views whose jobs stage 2 gives to that XCD,
+    // so the records it reads were written through the same L2.
     int b, bx;
     if (xcd_views > 0) {
-        const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+        const int xcd = blockIdx.x & (VB_XCDS - 1), k = blockIdx.x >> VB_XCD_BITS;
         b = xcd * xcd_views + k / gx;
         bx = k - (k / gx) * gx;
     } else {
@@ -295,13 +394,10 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
         bx = blockIdx.x - b * gx;
     }
     const int tid = threadIdx.x, L = g.L, H = g.H, W = g.W;
-    // chunk_role: the views of a step go through the chain in chunks (one, unless views x links exceeds what a job
-    // kernel handles): 1 = first chunk (the per-step housekeeping happens here), 2 = a later one (only the per-chunk
-    // counters are re-armed)
-    const bool pos_only = (chunk_role & 4) != 0;  // (the scoring op's chain)
-    chunk_role &= 3;
-    const bool first = bx == 0 && b == 0 && chunk_role == 1;
-    const bool rearm = bx == 0 && b == 0 && chunk_role == 2;
+    const bool pos_only = (chunk_role & VB_ROLE_POS_ONLY) != 0;
+    chunk_role &= VB_ROLE_CHUNK_MASK;
+    const bool first = bx == 0 && b == 0 && chunk_role == VB_ROLE_FIRST_CHUNK;
+    const bool rearm = bx == 0 && b == 0 && chunk_role == VB_ROLE_LATER_CHUNK;
     // A view's work items: [0, nvb) blocks of 256 vertices (-> posc; nvb = 0 where the plan computes clip-space vertices on
     // demand, see VbLazy), then groups of four clusters (one wave per cluster, one lane per triangle).  The workgroup takes items bx, bx + gx, ...: the pose head above every item (exponential,
     // matrices: ~3 us of dependent arithmetic) is paid once per workgroup, not once per 256 vertices -- with one item per
@@ -422,7 +518,7 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
             for (int i = tid; i < n2; i += 256) hv.stamp[min(vb_hint_dense(hv.mlist[cur * VB_MED_CAP + i], g.nt, g.ntx), B * L * g.nt - 1)] = -gen;
         }
         if (tid < 8) meta[tid] = 0;                          // overflow flag, spill cursor
-        if (tid < VB_LINES) *vb_line(meta, tid) = 0;         // job cursors of the 8 XCDs, tickets, slow-job count
+        if (tid < VB_LINES) *vb_line(meta, tid) = 0;         // job cursors of the XCDs, tickets, slow-job count
     }
     if (rearm) {  // a later chunk of the same step: cursors and tickets again, the overflow flag stays
         if (tid < 8 && tid != EHR_META_OVERFLOW) meta[tid] = 0;
@@ -1218,18 +1314,17 @@ __device__ __forceinline__ bool vb_unit_tiles(const int* __restrict__ bx, int W,
 // Kernel-wide arguments of a job (what the job kernel's helpers need besides the job itself).
 constexpr int VB_CULL_BATCHES = 2;  // batches of 64 cluster boxes requested together
 constexpr int VB_CULL_GROUP = 8;    // candidate clusters whose triangle boxes are requested together
+// (vb_slow_kernel takes this struct by value: with this field order, behind `meta`, it spills 82 scalar registers; other
+//  orders up to 132, the flat argument list it replaces 127 -- compare tools/kres.py before and after touching it.)
 struct VbJobArgs {
-    VbRecs rc;
     const float* verts;   // [V][3] object-space vertices
     const float* mvp;     // [B][L][16] the chunk's (view, link) matrices: clip-space vertices are computed on demand (VbLazy) ...
-    const float4* posc;   // ... or read from here ([B][V]) where the plan keeps them (NULL: lazy)
-    const int4* cvidx;    // [NC * 64] {v0, v1, v2, triangle} of every cluster slot
-    const int* lcoff;     // LDS: first cluster of every link
-    unsigned* jid;        // job slots: triangle ids of the region's pixels
-    u64* jcov;            //            coverage bitmap (region-linear, VB_WORDS words)
-    int* jdesc;
-    int* jn;
+    VbRecs rc;
     int NC, V, W, H, L;
+    VbSlots sl;
+    const int4* cvidx;    // [NC * 64] {v0, v1, v2, triangle} of every cluster slot
+    const float4* posc;   // ... or read from here ([B][V]) where the plan keeps them (NULL: lazy)
+    const int* lcoff;     // first cluster of every link (the job kernel: its copy in LDS)
 };
 
 // Culls the link's clusters and triangles against the job's region and rasterizes this wave's share of them into the
@@ -1386,7 +1481,7 @@ __device__ __forceinline__ void vb_publish(const VbJobArgs& A, const u64* key_, 
                                            int ty) {
     const int lane = lane_id();
     VB_WAVE_SYNC();
-    unsigned* const dst = A.jid + (size_t)job * VB_RN;
+    unsigned* const dst = A.sl.jid + (size_t)job * VB_RN;
 #pragma unroll
     for (int k = 0; k < VB_WORDS; k++) {
         const unsigned i = 64u * k + lane;
@@ -1398,9 +1493,9 @@ __device__ __forceinline__ void vb_publish(const VbJobArgs& A, const u64* key_, 
         const unsigned i = 64u * k + lane;
         const unsigned row = (unsigned)vb_div_rw((int)i), col = i - row * VB_RW;
         const u64 w = __ballot(i < (unsigned)VB_RN && ((cov_[row < (unsigned)VB_RH ? row : 0] >> col) & 1ull));
-        if (lane == 0) A.jcov[(size_t)job * VB_WORDS + k] = w;
+        if (lane == 0) A.sl.jcov[(size_t)job * VB_WORDS + k] = w;
     }
-    if (lane == 0) A.jdesc[job] = u | (tx << 9) | (ty << 19);
+    if (lane == 0) A.sl.jdesc[job] = u | (tx << 9) | (ty << 19);
 }
 
 // A whole job on one wave with the general triangle path compiled in (near-plane clipping, 64-bit edge functions): what a
@@ -1431,8 +1526,8 @@ __device__ __forceinline__ void vb_job_slow(const VbJobArgs& A, VbWaveLds& S, in
     if (drawn > 0) {
         vb_publish(A, S.key, S.cov, job, u, tx, ty);
     } else if (lane == 0) {
-        A.jn[job] = -1;
-        A.jdesc[job] = -1;
+        A.sl.jn[job] = -1;
+        A.sl.jdesc[job] = -1;
     }
 }
 
@@ -1446,13 +1541,13 @@ __device__ __forceinline__ void vb_job_slow(const VbJobArgs& A, VbWaveLds& S, in
 // A job that met a triangle for the general path goes on the list vb_slow_kernel works off.  The solver-step form of the
 // chain does not launch that kernel until a step has needed it (slow_list == NULL: an empty launch costs the step 1.7 us
 // and a robot in front of the camera never has such a triangle): then the job is marked empty and the step REPORTS it --
-// overflow bit 4, so loss and gradient come out NaN and the optimiser state stays as it was; ehr_fused_status() returns
+// VB_FLAG_NEED_SLOW among the overflow bits, so loss and gradient come out NaN and the optimiser state stays as it was; ehr_fused_status() returns
 // EHR_ERR_RETRY and switches the pass on for the context's later calls.
-#define VB_FLAG_NEED_SLOW 4
 __device__ __forceinline__ void vb_put_aside(int4* __restrict__ slow_list, int* __restrict__ meta, int* __restrict__ jn,
                                              int* __restrict__ jdesc, int job, int u, int tx, int ty) {
     if (slow_list) {
-        slow_list[atomicAdd(vb_line(meta, 17), 1)] = make_int4(job, u, tx, ty);
+        int* const nslow = vb_line(meta, VB_LINE_SLOW_COUNT);
+        slow_list[atomicAdd(nslow, 1)] = make_int4(job, u, tx, ty);
     } else {
         atomicOr(&meta[EHR_META_OVERFLOW], VB_FLAG_NEED_SLOW);
         jn[job] = -1;
@@ -1468,11 +1563,8 @@ struct VbResolveArgs {
     int L;
     const int4* tri4;     // [T] padded index table
     const int4* opp4;     // [T] opposite vertices (edge topology)
-    int* jn;              // job slots: number of blended pairs (-1: the link contributes nothing to the tile)
-    float* jval;          //            the link's 256 antialiased values
-    VbItem* jitems;       //            blended pairs for the backward pass
-    int* jspill;
-    VbItem* spill;
+    VbSlots sl;
+    VbItem* spill;        // pool of blended pairs for jobs that exceed their slot
     int* meta;
     int V, T, W, H, spill_cap, want_grad;
 };
@@ -1492,12 +1584,9 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
     const int lane = lane_id();
     const int4* const tri4 = Q.tri4;
     const int4* const opp4 = Q.opp4;
-    int* const jn = Q.jn;
-    float* const jval = Q.jval;
-    VbItem* const jitems = Q.jitems;
-    int* const jspill = Q.jspill;
-    VbItem* const spill = Q.spill;
-    int* const meta = Q.meta;
+    int *const jn = Q.sl.jn, *const jspill = Q.sl.jspill, *const meta = Q.meta;
+    float* const jval = Q.sl.jval;
+    VbItem *const jitems = Q.sl.jitems, *const spill = Q.spill;
     const int V = Q.V, T = Q.T, W = Q.W, H = Q.H, spill_cap = Q.spill_cap, want_grad = Q.want_grad;
 #define KT(i) (ids[i])
     const int r = lane >> 3, c4 = (lane & 7) * 4;
@@ -1720,25 +1809,35 @@ __device__ __forceinline__ void vb_zero_tile_row(float* __restrict__ mask, size_
     }
 }
 
-struct VbCompArgs {  // what the composite stage needs besides its LDS tables
-    BinGeom g;
-    int B;
-    const float* mvp;    // [B][L][16] (clip-space vertices on demand: VbLazy)
-    int V;
-    const float* verts;
-    const int* jn;
-    const float* jval;
-    const VbItem* jitems;
-    const int* jspill;
-    int jcap;
-    const float* ref;
-    float* mask;
-    long long* facc;
-    int nls, want_grad, vec_ok;
-    const VbItem* spill;
-    int spill_cap;
-    int* meta;
+// What the composite stage needs besides its LDS tables.  vb_composite_kernel takes the struct by value, and the ORDER of the
+// fields (with StepTail behind the struct) is what the register allocator's result depends on: this order, found by trying
+// 160 random ones, is the one where every variant spills fewer scalar registers than the flat argument list it replaces
+// (<TAIL,FILL> 39, <TAIL> 37, <FILL> 37, <> 31; before 48 / 44 / 38 / 32; other orders 29-74).  Adding or moving a field
+// moves those figures: compare tools/kres.py before and after (profiles/r07_scratch_layout_refactor.md holds the table).
+// (Read in place through the kernarg pointer instead, the fields are fetched again in the tile loop: 16-19 spilled, and
+// 0.5-1 % of the step slower.)
+struct VbCompArgs {
     const long long* tsum;
+    int nls, want_grad, vec_ok;
+    float* loss;         // (loss .. lbox_all, ref_flag: for the finish stage, run by the last-arriving workgroup of the call's
+    int B;               //  last chunk of views -- do_finish -- over ALL views of the call)
+    long long* facc;     // the chunk's accumulators
+    VbSlots sl;          // (read only here)
+    int do_finish, B_all;
+    const float* mvp;    // [B][L][16] (clip-space vertices on demand: VbLazy)
+    int spill_cap;
+    int* lbox_all;
+    float* mask;
+    const float* verts;
+    const float* ref;
+    const long long* vtot_all;
+    int* meta;
+    float* grad_mvp;
+    const VbItem* spill;
+    int V;
+    const long long* facc_all;
+    const int* ref_flag;
+    BinGeom g;
 };
 
 // The composite stage's work items of ONE wave (slot `wslot` of the `nslots` wave slots its XCD has; `nwg` workgroups in
@@ -1750,15 +1849,10 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const int W = g.W, H = g.H, L = g.L, B = C.B, U = B * L;
     const bool sparse = C.tsum != nullptr;
-    const int jcap = C.jcap, nls = C.nls, want_grad = C.want_grad, vec_ok = C.vec_ok, V = C.V, spill_cap = C.spill_cap;
-    const float* const mvpc = C.mvp;
-    const float* const verts = C.verts;
-    const int* const jn = C.jn;
-    const float* const jval = C.jval;
-    const VbItem* const jitems = C.jitems;
-    const int* const jspill = C.jspill;
-    const VbItem* const spill = C.spill;
-    const float* const ref = C.ref;
+    const int jcap = C.sl.jcap, nls = C.nls, want_grad = C.want_grad, vec_ok = C.vec_ok, V = C.V, spill_cap = C.spill_cap;
+    const float *const mvpc = C.mvp, *const verts = C.verts, *const jval = C.sl.jval, *const ref = C.ref;
+    const int *const jn = C.sl.jn, *const jspill = C.sl.jspill;
+    const VbItem *const jitems = C.sl.jitems, *const spill = C.spill;
     float* const mask = C.mask;
     long long* const facc = C.facc;
     int* const meta = C.meta;
@@ -1767,10 +1861,10 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     // its own has a job there, so that every tile with a job comes up exactly once and the others never
     const int nitems = sparse ? min(s_jbase[U], jcap) : B * g.nt;
     // XCD-aware order (locality only): every XCD takes a contiguous run of items
-    const int per_xcd = (nitems + 7) >> 3;
+    const int per_xcd = vb_xcd_share(nitems);
     const int ibeg = xcd * per_xcd, iend = min(ibeg + per_xcd, nitems);
     const int istep = nslots;
-    const int acc_stride = 12 * L + nls * VB_LOSS_STRIDE;
+    const int acc_stride = vb_acc_stride(L, nls);
     const int r = lane >> 3, c4 = (lane & 7) * 4;
     const float invL = __builtin_amdgcn_rcpf((float)L);  // (u / L by vb_div_small)
     for (int item = ibeg + wslot; item < iend; item += istep) {
@@ -1996,24 +2090,11 @@ struct VbJobParams {
     VbClusters cl;
     VbRecs rc;
     const int* lbox;
-    int* jn;
-    unsigned* jid;
-    int* jdesc;
-    int* jbase;
-    unsigned* jutile;
-    int jcap;
-    int* meta;
     int use_hint;  // 1: deal the previous step's heavy and long jobs (the hint names jobs by their dense id in a chunk)
     VbHeavy hv;
-    const float* verts;  // object-space vertices and the chunk's matrices: clip-space vertices are computed on demand (VbLazy) ...
-    const float* mvp;
-    const float4* posc;  // ... or kept per view ([B][V]) by the eager instantiations (NULL: lazy)
-    int V;
     VbSlotIdx si;
-    u64* jcov;
-    int4* slow_list;
     int heavy_t, med_t0;
-    VbResolveArgs rq;
+    VbResolveArgs rq;  // the scene, the job slots and the meta block: the resolve stage runs on the wave that drew the job
 };
 typedef const VbJobParams __attribute__((address_space(4)))* VbJobParamsPtr;
 __device__ __forceinline__ VbJobParamsPtr vb_job_params() {
@@ -2021,13 +2102,11 @@ __device__ __forceinline__ VbJobParamsPtr vb_job_params() {
     asm volatile("" : "+s"(p));  // (what the optimiser cannot see through it cannot hoist to the kernel's entry)
     return p;
 }
-template <class P>
-__device__ __forceinline__ VbResolveArgs vb_load_rq(P p) {
-    VbResolveArgs q;
-    q.verts = p->rq.verts; q.mvp = p->rq.mvp; q.posc = p->rq.posc; q.L = p->rq.L; q.tri4 = p->rq.tri4; q.opp4 = p->rq.opp4; q.jn = p->rq.jn; q.jval = p->rq.jval;
-    q.jitems = p->rq.jitems; q.jspill = p->rq.jspill; q.spill = p->rq.spill; q.meta = p->rq.meta; q.V = p->rq.V;
-    q.T = p->rq.T; q.W = p->rq.W; q.H = p->rq.H; q.spill_cap = p->rq.spill_cap; q.want_grad = p->rq.want_grad;
-    return q;
+// a whole sub-struct of the parameters, copied through a generic pointer: address-space inference turns the copy back into
+// scalar loads of the kernarg segment (checked in the ISA: the job kernels hold no flat_load at all)
+template <class T>
+__device__ __forceinline__ T vb_prm_copy(const T __attribute__((address_space(4)))* p) {
+    return *(const T*)p;
 }
 // COVER (the scoring op): jcov = the (view, tile) coverage words [B][nt][4] the jobs OR their tile's interior into, jn = one
 // sticky flag raised by a job that met a triangle whose depth class does not let coverage decide; no slots, no lists.
@@ -2037,13 +2116,12 @@ vb_job_kernel(VbJobParams) {
     __shared__ VbWaveLds lds_all[4];
     // PRM(field): a kernel parameter, read where it is used (see VbJobParams)
 #define PRM(f) (vb_job_params()->f)
-#define VB_RQ() vb_load_rq(vb_job_params())
     const int W = PRM(g.W), H = PRM(g.H), L = PRM(g.L), gnt = PRM(g.nt), gntx = PRM(g.ntx);
-    const int B = PRM(B), V = PRM(V);
+    const int B = PRM(B), V = PRM(rq.V);
     int heavy_t = max(PRM(heavy_t), PRM(hv.gen)[6]);  // (the value in force: the vertex kernel adapts it, see VbHeavy)
-    const float* const pverts = PRM(verts);
-    const float* const pmvp = PRM(mvp);
-    const float4* const posc = LAZY ? nullptr : PRM(posc);
+    const float* const pverts = PRM(rq.verts);
+    const float* const pmvp = PRM(rq.mvp);
+    const float4* const posc = LAZY ? nullptr : PRM(rq.posc);
     // the scheduling hint of the previous step is requested before anything else, in ONE round trip: which of the two
     // lists is the one to consume follows from the generation, so both lists' counts and this workgroup's entry of either are
     // requested together with it (they were a second, dependent round trip on every wave's way to its first job)
@@ -2115,38 +2193,32 @@ vb_job_kernel(VbJobParams) {
         // job slots are numbered like the jobs: stage 3 finds a (view, link, tile) slot from the link's first job
         // (every entry this wave may read here it has written itself, or a barrier lies in between: see above)
         if (!COVER) {
-            for (int u = tid; u <= U; u += 256) PRM(jbase)[u] = upre[u];
-            for (int u = tid; u < U; u += 256) PRM(jutile)[u] = utile[u];
+            for (int u = tid; u <= U; u += 256) PRM(rq.sl.jbase)[u] = upre[u];
+            for (int u = tid; u < U; u += 256) PRM(rq.sl.jutile)[u] = utile[u];
         }
         if (tid == 0) {
-            PRM(meta)[5] = total;  // number of jobs (the resolve kernel's loop bound)
-            if (!COVER && total > PRM(jcap)) PRM(meta)[EHR_META_OVERFLOW] = 1;  // cannot happen with one slot per (view, link, tile)
+            PRM(rq.meta)[5] = total;  // number of jobs (the resolve kernel's loop bound)
+            if (!COVER && total > PRM(rq.sl.jcap)) PRM(rq.meta)[EHR_META_OVERFLOW] = 1;  // cannot happen with one slot per (view, link, tile)
         }
     }
-    if (!COVER) total = min(total, PRM(jcap));
-    // XCD-aware order: workgroup w runs on XCD w % 8 (observed, used for L2 locality only): every XCD takes a contiguous
+    if (!COVER) total = min(total, PRM(rq.sl.jcap));
+    // XCD-aware order (workgroup w runs on XCD w % VB_XCDS; used for L2 locality only): every XCD takes a contiguous
     // eighth of the job list, so that a view's vertices, boxes and records stay in one L2.  Inside that eighth every wave
     // takes one job statically; the jobs beyond that are claimed (one returning atomic on the XCD's cursor) by whichever
     // wave finishes first.  Jobs differ by two orders of magnitude in cost: dealt statically, the kernel waits for a wave
     // that got a heavy SECOND job; claimed from the start, 500 waves hit each cursor at once (~12 ns per same-address
     // atomic) and the kernel is 20 % slower.
-    const int per_xcd = (total + 7) >> 3, xcd = blockIdx.x & 7;
+    const int per_xcd = vb_xcd_share(total), xcd = blockIdx.x & (VB_XCDS - 1);
     const int jbeg = xcd * per_xcd, jend = min(jbeg + per_xcd, total);
-    int* const cursor = vb_line(PRM(meta), xcd);
+    int* const cursor = vb_line(PRM(rq.meta), VB_LINE_JOB_CURSOR + xcd);
     VbJobArgs A;
-    A.rc.tbox = PRM(rc.tbox);
-    A.rc.cbox = PRM(rc.cbox);
-    A.rc.trec = PRM(rc.trec);
-    A.rc.n = PRM(rc.n);
+    A.rc = vb_prm_copy(&PRM(rc));
     A.verts = pverts;
     A.mvp = pmvp;
     A.posc = posc;
     A.cvidx = PRM(si.cvidx);
     A.lcoff = lcoff;
-    A.jid = PRM(jid);
-    A.jcov = PRM(jcov);
-    A.jdesc = PRM(jdesc);
-    A.jn = PRM(jn);
+    A.sl = vb_prm_copy(&PRM(rq.sl));
     A.NC = PRM(cl.NC);
     A.V = V;
     A.W = W;
@@ -2231,11 +2303,11 @@ vb_job_kernel(VbJobParams) {
         }
         if (wave == 0) {
             if (any_drawn & 2) {  // put aside for vb_slow_kernel
-                if (lane == 0) vb_put_aside(PRM(slow_list), PRM(meta), PRM(jn), PRM(jdesc), job, u, tx, ty);
+                if (lane == 0) vb_put_aside(PRM(rq.sl.slow_list), PRM(rq.meta), PRM(rq.sl.jn), PRM(rq.sl.jdesc), job, u, tx, ty);
             } else if (any_drawn) {
             } else if (lane == 0) {
-                PRM(jn)[job] = -1;
-                PRM(jdesc)[job] = -1;
+                PRM(rq.sl.jn)[job] = -1;
+                PRM(rq.sl.jdesc)[job] = -1;
             }
             if (lane == 0) {
                 s_heavy[0] = 0;
@@ -2250,16 +2322,16 @@ vb_job_kernel(VbJobParams) {
     }
 
     // (the loop's last barrier is behind us: waves 1-3 go on to their own jobs, nobody touches wave 0's LDS but wave 0)
-    if (!COVER && wave == 0 && hres_job >= 0) vb_resolve_from_lds<LAZY>(VB_RQ(), S, S.key, S.cov, (size_t)hres_job, hres_b, hres_l, hres_rx0, hres_ry0);
+    if (!COVER && wave == 0 && hres_job >= 0) vb_resolve_from_lds<LAZY>(vb_prm_copy(&PRM(rq)), S, S.key, S.cov, (size_t)hres_job, hres_b, hres_l, hres_rx0, hres_ry0);
     __builtin_amdgcn_s_setprio(0);
     // workgroups that just spent their time on a heavy job take no static job: the first hk of this XCD's workgroups
     const int nhw = min(nheavy, (int)gridDim.x);
-    const int hk = (nhw > xcd) ? (nhw - xcd + 7) >> 3 : 0;
-    const int kx = blockIdx.x >> 3;                      // this workgroup's index inside its XCD
-    const int G8 = (int)gridDim.x >> 3;                  // workgroups per XCD
-    // static first jobs: wave rx of this XCD's static waves (global rank 8 rx + xcd) takes long job number <rank> of the
+    const int hk = (nhw > xcd) ? vb_xcd_share(nhw - xcd) : 0;
+    const int kx = blockIdx.x >> VB_XCD_BITS;            // this workgroup's index inside its XCD
+    const int G8 = (int)gridDim.x >> VB_XCD_BITS;        // workgroups per XCD
+    // static first jobs: wave rx of this XCD's static waves (global rank VB_XCDS rx + xcd) takes long job number <rank> of the
     // previous step if there is one, else the (rx - nmx)-th job of the XCD's eighth; the rest of the eighth is claimed
-    const int nmx = (nmed > xcd) ? (nmed - xcd + 7) >> 3 : 0;  // long jobs that go to this XCD's waves (<= the static waves, see mcap)
+    const int nmx = (nmed > xcd) ? vb_xcd_share(nmed - xcd) : 0;  // long jobs that go to this XCD's waves (<= the static waves, see mcap)
     // (the long jobs one per WORKGROUP first -- rank wave * (G8 - hk) + (kx - hk) -- instead of four to a workgroup: measured in
     //  round 6, no difference: 41.1 / 33.9 / 90.4 us job stage either way at 8 views / 1 view / Franka)
     const int rx = (kx - hk) * 4 + wave;
@@ -2272,7 +2344,7 @@ vb_job_kernel(VbJobParams) {
         if (list_first) {
             list_first = false;
             __builtin_amdgcn_s_setprio(VB_PRIO_LONG);
-            const int id = PRM(hv.mlist)[hcur * VB_MED_CAP + 8 * rx + xcd];
+            const int id = PRM(hv.mlist)[hcur * VB_MED_CAP + VB_XCDS * rx + xcd];
             u = min((int)((unsigned)id >> 22), U - 1);
             tx = id & 1023;
             ty = (id >> 10) & 4095;
@@ -2346,7 +2418,7 @@ vb_job_kernel(VbJobParams) {
                 vb_flush<true, LAZY>(S, S.key, S.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
             VB_WAVE_SYNC();
             if (drawn < 0 || S.bad) {  // a triangle for the general path, or a drawn pixel with a depth <= 0: coverage cannot
-                if (lane == 0) PRM(jn)[0] = 1;  // decide here and the caller falls back for the whole call
+                if (lane == 0) PRM(rq.sl.jn)[0] = 1;  // decide here and the caller falls back for the whole call
                 continue;
             }
             if (drawn > 0) {
@@ -2355,14 +2427,14 @@ vb_job_kernel(VbJobParams) {
                 if (lane < 4) {
                     const u64 w = ((S.cov[2 * lane + 1] >> 1) & 0xffffffffull) | (((S.cov[2 * lane + 2] >> 1) & 0xffffffffull) << 32);
                     // (layout [candidate][tile][pose][4]: the count kernel reads a candidate's words of a tile in one piece;
-                    //  PRM(jcap) carries S, the poses per candidate, in this form)
-                    if (w) atomicOr((unsigned long long*)&PRM(jcov)[((((size_t)(b / PRM(jcap)) * gnt + (size_t)ty * gntx + tx) * PRM(jcap) + (b % PRM(jcap))) * 4 + lane)], w);
+                    //  PRM(rq.sl.jcap) carries S, the poses per candidate, in this form)
+                    if (w) atomicOr((unsigned long long*)&PRM(rq.sl.jcov)[((((size_t)(b / PRM(rq.sl.jcap)) * gnt + (size_t)ty * gntx + tx) * PRM(rq.sl.jcap) + (b % PRM(rq.sl.jcap))) * 4 + lane)], w);
                 }
             }
             continue;
         }
         if (drawn < 0) {  // a triangle for the general path (near-plane clipping, huge extent): put the job aside
-            if (lane == 0) vb_put_aside(PRM(slow_list), PRM(meta), PRM(jn), PRM(jdesc), job, u, tx, ty);
+            if (lane == 0) vb_put_aside(PRM(rq.sl.slow_list), PRM(rq.meta), PRM(rq.sl.jn), PRM(rq.sl.jdesc), job, u, tx, ty);
             continue;
         }
         if (dln > 0) vb_flush<false, LAZY>(S, S.key, S.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
@@ -2374,47 +2446,26 @@ vb_job_kernel(VbJobParams) {
         }
         if (drawn == 0) {  // the link's box touches this tile, its triangles do not
             if (lane == 0) {
-                PRM(jn)[slot] = -1;
-                PRM(jdesc)[slot] = -1;
+                PRM(rq.sl.jn)[slot] = -1;
+                PRM(rq.sl.jdesc)[slot] = -1;
             }
             continue;
         }
-        vb_resolve_from_lds<LAZY>(VB_RQ(), S, S.key, S.cov, slot, b, l, rx0, ry0);
+        vb_resolve_from_lds<LAZY>(vb_prm_copy(&PRM(rq)), S, S.key, S.cov, slot, b, l, rx0, ry0);
     }
 }
 #undef PRM
-#undef VB_RQ
 
 // Stage 2a (normally empty): the jobs the lean code put aside, one wave each, with the general triangle path.
 __global__ void __launch_bounds__(256)
-vb_slow_kernel(BinGeom g, VbClusters cl, VbRecs rc, const float* __restrict__ verts, const float* __restrict__ mvp,
-               const float4* __restrict__ posc, int V, VbSlotIdx si,
-               unsigned* __restrict__ jid, u64* __restrict__ jcov, int* __restrict__ jdesc, int* __restrict__ jn,
-               const int4* __restrict__ slow_list, const int* __restrict__ meta) {
-    const int n = *vb_line(const_cast<int*>(meta), 17);
+vb_slow_kernel(const int* __restrict__ meta, VbJobArgs A) {
+    const int n = *vb_line(const_cast<int*>(meta), VB_LINE_SLOW_COUNT);
     if (n == 0) return;
     __shared__ VbWaveLds lds_all[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    VbJobArgs A;
-    A.rc = rc;
-    A.verts = verts;
-    A.mvp = mvp;
-    A.posc = posc;
-    A.cvidx = si.cvidx;
-    A.lcoff = cl.coff;
-    A.jid = jid;
-    A.jcov = jcov;
-    A.jdesc = jdesc;
-    A.jn = jn;
-    A.NC = cl.NC;
-    A.V = V;
-    A.W = g.W;
-    A.H = g.H;
-    A.L = g.L;
-    (void)lane;
+    const int wave = threadIdx.x >> 6;
     for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
-        const int4 e = slow_list[i];
-        if (posc)  // (not a hot kernel: both forms compiled in, chosen per launch)
+        const int4 e = A.sl.slow_list[i];
+        if (A.posc)  // (not a hot kernel: both forms compiled in, chosen per launch)
             vb_job_slow<false>(A, lds_all[wave], e.x, e.y, e.z, e.w);
         else
             vb_job_slow<true>(A, lds_all[wave], e.x, e.y, e.z, e.w);
@@ -2426,35 +2477,28 @@ vb_slow_kernel(BinGeom g, VbClusters cl, VbRecs rc, const float* __restrict__ ve
 // other job was resolved by the job kernel's wave that drew it, straight from LDS (vb_resolve_from_lds).  The solver step
 // launches this kernel only together with vb_slow_kernel.
 __global__ void __launch_bounds__(256)
-vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float* __restrict__ mvp,
-                  const float4* __restrict__ posc, int V, int T, const int4* __restrict__ tri4,
-                  const int4* __restrict__ opp4, const unsigned* __restrict__ jid, const u64* __restrict__ jcov,
-                  const int* __restrict__ jdesc,
-                  int* __restrict__ jn, float* __restrict__ jval, VbItem* __restrict__ jitems,
-                  int* __restrict__ jspill, int jcap, int want_grad, VbItem* __restrict__ spill, int spill_cap,
-                  int* __restrict__ meta, const int4* __restrict__ slow_list) {
+vb_resolve_kernel(VbResolveArgs Q) {
     __shared__ VbResolveLds lds_all[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     VbResolveLds& S = lds_all[wave];
-    const int W = g.W, H = g.H, L = g.L;
-    (void)B;
-    const int n = *vb_line(meta, 17);  // jobs put aside (vb_put_aside)
+    const int L = Q.L;
+    const int n = *vb_line(Q.meta, VB_LINE_SLOW_COUNT);  // jobs put aside (vb_put_aside)
     for (int it = (int)blockIdx.x * 4 + wave; it < n; it += (int)gridDim.x * 4) {
-        const int job = slow_list[it].x;
-        if (job >= jcap) continue;
+        const int job = Q.sl.slow_list[it].x;
+        if (job >= Q.sl.jcap) continue;
         const size_t slot = (size_t)job;
         // the ids are requested together with the descriptor (one round trip; an undrawn slot holds stale ids, unused)
         unsigned idw[VB_WORDS];
         {
-            const unsigned* const src = jid + slot * VB_RN;
+            const unsigned* const src = Q.sl.jid + slot * VB_RN;
 #pragma unroll
             for (int k = 0; k < VB_WORDS; k++) {
                 const unsigned i = 64u * k + lane;
                 idw[k] = (i < (unsigned)VB_RN) ? src[i] : 0xffffffffu;
             }
         }
-        const u64 mycw = (lane < VB_WORDS) ? jcov[slot * VB_WORDS + lane] : 0ull;  // coverage bitmap of the region
-        const int de = jdesc[job];
+        const u64 mycw = (lane < VB_WORDS) ? Q.sl.jcov[slot * VB_WORDS + lane] : 0ull;  // coverage bitmap of the region
+        const int de = Q.sl.jdesc[job];
         if (de < 0) continue;  // nothing drawn: the job kernel has already marked the slot
         const int u = de & 511, tx = (de >> 9) & 1023, ty = (de >> 19) & 4095;
         const int b = u / L;
@@ -2474,10 +2518,7 @@ vb_resolve_kernel(BinGeom g, int B, const float* __restrict__ verts, const float
             if (i < (unsigned)VB_RN)
                 S.ids[i] = (idw[k] != 0xffffffffu) ? idw[k] : (((C[k] >> lane) & 1ull) ? VB_ID_COVERED : 0xffffffffu);
         }
-        VbResolveArgs Q;  // (wave-uniform; the compiler keeps what it needs in scalar registers)
-        Q.verts = verts; Q.mvp = mvp; Q.posc = posc; Q.L = L; Q.tri4 = tri4; Q.opp4 = opp4; Q.jn = jn; Q.jval = jval; Q.jitems = jitems; Q.jspill = jspill;
-        Q.spill = spill; Q.meta = meta; Q.V = V; Q.T = T; Q.W = W; Q.H = H; Q.spill_cap = spill_cap; Q.want_grad = want_grad;
-        if (posc)
+        if (Q.posc)
             vb_resolve_job<false>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
         else
             vb_resolve_job<true>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
@@ -2547,64 +2588,52 @@ vb_refsum_kernel(BinGeom g, int B, const float* __restrict__ ref, int vec_ok, lo
 // loss / grad_mvp [-> pose backward -> Adam], re-arms the link boxes.  vec_ok: W % 4 == 0 and 16-byte aligned images.
 template <bool TAIL, bool FILL>
 __global__ void __launch_bounds__(256, FILL ? 5 : 6)
-vb_composite_kernel(BinGeom g, int B, const float* __restrict__ mvp, int V, const float* __restrict__ verts,
-                    int* __restrict__ lbox, const int* __restrict__ jn, const float* __restrict__ jval,
-                    const VbItem* __restrict__ jitems, const int* __restrict__ jspill, const int* __restrict__ jbase,
-                    const unsigned* __restrict__ jutile, int jcap, const float* __restrict__ ref,
-                    float* __restrict__ mask, long long* __restrict__ facc, int nls, int want_grad, int vec_ok,
-                    const VbItem* __restrict__ spill, int spill_cap, int* __restrict__ meta,
-                    const long long* __restrict__ tsum, const long long* __restrict__ vtot,
-                    const int* __restrict__ ref_flag, float* __restrict__ loss,
-                    float* __restrict__ grad_mvp, StepTail tail, int do_finish, int B_all,
-                    const long long* __restrict__ facc_all, const long long* __restrict__ vtot_all,
-                    int* __restrict__ lbox_all) {
+vb_composite_kernel(VbCompArgs C, StepTail tail) {
     __shared__ float gpix_all[4][EHR_TILE_W * EHR_TILE_H];
     extern __shared__ int s_dyn[];  // [U + 1] first job of every (view, link) | [U] its tile range
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float* const gpix = gpix_all[wave];
-    const int W = g.W, H = g.H, L = g.L, U = B * L;
+    const int U = C.B * C.g.L;
     int* const s_jbase = s_dyn;
     unsigned* const s_utile = reinterpret_cast<unsigned*>(s_dyn + U + 1);
-    const bool sparse = tsum != nullptr;
-    for (int i = tid; i <= U; i += 256) s_jbase[i] = jbase[i];
-    for (int i = tid; i < U; i += 256) s_utile[i] = jutile[i];
+    const bool sparse = C.tsum != nullptr;
+    for (int i = tid; i <= U; i += 256) s_jbase[i] = C.sl.jbase[i];
+    for (int i = tid; i < U; i += 256) s_utile[i] = C.sl.jutile[i];
     // The links' screen boxes start "empty" in the next step.  Nobody reads them after the job kernel's prologue, so the
     // call's last composite launch re-arms them here, a store per thread of its first workgroups, instead of in the
     // finish stage at its end (where it was 32 stores per thread on the step's critical path).
-    if (do_finish && lbox_all)
-        for (int i = (int)blockIdx.x * 256 + tid; i < 16 * B_all * g.L; i += (int)gridDim.x * 256)
-            lbox_all[i] = (i & 2) ? INT_MIN : INT_MAX;  // 16 ints (one line) per box: min x, min y, max x, max y, padding
+    if (C.do_finish && C.lbox_all)
+        for (int i = (int)blockIdx.x * 256 + tid; i < VB_LBOX_STRIDE * C.B_all * C.g.L; i += (int)gridDim.x * 256)
+            C.lbox_all[i] = (i & 2) ? INT_MIN : INT_MAX;  // one line per box: min x, min y, max x, max y, padding
     __syncthreads();
-    VbCompArgs C;
-    C.g = g; C.B = B; C.mvp = mvp; C.V = V; C.verts = verts; C.jn = jn; C.jval = jval; C.jitems = jitems; C.jspill = jspill;
-    C.jcap = jcap; C.ref = ref; C.mask = mask; C.facc = facc; C.nls = nls; C.want_grad = want_grad; C.vec_ok = vec_ok;
-    C.spill = spill; C.spill_cap = spill_cap; C.meta = meta; C.tsum = tsum;
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7;
-    vb_composite_items<FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> 3) * 4 + wave, (nwg >> 3) * 4, nwg);
+    const int nwg = gridDim.x, xcd = blockIdx.x & (VB_XCDS - 1);
+    vb_composite_items<FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> VB_XCD_BITS) * 4 + wave, (nwg >> VB_XCD_BITS) * 4, nwg);
     // ---- the workgroup whose atomics are performed last runs the finish stage.  Every wave first waits until its own
     //      atomics have been performed (vmcnt covers them), then one lane takes a ticket on the XCD's counter and the
     //      last of an XCD one on the top counter: two levels, because a few thousand arrivals on ONE address serialise
     //      at ~12 ns each.  The accumulators are only ever touched by agent-scope atomics and read back with agent-scope
     //      loads (acc_load), so no cache maintenance is needed between the two.
-    if (!do_finish) return;  // (not the last chunk of views: the kernel boundary orders its sums before the last chunk's finish)
+    if (!C.do_finish) return;  // (not the last chunk of views: the kernel boundary orders its sums before the last chunk's finish)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __shared__ int s_last;
     if (tid == 0) {
         int last = 0;
-        const int per = nwg >> 3;  // workgroups per XCD counter (nwg is a multiple of 8)
-        if (atomicAdd(vb_line(meta, 8 + xcd), 1) == per - 1) last = atomicAdd(vb_line(meta, 16), 1) == 7;
+        const int per = nwg >> VB_XCD_BITS;  // workgroups per XCD counter (nwg is a multiple of VB_XCDS)
+        int* const xcd_ticket = vb_line(C.meta, VB_LINE_COMP_TICKET + xcd);
+        int* const top_ticket = vb_line(C.meta, VB_LINE_TOP_TICKET);
+        if (atomicAdd(xcd_ticket, 1) == per - 1) last = atomicAdd(top_ticket, 1) == VB_XCDS - 1;
         s_last = last;
     }
     __syncthreads();
     if (!s_last) return;
-    if (ref_flag && tid == 0 && ref_flag[0]) atomicOr(&meta[EHR_META_OVERFLOW], 1);  // the bound reference's own sums overflowed
+    if (C.ref_flag && tid == 0 && C.ref_flag[0]) atomicOr(&C.meta[EHR_META_OVERFLOW], 1);  // the bound reference's own sums overflowed
     __syncthreads();
     __shared__ double S[4][17];
     __shared__ float red_lds[8];
     __shared__ float Js[6][16];
-    finish_body<TAIL>(g, B_all, facc_all, sparse ? vtot_all : nullptr, loss, grad_mvp, meta, tail, nls, nullptr, VB_LOSS_STRIDE,
-                      gpix_all[0], S, red_lds, Js);
+    finish_body<TAIL>(C.g, C.B_all, C.facc_all, sparse ? C.vtot_all : nullptr, C.loss, C.grad_mvp, C.meta, tail, C.nls, nullptr,
+                      VB_LOSS_STRIDE, gpix_all[0], S, red_lds, Js);
 }
 
 // Content hash of the scoring op's mesh arrays: the cluster index holds copies of the vertex positions, so a mesh edited
@@ -2878,7 +2907,7 @@ static VbVertexGrid vb_vertex_grid(int num_cus, int nitems, int Bk) {
     const int items_per_wg = (nitems + per_view_cap - 1) / per_view_cap;
     VbVertexGrid v;
     v.gx = std::max(1, (nitems + items_per_wg - 1) / std::max(items_per_wg, 1));
-    v.xcd_views = (VB_XCD_SPLIT && (Bk % 8) == 0) ? Bk / 8 : 0;
+    v.xcd_views = (VB_XCD_SPLIT && (Bk % VB_XCDS) == 0) ? Bk / VB_XCDS : 0;
     return v;
 }
 
@@ -2893,7 +2922,7 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
     const int NC = std::max(ctx->vb_nc, 1);
     // The views of a call go through the chain in CHUNKS of Bc views (one chunk in the common case): the job kernel
     // keeps its (view, link) tables in LDS (VB_MAX_UNITS entries), and the per-chunk scratch -- clip-space vertices,
-    // raster records, job slots (3.5 KB each) -- is bounded to 24 GB of the 288 (EHR_VB_SCRATCH_MB) however many views a
+    // raster records (vb_recs), job slots (vb_slots, 3.5 KB each) -- is bounded to 24 GB of the 288 (EHR_VB_SCRATCH_MB) however many views a
     // call brings: a chunk costs a pass of the chain with its own tails, so chunks are as large as they may be (the reference
     // batches all frames of a data set in one step, configs/xarm7/example.yaml: batch_size 100).  A job = a (link, tile)
     // pair whose boxes touch; by default (`slack` <= 0) one slot per (link, tile) is provided, so nothing can overflow;
@@ -2901,17 +2930,15 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
     // the tiles of a typical frame; less scratch, larger chunks); a view that needs more (every pixel under more than
     // `slack` link boxes on average) is reported (loss = NaN, ehr_fused_status).
     BinGeom gp = make_geom(H, W, L);
-    const size_t slot_bytes = 256 * sizeof(float) + VB_JOB_ITEMS * sizeof(VbItem) + VB_WORDS * sizeof(u64) + 2 * sizeof(int) +
-                              VB_RN * sizeof(unsigned) + sizeof(int) + sizeof(int4);
     const double jobs_per_view = std::max(1.0, ((slack > 0.f) ? std::min((double)L, (double)slack) : (double)L) * gp.nt);
-    const double view_bytes = jobs_per_view * slot_bytes + (double)NC * (64 * 40 + 8) + (double)std::max(V, 1) * 16 +
-                              (double)L * gp.nt * 4;
+    const double view_bytes = jobs_per_view * VB_SLOT_BYTES + (double)NC * VB_CLUSTER_REC_BYTES + (double)std::max(V, 1) * sizeof(float4) +
+                              (double)L * gp.nt * sizeof(int);
     static const double budget = getenv("EHR_VB_SCRATCH_MB") ? atof(getenv("EHR_VB_SCRATCH_MB")) * 1048576.0 : 24576.0 * 1048576.0;
     int Bc = std::min(B, std::max(1, VB_MAX_UNITS / L));
     Bc = std::max(1, std::min(Bc, (int)(budget / view_bytes)));
     if (jobs_per_view * Bc > 2.0e9) return fail(EHR_ERR_INVALID, "ehr_fused_plan: views x links x tiles of a chunk exceeds 2e9");
     ctx->vb_chunk = Bc;
-    if ((rc = ctx->vb_acc.reserve(((size_t)B * (12 * (size_t)L + VB_LOSS_SLOTS * VB_LOSS_STRIDE)) * sizeof(long long) + EHR_META_INTS * sizeof(int) + (VB_LINES + 1) * 128))) return rc;
+    if ((rc = ctx->vb_acc.reserve((size_t)B * vb_acc_stride(L) * sizeof(long long) + VB_META_BYTES))) return rc;
     {   // Clip-space vertices: kept per view (posc, 16 B per vertex and view, written by the vertex kernel) or computed where
         // they are looked up (VbLazy).  Lazy pays where vertices outnumber the look-ups by far -- meshes with unshared
         // vertices (V ~ 3 T): Franka 16 x 1080p spends 168 of the vertex launch's 286 MB on them -- and costs the job kernel
@@ -2924,8 +2951,9 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
         }
         if (!ctx->vb_lazy && (rc = ctx->vb_posc.reserve((size_t)Bc * std::max(V, 1) * sizeof(float4)))) return rc;
     }
-    // per step and (view, cluster slot): trec 32 B | tbox 8 B, then cbox 8 B per (view, cluster)
-    if ((rc = ctx->vb_boxes.reserve((size_t)Bc * NC * (64 * 40 + 8)))) return rc;
+    size_t bytes;
+    vb_recs(nullptr, Bc, NC, &bytes);
+    if ((rc = ctx->vb_boxes.reserve(bytes))) return rc;
     {  // pool of blended pairs for jobs that exceed their slot (EHR_VB_SPILL_ITEMS: test hook for the overflow path)
         const char* e = getenv("EHR_VB_SPILL_ITEMS");
         ctx->vb_spill_cap = e ? std::max(0, atoi(e)) : VB_SPILL_ITEMS;
@@ -2937,17 +2965,12 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
         if ((rc = ctx->vb_refsum.reserve(((size_t)B * gp.nt + B + 1) * sizeof(long long)))) return rc;
         ctx->vb_ref = nullptr;  // a new plan forgets the binding
     }
-    {  // job slots of a chunk, compact (numbered like the jobs): value tile 1 KB | items 1 KB | coverage words | count | spill
-       // base | region ids 1.36 KB | descriptor | an entry of the slow-job list; then the links' first jobs and tile ranges
-        ctx->vb_jcap = (int)(jobs_per_view * Bc);
-        const size_t nslot = (size_t)ctx->vb_jcap;
-        if ((rc = ctx->vb_jobs.reserve(nslot * slot_bytes + (2 * (size_t)Bc * L + 1) * sizeof(int) + 32))) return rc;
-    }
-    {  // heavy-job hint: generation + two counts | two lists | stamp table (dense ids of a chunk)
-        const size_t ints = 8 + 2 * (size_t)VB_HEAVY_CAP + 2 * (size_t)VB_MED_CAP + (size_t)Bc * L * gp.nt;
-        if ((rc = ctx->vb_heavy.reserve(ints * sizeof(int)))) return rc;
-        EHR_HIP(hipMemset(ctx->vb_heavy.ptr, 0, ints * sizeof(int)));
-    }
+    ctx->vb_jcap = (int)(jobs_per_view * Bc);
+    vb_slots(nullptr, (size_t)ctx->vb_jcap, (size_t)Bc * L, &bytes);
+    if ((rc = ctx->vb_jobs.reserve(bytes))) return rc;
+    vb_heavy(nullptr, (size_t)Bc * L * gp.nt, &bytes);  // (the stamp table: dense ids of a chunk)
+    if ((rc = ctx->vb_heavy.reserve(bytes))) return rc;
+    EHR_HIP(hipMemset(ctx->vb_heavy.ptr, 0, bytes));
     if ((rc = ctx->vb_idx.reserve((size_t)2 * std::max(T, 1) * sizeof(int4)))) return rc;
     if (T > 0) {
         vb_pad_kernel<<<(T + 255) / 256, 256>>>(tris, T, (int4*)ctx->vb_idx.ptr);
@@ -2970,31 +2993,25 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
 }
 
 int ehr::vbuf_meta_read(ehr_ctx* ctx, int* meta4) {
-    const size_t off = (size_t)ctx->pB * (12 * (size_t)ctx->pL + VB_LOSS_SLOTS * VB_LOSS_STRIDE) * sizeof(long long);
-    EHR_HIP(hipMemcpy(meta4, (char*)ctx->vb_acc.ptr + off, 4 * sizeof(int), hipMemcpyDeviceToHost));
+    EHR_HIP(hipMemcpy(meta4, vb_acc_meta((long long*)ctx->vb_acc.ptr, ctx->pB, ctx->pL), 4 * sizeof(int), hipMemcpyDeviceToHost));
     return EHR_OK;
 }
 
-int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
-                    const int32_t* vert_link, const int32_t* opp, float* mvp, const float* ref, int B, int L, int V,
+int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const int32_t* opp, float* mvp, const float* ref, int B, int L, int V,
                     int T, int H, int W, float* mask, float* loss, float* grad_mvp, const StepHead* head,
                     const StepTail* tail, hipStream_t stream) {
-    (void)tri_link;
     if (tris != ctx->vb_plan_tris || opp != ctx->vb_plan_opp || verts != ctx->vb_plan_verts)
         return fail(EHR_ERR_INVALID, "fused op: the scene arrays differ from the planned ones; call ehr_fused_plan again");
     BinGeom g = make_geom(H, W, L);
     long long* const facc_all = (long long*)ctx->vb_acc.ptr;
-    const int acc_stride = 12 * L + VB_LOSS_SLOTS * VB_LOSS_STRIDE;
-    int* meta = (int*)(facc_all + (size_t)B * acc_stride);
+    const int acc_stride = vb_acc_stride(L);
+    int* meta = vb_acc_meta(facc_all, B, L);
     int* const lbox_all = (int*)ctx->vb_units.ptr;
     VbItem* spill = (VbItem*)ctx->vb_spill.ptr;
     const int NC = ctx->vb_nc, NC1 = std::max(NC, 1);
     const auto [cl, si] = vb_cluster_index(ctx->vb_clus, NC, L);
-    VbHeavy hv;
-    hv.gen = (int*)ctx->vb_heavy.ptr;
-    hv.list = hv.gen + 8;
-    hv.mlist = hv.list + 2 * VB_HEAVY_CAP;
-    hv.stamp = hv.mlist + 2 * VB_MED_CAP;
+    const int Bc = std::max(1, std::min(ctx->vb_chunk, B));
+    VbHeavy hv = vb_heavy(ctx->vb_heavy.ptr, (size_t)Bc * L * g.nt);
 
     hipEvent_t* ev = nullptr;
     if (ctx->timing) {
@@ -3009,7 +3026,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         EHR_HIP(hipEventRecord(ev[0], stream));
     }
     const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0) && (!mask || ((uintptr_t)mask & 15) == 0);
-    const int job_wgs = ((ctx->num_cus * VB_JOB_GRID) + 7) & ~7;
+    const int job_wgs = vb_xcd_round_up(ctx->num_cus * VB_JOB_GRID);
     hv.mcap = std::min(VB_MED_CAP, 2 * job_wgs);
     hv.heavy_base = VB_HEAVY_T_DEFAULT;
     hv.heavy_max = job_wgs / 2;
@@ -3017,18 +3034,10 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     const long long* const tsum_all = sparse ? (const long long*)ctx->vb_refsum.ptr : nullptr;
     const long long* const vtot_all = sparse ? tsum_all + (size_t)B * g.nt : nullptr;
     const int* const ref_flag = sparse ? (const int*)(vtot_all + B) : nullptr;
-    const int Bc = std::max(1, std::min(ctx->vb_chunk, B));
-    const size_t nslot = (size_t)ctx->vb_jcap;
-    float* jval = (float*)ctx->vb_jobs.ptr;
-    VbItem* jitems = (VbItem*)(jval + nslot * 256);
-    u64* jcov = (u64*)(jitems + nslot * VB_JOB_ITEMS);
-    int* jn = (int*)(jcov + nslot * VB_WORDS);
-    int* jspill = jn + nslot;
-    unsigned* jid = (unsigned*)(jspill + nslot);
-    int* jdesc = (int*)(jid + nslot * VB_RN);
-    int* jbase = jdesc + nslot;                                 // [Bc * L + 1] first job of every (view, link) of the chunk
-    unsigned* jutile = (unsigned*)(jbase + (size_t)Bc * L + 1);  // [Bc * L] its tile range
-    int4* slow_list = (int4*)(((uintptr_t)(jutile + (size_t)Bc * L) + 15) & ~(uintptr_t)15);  // [nslot] jobs for vb_slow_kernel
+    // stage 1a (below) is launched by the stateless render call always, by the solver step only once a step needed it
+    const bool with_slow = !tail || ctx->vb_slow_needed;
+    VbSlots sl = vb_slots(ctx->vb_jobs.ptr, (size_t)ctx->vb_jcap, (size_t)Bc * L);
+    if (!with_slow) sl.slow_list = nullptr;
     const bool lazy = ctx->vb_lazy;
     float4* const posc = lazy ? nullptr : (float4*)ctx->vb_posc.ptr;
     const int nvb = lazy ? 0 : (std::max(V, 1) + 255) / 256;  // (no per-vertex work items where clip-space vertices are computed on demand)
@@ -3042,16 +3051,12 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         float* mvp_k = mvp + (size_t)b0 * L * 16;
         const float* ref_k = ref + (size_t)b0 * H * W;
         float* mask_k = mask ? mask + (size_t)b0 * H * W : nullptr;
-        VbRecs recs;
-        recs.n = (size_t)Bk * NC1 * 64;
-        recs.trec = (int4*)ctx->vb_boxes.ptr;
-        recs.tbox = (uint2*)(recs.trec + recs.n * 2);
-        recs.cbox = recs.tbox + recs.n;
+        const VbRecs recs = vb_recs(ctx->vb_boxes.ptr, Bk, NC1);
         // stage 0: [pose forward] + vertices + screen boxes
         const VbVertexGrid vg = vb_vertex_grid(ctx->num_cus, nitems, Bk);
         const dim3 vgrid(vg.gx * Bk);
         const int nacc_ints = 2 * Bk * acc_stride;
-        const int role = first_chunk ? 1 : 2;
+        const int role = first_chunk ? VB_ROLE_FIRST_CHUNK : VB_ROLE_LATER_CHUNK;
         if (head) {
             StepHead hk = *head;
             hk.link_poses = head->link_poses + (size_t)b0 * L * 16;
@@ -3065,49 +3070,19 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         EHR_LAUNCH_CHECK();
         if (time_it) EHR_HIP(hipEventRecord(ev[1], stream));
         // stage 1: jobs = (view, link, tile) -> coverage and the triangle ids the silhouette analysis will ask for
-        // stage 1a (below) is launched by the stateless render call always, by the solver step only once a step needed it
-        const bool with_slow = !tail || ctx->vb_slow_needed;
         VbResolveArgs rq;  // the resolve stage runs inside the job kernel, on the wave that drew the job
-        rq.verts = verts;
-        rq.mvp = mvp_k;
-        rq.posc = posc;
-        rq.L = L;
+        rq.verts = verts; rq.mvp = mvp_k; rq.posc = posc; rq.V = V; rq.L = L; rq.W = W; rq.H = H;
         rq.tri4 = (const int4*)ctx->vb_idx.ptr;
         rq.opp4 = (const int4*)ctx->vb_idx.ptr + T;
-        rq.jn = jn;
-        rq.jval = jval;
-        rq.jitems = jitems;
-        rq.jspill = jspill;
-        rq.spill = spill;
-        rq.meta = meta;
-        rq.V = V;
         rq.T = T;
-        rq.W = W;
-        rq.H = H;
+        rq.sl = sl;
+        rq.spill = spill;
         rq.spill_cap = ctx->vb_spill_cap;
+        rq.meta = meta;
         rq.want_grad = grad_mvp ? 1 : 0;
         VbJobParams jp;
-        jp.g = g;
-        jp.B = Bk;
-        jp.cl = cl;
-        jp.rc = recs;
-        jp.lbox = lbox;
-        jp.jn = jn;
-        jp.jid = jid;
-        jp.jdesc = jdesc;
-        jp.jbase = jbase;
-        jp.jutile = jutile;
-        jp.jcap = ctx->vb_jcap;
-        jp.meta = meta;
+        jp.g = g; jp.B = Bk; jp.cl = cl; jp.si = si; jp.rc = recs; jp.lbox = lbox; jp.hv = hv;
         jp.use_hint = Bc == B;  // (the heavy-job hint names jobs by their dense id inside a chunk: off with more than one)
-        jp.hv = hv;
-        jp.verts = verts;
-        jp.mvp = mvp_k;
-        jp.posc = posc;
-        jp.V = V;
-        jp.si = si;
-        jp.jcov = jcov;
-        jp.slow_list = with_slow ? slow_list : nullptr;
         jp.heavy_t = VB_HEAVY_T_DEFAULT;
         jp.med_t0 = VB_MED_T_DEFAULT;
         jp.rq = rq;
@@ -3118,16 +3093,15 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         EHR_LAUNCH_CHECK();
         // stage 1a: jobs with a triangle that crosses the near plane or spans > 512 pixels (normally none: the kernel returns at once)
         if (with_slow) {
-            vb_slow_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(g, cl, recs, verts, mvp_k, posc, V, si, jid, jcov, jdesc, jn, slow_list, meta);
+            const VbJobArgs ja = {verts, mvp_k, recs, cl.NC, V, W, H, L, sl, si.cvidx, posc, cl.coff};
+            vb_slow_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(meta, ja);
             EHR_LAUNCH_CHECK();
         }
         if (time_it) EHR_HIP(hipEventRecord(ev[2], stream));
         // stage 1b: drawn jobs -> per-link values and blended pairs.  The job kernel has done that for the jobs it drew itself;
         // only the jobs vb_slow_kernel redrew are left (none, normally: a launch of 32 workgroups that read a counter)
         if (with_slow) {
-            vb_resolve_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(g, Bk, verts, mvp_k, posc, V, T, rq.tri4, rq.opp4, jid, jcov, jdesc, jn, jval,
-                                                                          jitems, jspill, ctx->vb_jcap, rq.want_grad, spill,
-                                                                          ctx->vb_spill_cap, meta, slow_list);
+            vb_resolve_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(rq);
             EHR_LAUNCH_CHECK();
         }
         if (time_it) {
@@ -3138,17 +3112,18 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         // the link boxes).  With a bound reference mask and no mask output only tiles that hold a job are visited.
         int nwg = ctx->num_cus * VB_COMPOSITE_GRID;
         if (!sparse) nwg = std::min(nwg, (Bk * g.nt + 3) / 4);
-        nwg = std::max(8, (nwg + 7) & ~7);  // a multiple of 8: the XCD split and the two-level arrival ticket rely on it
-        const long long* tsum = sparse ? tsum_all + (size_t)b0 * g.nt : nullptr;
-        const long long* vtot = sparse ? vtot_all + b0 : nullptr;
+        nwg = std::max(VB_XCDS, vb_xcd_round_up(nwg));  // a multiple of VB_XCDS: the XCD split and the two-level arrival ticket rely on it
         const size_t dyn = (2 * (size_t)Bk * L + 1) * sizeof(int);  // link tables in LDS
         const bool fill = sparse && mask_k != nullptr;  // (FILL: the zero fill of the tiles no job owns, a variant of its own
                                                           //  so that the form without a mask output keeps its registers)
-#define VB_COMPOSITE(TAILV, FILLV, tailarg)                                                                                  \
-    vb_composite_kernel<TAILV, FILLV><<<nwg, 256, dyn, stream>>>(                                                            \
-        g, Bk, mvp_k, V, verts, lbox, jn, jval, jitems, jspill, jbase, jutile, ctx->vb_jcap, ref_k, mask_k, facc,            \
-        VB_LOSS_SLOTS, grad_mvp ? 1 : 0, vec_ok, spill, ctx->vb_spill_cap, meta, tsum, vtot, ref_flag, loss, grad_mvp,       \
-        tailarg, last_chunk ? 1 : 0, B, facc_all, vtot_all, lbox_all)
+        VbCompArgs ca;
+        ca.g = g; ca.B = Bk; ca.mvp = mvp_k; ca.V = V; ca.verts = verts; ca.sl = sl; ca.ref = ref_k; ca.mask = mask_k; ca.facc = facc;
+        ca.nls = VB_LOSS_SLOTS; ca.want_grad = rq.want_grad; ca.vec_ok = vec_ok; ca.spill = spill; ca.spill_cap = ctx->vb_spill_cap;
+        ca.meta = meta;
+        ca.tsum = sparse ? tsum_all + (size_t)b0 * g.nt : nullptr;
+        ca.ref_flag = ref_flag; ca.loss = loss; ca.grad_mvp = grad_mvp;
+        ca.do_finish = last_chunk ? 1 : 0; ca.B_all = B; ca.facc_all = facc_all; ca.vtot_all = vtot_all; ca.lbox_all = lbox_all;
+#define VB_COMPOSITE(TAILV, FILLV, tailarg) vb_composite_kernel<TAILV, FILLV><<<nwg, 256, dyn, stream>>>(ca, tailarg)
         StepTail none = {};
         if (tail) {
             if (fill) VB_COMPOSITE(true, true, *tail); else VB_COMPOSITE(true, false, *tail);
@@ -3164,9 +3139,33 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     return EHR_OK;
 }
 
+// The scoring chain's small scratch (ehr_ctx::sc_misc), for a chunk of Qc candidates x S poses = Bc views
+struct VbScoreMisc {
+    int* lbox;                  // [Bc][L][VB_LBOX_STRIDE] link boxes
+    int* meta;                  // a meta block (VB_META_BYTES)
+    VbHeavy hv;                 // the heavy-job hint's counters and lists (no stamps: the hint is off)
+    int* sticky;                // [16] [0]: a triangle needs the exact z-buffer
+    size_t zero_bytes;          // hv .. sticky, cleared at the start of a call
+    unsigned long long* sacc;   // [2][Qc][16] per-candidate sums, double buffered
+    u64* tcov;                  // [Bc][nt][4] coverage words of the (view, tile)s
+};
+static VbScoreMisc vb_score_misc(void* base, size_t Qc, size_t Bc, int L, int nt, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbScoreMisc m;
+    m.lbox = c.take<int>((size_t)VB_LBOX_STRIDE * Bc * L);
+    m.meta = (int*)c.take<char>(VB_META_BYTES, alignof(int));
+    size_t hv_bytes;
+    m.hv = vb_heavy((void*)c.at, 0, &hv_bytes);
+    c.at += hv_bytes;
+    m.hv.stamp = m.hv.gen;  // (never touched)
+    m.sticky = c.take<int>(16);
+    m.zero_bytes = c.at - (uintptr_t)m.hv.gen;
+    m.sacc = c.take<unsigned long long>(2 * 16 * Qc, 128);
+    m.tcov = c.take<u64>(Bc * nt * 4);
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return m;
+}
 
-// Binds a reference mask to the plan (ehr_fused_bind_ref): one pass stores per (view, tile) the fixed-point sum(ref^2)
-// exactly as the composite kernel would add it for a tile no link touches, and per view the total.  ref == NULL unbinds.
 // The scoring op (ehr_mask_variance, csrc/ehr_score.hip) on the solver's machinery: the static cluster index of the packed
 // mesh, then per chunk of candidates the vertex kernel (records + link boxes; depth class "coverage decides": every
 // coverable pixel of the triangle has z/w in (0, 1]), the job kernel in its coverage-only form (no deferred units, no
@@ -3220,39 +3219,27 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     const int NC = ctx->sc_nc;
     const auto [cl, si] = vb_cluster_index(ctx->sc_clus, NC, L);
     // candidates per chunk: (view, link) units of a chunk fit the job kernel's LDS tables; scratch bounded like the solver's
-    const double view_bytes = (double)NC * (64 * 40 + 8) + (double)V * 16 + (double)g.nt * 32;
+    const double view_bytes = (double)NC * VB_CLUSTER_REC_BYTES + (double)V * sizeof(float4) + (double)g.nt * 4 * sizeof(u64);
     int Qc = std::max(1, (VB_MAX_UNITS / L) / S);
     Qc = std::max(1, std::min(Qc, (int)(8192.0 * 1048576.0 / (view_bytes * S))));
     Qc = std::min(Qc, Q);
     const int Bc = Qc * S;
-    const size_t n_hv = 8 + 2 * (size_t)VB_HEAVY_CAP + 2 * (size_t)VB_MED_CAP;
-    const size_t misc_ints = (size_t)VB_LBOX_STRIDE * Bc * L + EHR_META_INTS + (VB_LINES + 2) * 32 + n_hv + 16 + 64 + 2 * 32 * (size_t)Qc;
+    size_t bytes;
     if ((rc = ctx->sc_posc.reserve((size_t)Bc * V * sizeof(float4)))) return rc;
-    if ((rc = ctx->sc_entries.reserve((size_t)Bc * NC * (64 * 40 + 8)))) return rc;
-    if ((rc = ctx->sc_misc.reserve(misc_ints * sizeof(int) + 64 + (size_t)Bc * g.nt * 4 * sizeof(u64)))) return rc;
+    vb_recs(nullptr, Bc, NC, &bytes);
+    if ((rc = ctx->sc_entries.reserve(bytes))) return rc;
+    vb_score_misc(nullptr, Qc, Bc, L, g.nt, &bytes);
+    if ((rc = ctx->sc_misc.reserve(bytes))) return rc;
     ctx->sc_entries_cap = 0;  // (the per-triangle path sizes its queues again if it runs after this)
-    int* lbox = (int*)ctx->sc_misc.ptr;
-    int* meta = lbox + (size_t)VB_LBOX_STRIDE * Bc * L;
-    int* hvp = meta + EHR_META_INTS + (VB_LINES + 2) * 32;
-    int* sticky = hvp + n_hv;
-    unsigned long long* sacc0 = (unsigned long long*)(((uintptr_t)(sticky + 16) + 127) & ~(uintptr_t)127);  // [2][Qc][16]
-    u64* tcov = (u64*)(sacc0 + 2 * 16 * (size_t)Qc);
+    const auto [lbox, meta, hv, sticky, zero_bytes, sacc0, tcov] = vb_score_misc(ctx->sc_misc.ptr, Qc, Bc, L, g.nt);
     float4* posc = (float4*)ctx->sc_posc.ptr;
-    VbHeavy hv;
-    hv.gen = hvp;
-    hv.list = hv.gen + 8;
-    hv.mlist = hv.list + 2 * VB_HEAVY_CAP;
-    hv.stamp = hv.gen;  // (never touched: the hint is off)
-    hv.mcap = 0;
-    hv.heavy_base = 0;
-    hv.heavy_max = 0;
-    EHR_HIP(hipMemsetAsync(hvp, 0, (n_hv + 16) * sizeof(int), stream));
+    EHR_HIP(hipMemsetAsync(hv.gen, 0, zero_bytes, stream));
     EHR_HIP(hipMemsetAsync(sacc0, 0, 2 * 16 * (size_t)Qc * sizeof(unsigned long long), stream));
     EHR_HIP(hipMemsetAsync(score, 0, (size_t)Q * sizeof(long long), stream));
     if (count) EHR_HIP(hipMemsetAsync(count, 0, (size_t)Q * H * W, stream));
     const int nvb = (std::max(V, 1) + 255) / 256;
     const int nitems = nvb + (NC + 3) / 4;
-    const int job_wgs = ((ctx->num_cus * VB_JOB_GRID) + 7) & ~7;
+    const int job_wgs = vb_xcd_round_up(ctx->num_cus * VB_JOB_GRID);
     // link boxes start empty (afterwards the count kernel re-arms them)
     vb_score_count_kernel<<<64, 256, 0, stream>>>(g, 0, S, tcov, sacc0, nullptr, lbox, VB_LBOX_STRIDE * Bc * L, sacc0, score, 0);
     EHR_LAUNCH_CHECK();
@@ -3261,34 +3248,20 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     int prev_nq = 0, flip = 0;
     for (int q0 = 0; q0 < Q; q0 += Qc) {
         const int nq = std::min(Qc, Q - q0), Bk = nq * S;
-        VbRecs recs;
-        recs.n = (size_t)Bk * NC * 64;
-        recs.trec = (int4*)ctx->sc_entries.ptr;
-        recs.tbox = (uint2*)(recs.trec + recs.n * 2);
-        recs.cbox = recs.tbox + recs.n;
+        const VbRecs recs = vb_recs(ctx->sc_entries.ptr, Bk, NC);
         const VbVertexGrid vg = vb_vertex_grid(ctx->num_cus, nitems, Bk);
         StepHead none = {};
         vb_vertex_kernel<false><<<dim3(vg.gx * Bk), 256, 0, stream>>>(verts, vert_link, tris, cl, none, const_cast<float*>(mvp) + (size_t)q0 * S * L * 16,
                                                                    V, nvb, g, posc, recs, lbox, (int*)tcov, Bk * g.nt * 8, meta, Bk, vg.gx,
-                                                                   vg.xcd_views, hv, 1 | 4);
+                                                                   vg.xcd_views, hv, VB_ROLE_FIRST_CHUNK | VB_ROLE_POS_ONLY);
         EHR_LAUNCH_CHECK();
         VbJobParams jp = {};
-        jp.g = g;
-        jp.B = Bk;
-        jp.cl = cl;
-        jp.rc = recs;
-        jp.lbox = lbox;
-        jp.jn = sticky;
-        jp.jcap = S;
-        jp.meta = meta;
-        jp.use_hint = 0;
-        jp.hv = hv;
-        jp.verts = verts;
-        jp.mvp = mvp + (size_t)q0 * S * L * 16;
-        jp.posc = posc;
-        jp.V = V;
-        jp.si = si;
-        jp.jcov = tcov;
+        jp.g = g; jp.B = Bk; jp.cl = cl; jp.si = si; jp.rc = recs; jp.lbox = lbox; jp.hv = hv;  // (use_hint = 0)
+        jp.rq.verts = verts; jp.rq.posc = posc; jp.rq.V = V; jp.rq.meta = meta;
+        jp.rq.mvp = mvp + (size_t)q0 * S * L * 16;
+        jp.rq.sl.jn = sticky;  // (the coverage-only form of the slots: see vb_job_kernel)
+        jp.rq.sl.jcov = tcov;
+        jp.rq.sl.jcap = S;
         jp.heavy_t = 0x7fffffff;
         jp.med_t0 = 0x7fffffff;
         vb_job_kernel<true><<<job_wgs, 256, 0, stream>>>(jp);
@@ -3313,6 +3286,8 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     return EHR_OK;
 }
 
+// Binds a reference mask to the plan (ehr_fused_bind_ref): one pass stores per (view, tile) the fixed-point sum(ref^2)
+// exactly as the composite kernel would add it for a tile no link touches, and per view the total.  ref == NULL unbinds.
 int ehr::vbuf_bind_ref(ehr_ctx* ctx, const float* ref, hipStream_t stream) {
     ctx->vb_ref = nullptr;
     if (!ref) return EHR_OK;
