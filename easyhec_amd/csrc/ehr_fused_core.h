@@ -1,6 +1,6 @@
 // ehr_fused_core.h -- pieces of the fused op's launch chain (ehr_vbuf.hip) that are not rasterization: fixed-point
 // accumulators, the head / tail descriptors of a solver step and the finish stage (accumulators -> loss / grad_mvp ->
-// pose backward -> Adam), which runs inside the composite kernel's last-arriving workgroup.
+// pose backward -> Adam), which runs inside the composite kernel's finisher workgroup.
 #pragma once
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
@@ -34,7 +34,7 @@ __device__ __forceinline__ void fix_add_delta(long long* acc, float v, long long
     if (d != 0) atomicAdd((unsigned long long*)acc, (unsigned long long)d);
 }
 __device__ __forceinline__ float fix_get(long long q) { return (float)((double)q * (1.0 / EHR_FIX_SCALE)); }
-// accumulators are read inside the launch that adds to them (finish stage in the last-arriving workgroup): agent-scope
+// accumulators are read inside the launch that adds to them (finish stage, once every arrival is counted): agent-scope
 // loads, which are served by the memory side the atomics were performed on, never by this CU's L1
 __device__ __forceinline__ long long acc_load(const long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -63,21 +63,43 @@ struct StepTail {  // what the solver-step form needs (all device pointers)
     int defer_adam;
 };
 
-// facc: see vb_acc_stride (lstride = VB_LOSS_STRIDE).  vtot (optional): per view a constant that belongs to the frame loss (the bound reference mask's
-// cached part).  Called by all 256 threads of one workgroup after every other workgroup's atomics were performed.
+// The finish stage comes in two halves, both called by all 256 threads of ONE workgroup (the composite stage's finisher).
+// finish_prefetch requests and prepares everything that does not depend on the accumulators or the overflow word: Adam's
+// state and bias corrections, the Jacobian rows and the first 64 link poses (to LDS), PF and the first views' cached
+// constants.  The finisher runs it while the other workgroups are still compositing.  finish_reduce runs once every other
+// workgroup's atomics have been performed: it reads the accumulators, contracts, reduces and applies Adam.  Together
+// they evaluate the expressions of the former single body in the same order: the split moves loads, not roundings.
+struct FinishPre {
+    AdamState st;
+    PoseBwdPre pb;
+    long long vt;  // nls == 32: vtot of the first view this thread publishes (view threadIdx.x / 32)
+};
+
+// vtot (optional): per view a constant that belongs to the frame loss (the bound reference mask's cached part).
 template <bool TAIL>
-__device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long long* __restrict__ facc,
-                                            const long long* __restrict__ vtot, float* __restrict__ loss,
-                                            float* __restrict__ grad_mvp, int* __restrict__ meta, const StepTail& tail,
-                                            int nls, int* __restrict__ lbox, int lstride, float* vloss /* LDS [256] */,
-                                            double (*S)[17] /* LDS [4][17] */, float* red_lds /* LDS [8] */,
-                                            float (*Js)[16] /* LDS [6][16] */) {
+__device__ __forceinline__ void finish_prefetch(FinishPre& pre, const BinGeom& g, int B, const long long* __restrict__ vtot,
+                                                const StepTail& tail, int nls, float (*Js)[16] /* LDS [6][16] */,
+                                                float* lp_lds /* LDS [1024] */) {
+    const int tid = threadIdx.x;
+    if (TAIL && !tail.defer_adam) pre.st = pose_adam_fetch(tail.dof, tail.m, tail.v, tail.step);
+    pre.vt = (nls == 32 && vtot && (tid & 31) == 0 && (tid >> 5) < B) ? vtot[tid >> 5] : 0ll;
+    if (TAIL) {
+        pose_backward_prefetch(pre.pb, tail.K, tail.link_poses, tail.tc_jac, B, g.L, g.H, g.W, tail.n, tail.f, Js, lp_lds);
+        // (Adam's bias corrections need the step count only)
+        if (!tail.defer_adam) pose_adam_bias(pre.st, tail.lr, tail.b1, tail.b2);
+    }
+}
+
+// facc: see vb_acc_stride (lstride = VB_LOSS_STRIDE).
+template <bool TAIL>
+__device__ __forceinline__ void finish_reduce(const FinishPre& pre, const BinGeom& g, int B, const long long* __restrict__ facc,
+                                              const long long* __restrict__ vtot, float* __restrict__ loss,
+                                              float* __restrict__ grad_mvp, int* __restrict__ meta, const StepTail& tail,
+                                              int nls, int lstride, double (*S)[17] /* LDS [4][17] */,
+                                              float* red_lds /* LDS [8] */, float (*Js)[16] /* LDS [6][16] */,
+                                              const float* lp_lds /* LDS [1024] */) {
     const int tid = threadIdx.x, L = g.L;
     const int acc_stride = vb_acc_stride(L, nls);
-    if (lbox)  // the links' screen boxes start "empty" in the next step
-        for (int i = tid; i < 16 * B * L; i += 256) lbox[i] = (i & 2) ? INT_MIN : INT_MAX;  // 16 ints (one line) per box
-    AdamState st;
-    if (TAIL && !tail.defer_adam) st = pose_adam_fetch(tail.dof, tail.m, tail.v, tail.step);
     auto view_loss_slow = [&](int b) {
         long long s = vtot ? vtot[b] : 0ll;
         for (int k = 0; k < nls; k++) s += acc_load(&facc[(size_t)b * acc_stride + 12 * L + k * lstride]);
@@ -85,8 +107,8 @@ __device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long 
     };
     // Frame losses.  nls == 32: one slot per lane, half a wave per view -- a single round trip instead of 32 dependent
     // adds -- and the lane that ends up with a view's sum stores loss[b] and keeps it as ITS share of sum_b loss_b: no
-    // hand-over through LDS, no barrier, so the reads below (gradient accumulators, link poses, Jacobian) travel with
-    // these instead of after them.
+    // hand-over through LDS, no barrier, so the reads below (gradient accumulators) travel with these instead of after
+    // them.
     const bool bad = __hip_atomic_load(&meta[EHR_META_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
     const float nanv = __int_as_float(0x7fc00000);  // overflow => NaN, never a silently wrong loss
     double la_mine = 0.0;
@@ -99,8 +121,6 @@ __device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long 
                 const int b = base + 8 * j + (tid >> 5);
                 s4[j] = (b < B) ? acc_load(&facc[(size_t)b * acc_stride + 12 * L + k * lstride]) : 0;
             }
-            // (Adam's bias corrections while the slots are on their way: they need the step count only)
-            if (TAIL && base == 0 && !tail.defer_adam) pose_adam_bias(st, tail.lr, tail.b1, tail.b2);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int b = base + 8 * j + (tid >> 5);
@@ -112,7 +132,7 @@ __device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long 
                 s += wave_xor<2>(s);
                 s += wave_xor<1>(s);
                 if (k == 0 && b < B) {
-                    const float lv = bad ? nanv : fix_get(s + (vtot ? vtot[b] : 0ll));
+                    const float lv = bad ? nanv : fix_get(s + (vtot ? (base + j == 0 ? pre.vt : vtot[b]) : 0ll));
                     loss[b] = lv;
                     la_mine += (double)lv;
                 }
@@ -150,20 +170,18 @@ __device__ __forceinline__ void finish_body(const BinGeom& g, int B, const long 
             }
         return;
     }
-    // One dependent round trip in total: the optimiser state and the Jacobian are requested up front, the gradients
-    // come straight from the accumulators, and Adam reads the 8 reduced floats back from LDS.
-    pose_backward_block_t(
+    // The gradients come straight from the accumulators, and Adam reads the 8 reduced floats back from LDS.
+    pose_backward_reduce_t(
         [&](int i, float* G) {
             grad16(i, G);
             if (grad_mvp)
 #pragma unroll
                 for (int e = 0; e < 16; e++) grad_mvp[(size_t)i * 16 + e] = G[e];
         },
-        [&](int) { return 0.f; }, tail.K, tail.link_poses, tail.tc_jac, B, L, g.H, g.W, tail.n, tail.f, tail.red, S, red_lds,
-        &la_mine, nls == 32, Js);
+        [&](int) { return 0.f; }, pre.pb, tail.link_poses, B, L, tail.red, S, red_lds, &la_mine, nls == 32, Js, lp_lds);
     __syncthreads();
     if (!tail.defer_adam)
-        pose_adam_apply(st, tail.dof, tail.m, tail.v, tail.step, red_lds, tail.lr, tail.b1, tail.b2, tail.eps, tail.wd,
+        pose_adam_apply(pre.st, tail.dof, tail.m, tail.v, tail.step, red_lds, tail.lr, tail.b1, tail.b2, tail.eps, tail.wd,
                         tail.loss_out, tail.grad_out);
 }
 

@@ -185,42 +185,61 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     v += wave_xor<1>(v);
     return v;
 }
-template <class GetG, class GetLoss>
-__device__ __forceinline__ void pose_backward_block_t(GetG get_g, GetLoss get_loss, const float* __restrict__ K,
-                                                      const float* __restrict__ link_poses,
-                                                      const float* __restrict__ tc_jac, int B, int L, int H, int W,
-                                                      float n, float f, float* __restrict__ red, double (*S)[17],
-                                                      float* red_lds, const double* la_pre,
-                                                      bool la_lanes_0_32, float (*Js_lds)[16]) {
-    // (la_pre: this thread's share of sum_b loss_b, already known to the caller -- get_loss is not called then;
-    //  la_lanes_0_32: only lanes 0 and 32 of a wave hold a share, the wave's sum is one shuffle instead of six)
+// The part of pose_backward_block_t that depends on nothing the caller sums: the Jacobian rows (to LDS), PF = proj @
+// opencv2blender and (lp_lds, optional: LDS float[1024]) the link poses of the first 64 (view, link) pairs, the ones the
+// threads' first round contracts with.  A caller that has to wait for its sums anyway (the fused step's finisher)
+// requests these before it waits; pose_backward_reduce_t then contracts with them.
+struct PoseBwdPre {
+    float Pc[4];  // column threadIdx.x & 3 of PF
+};
+__device__ __forceinline__ void pose_backward_prefetch(PoseBwdPre& pre, const float* __restrict__ K,
+                                                       const float* __restrict__ link_poses,
+                                                       const float* __restrict__ tc_jac, int B, int L, int H, int W,
+                                                       float n, float f, float (*Js_lds)[16], float* lp_lds) {
     // Jacobian rows are needed last but depend on nothing computed here: fetch them first (into LDS, not registers:
     // this body also runs inside the composite kernel, which is compiled for 80 registers)
-    // (Js_lds: 6 x 16 floats of the caller's LDS -- the merged job kernel has none to spare, it lends a job's work area)
-    float (*const Js)[16] = Js_lds;
-    if (threadIdx.x < 96) Js[threadIdx.x >> 4][threadIdx.x & 15] = tc_jac[16 + threadIdx.x];
+    // (Js_lds: 6 x 16 floats of the caller's LDS)
+    if (threadIdx.x < 96) Js_lds[threadIdx.x >> 4][threadIdx.x & 15] = tc_jac[16 + threadIdx.x];
     float P[16];
     projection(K, H, W, n, f, P);
     for (int r = 0; r < 4; r++) {  // PF = proj @ opencv2blender
         P[4 * r + 1] = -P[4 * r + 1];
         P[4 * r + 2] = -P[4 * r + 2];
     }
+    for (int k = 0; k < 4; k++) pre.Pc[k] = P[4 * k + (threadIdx.x & 3)];
+    if (lp_lds && (int)threadIdx.x < 4 * min(B * L, 64))  // (16 floats a pair: 16-byte aligned whenever link_poses is)
+        reinterpret_cast<float4*>(lp_lds)[threadIdx.x] = reinterpret_cast<const float4*>(link_poses)[threadIdx.x];
+}
+template <class GetG, class GetLoss>
+__device__ __forceinline__ void pose_backward_reduce_t(GetG get_g, GetLoss get_loss, const PoseBwdPre& pre,
+                                                       const float* __restrict__ link_poses, int B, int L,
+                                                       float* __restrict__ red, double (*S)[17], float* red_lds,
+                                                       const double* la_pre, bool la_lanes_0_32, float (*Js_lds)[16],
+                                                       const float* lp_lds) {
+    // (la_pre: this thread's share of sum_b loss_b, already known to the caller -- get_loss is not called then;
+    //  la_lanes_0_32: only lanes 0 and 32 of a wave hold a share, the wave's sum is one shuffle instead of six)
+    float (*const Js)[16] = Js_lds;
     // work item = (view-link pair, row r of d/dTc <G, PF @ Tc @ lp> = PF^T @ G @ lp^T): four threads per pair
-    const int r = threadIdx.x & 3;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     double la = 0.0;
     for (int i = threadIdx.x >> 2; i < B * L; i += blockDim.x >> 2) {
         // (the link pose is requested BEFORE the gradients: get_g may read them with atomic loads, behind which the
-        //  compiler does not move an ordinary load -- a round trip of its own otherwise)
+        //  compiler does not move an ordinary load -- a round trip of its own otherwise; the first 64 pairs' may be in LDS,
+        //  written before a barrier of the caller's)
         float lp[16];
+        if (lp_lds && i < 64) {
 #pragma unroll
-        for (int k = 0; k < 16; k++) lp[k] = link_poses[(size_t)i * 16 + k];
+            for (int k = 0; k < 16; k++) lp[k] = lp_lds[i * 16 + k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; k++) lp[k] = link_poses[(size_t)i * 16 + k];
+        }
         float G[16];
         get_g(i, G);
         float M[4];
         for (int c = 0; c < 4; c++) {
             float s = 0.f;
-            for (int k = 0; k < 4; k++) s = fmaf(P[4 * k + r], G[4 * k + c], s);
+            for (int k = 0; k < 4; k++) s = fmaf(pre.Pc[k], G[4 * k + c], s);
             M[c] = s;
         }
         for (int c = 0; c < 4; c++) {
@@ -265,6 +284,17 @@ __device__ __forceinline__ void pose_backward_block_t(GetG get_g, GetLoss get_lo
         red[threadIdx.x] = rr;
         if (red_lds) red_lds[threadIdx.x] = rr;
     }
+}
+template <class GetG, class GetLoss>
+__device__ __forceinline__ void pose_backward_block_t(GetG get_g, GetLoss get_loss, const float* __restrict__ K,
+                                                      const float* __restrict__ link_poses,
+                                                      const float* __restrict__ tc_jac, int B, int L, int H, int W,
+                                                      float n, float f, float* __restrict__ red, double (*S)[17],
+                                                      float* red_lds, const double* la_pre,
+                                                      bool la_lanes_0_32, float (*Js_lds)[16]) {
+    PoseBwdPre pre;
+    pose_backward_prefetch(pre, K, link_poses, tc_jac, B, L, H, W, n, f, Js_lds, nullptr);
+    pose_backward_reduce_t(get_g, get_loss, pre, link_poses, B, L, red, S, red_lds, la_pre, la_lanes_0_32, Js_lds, nullptr);
 }
 
 __device__ __forceinline__ void pose_backward_block(const float* __restrict__ grad_mvp, const float* __restrict__ loss,

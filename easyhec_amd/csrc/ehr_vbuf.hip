@@ -31,7 +31,7 @@
 //                       job, only for the jobs vb_slow_kernel redrew.
 //   vb_composite_kernel one wave per tile that holds a job (every tile without a bound reference mask): sums the links'
 //                       values in link order, clamps, frame loss, mask write, back-propagates the tile's blended pairs
-//                       to 12 numbers per link in the view's fixed-point accumulators; its last-arriving workgroup runs
+//                       to 12 numbers per link in the view's fixed-point accumulators; its finisher workgroup runs
 //                       the finish stage (accumulators -> loss / grad_mvp [-> pose backward -> Adam]).  (Run at the end of
 //                       the job kernel's launch instead, behind a grid-wide barrier, it was no faster: DESIGN.md section 6,
 //                       profiles/experiments/r06_merged_job_composite.patch.)
@@ -93,9 +93,8 @@ __host__ __device__ constexpr int vb_xcd_round_up(int n) { return (n + VB_XCDS -
 // one line serialise memory-side at ~12 ns each).
 enum VbLine {
     VB_LINE_JOB_CURSOR = 0,                               // + xcd: job cursor of that XCD
-    VB_LINE_COMP_TICKET = VB_LINE_JOB_CURSOR + VB_XCDS,   // + xcd: composite arrival ticket of that XCD
-    VB_LINE_TOP_TICKET = VB_LINE_COMP_TICKET + VB_XCDS,   // the ticket over the XCDs
-    VB_LINE_SLOW_COUNT,                                   // jobs put aside for vb_slow_kernel
+    VB_LINE_COMP_ARRIVE = VB_LINE_JOB_CURSOR + VB_XCDS,   // + xcd: composite workgroups of that XCD that have arrived
+    VB_LINE_SLOW_COUNT = VB_LINE_COMP_ARRIVE + VB_XCDS,   // jobs put aside for vb_slow_kernel
     VB_LINES
 };
 __host__ __device__ __forceinline__ int* vb_line(int* meta, int k) {
@@ -518,9 +517,9 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
             for (int i = tid; i < n2; i += 256) hv.stamp[min(vb_hint_dense(hv.mlist[cur * VB_MED_CAP + i], g.nt, g.ntx), B * L * g.nt - 1)] = -gen;
         }
         if (tid < 8) meta[tid] = 0;                          // overflow flag, spill cursor
-        if (tid < VB_LINES) *vb_line(meta, tid) = 0;         // job cursors of the XCDs, tickets, slow-job count
+        if (tid < VB_LINES) *vb_line(meta, tid) = 0;         // job cursors of the XCDs, arrival counters, slow-job count
     }
-    if (rearm) {  // a later chunk of the same step: cursors and tickets again, the overflow flag stays
+    if (rearm) {  // a later chunk of the same step: cursors and arrival counters again, the overflow flag stays
         if (tid < 8 && tid != EHR_META_OVERFLOW) meta[tid] = 0;
         if (tid < VB_LINES) *vb_line(meta, tid) = 0;
     }
@@ -1819,7 +1818,7 @@ __device__ __forceinline__ void vb_zero_tile_row(float* __restrict__ mask, size_
 struct VbCompArgs {
     const long long* tsum;
     int nls, want_grad, vec_ok;
-    float* loss;         // (loss .. lbox_all, ref_flag: for the finish stage, run by the last-arriving workgroup of the call's
+    float* loss;         // (loss .. lbox_all, ref_flag: for the finish stage, run by the finisher workgroup of the call's
     int B;               //  last chunk of views -- do_finish -- over ALL views of the call)
     long long* facc;     // the chunk's accumulators
     VbSlots sl;          // (read only here)
@@ -2056,7 +2055,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     // ---- bound reference AND a mask output: the tiles that hold a job were written by their owners above; every other
     //      tile of the images is zero.  The waves share them out (most have no item, or one): a wave tests a tile against
     //      the links' tile ranges -- the predicate that decides whether the tile HAS an owner -- and stores 1 KB of zeros if
-    //      it has none.  Stores only: nothing here is waited for before the ticket's vmcnt.
+    //      it has none.  Stores only: nothing here is waited for before the arrival's vmcnt.
     if (FILL) {
         const int total = B * g.nt;
         for (int t = (int)blockIdx.x * 4 + wave; t < total; t += nwg * 4) {
@@ -2577,6 +2576,34 @@ vb_refsum_kernel(BinGeom g, int B, const float* __restrict__ ref, int vec_ok, lo
     }
 }
 
+// The composite kernel's kernarg segment as its finish section reads it (see there and vb_job_params)
+struct VbCompParams {
+    VbCompArgs C;
+    StepTail tail;
+};
+typedef const VbCompParams __attribute__((address_space(4)))* VbCompParamsPtr;
+__device__ __forceinline__ VbCompParamsPtr vb_comp_params() {
+    VbCompParamsPtr p = (VbCompParamsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
+// How many of XCD `xcd`'s `per` composite workgroups (block xcd + VB_XCDS k, k < per) have work in the call's last launch:
+// an item of the XCD's contiguous run (wave slot 4 k + wave), a tile of the zero fill (nfill tiles, four per workgroup in
+// block order) or link boxes to re-arm (nlbox ints, 256 per workgroup).  Each is a prefix in k, so their union is the
+// longest one.  A function of the launch's tables only: every workgroup, and the finisher for every XCD, gets the same
+// number.
+constexpr int VB_FINISH_POLLS = 1 << 21;  // bound of the finisher's wait, ~0.5 us a poll
+__device__ __forceinline__ int vb_comp_arrivals(int xcd, int per, int nitems, int nfill, int nlbox) {
+    const int share = vb_xcd_share(nitems);
+    const int mine = max(0, min(share, nitems - xcd * share));  // items of this XCD
+    int n = (mine + 3) >> 2;
+    const int fwg = (nfill + 3) >> 2, lwg = (nlbox + 255) >> 8;  // workgroups (in block order) with a fill tile / boxes
+    n = max(n, fwg > xcd ? vb_xcd_share(fwg - xcd) : 0);
+    n = max(n, lwg > xcd ? vb_xcd_share(lwg - xcd) : 0);
+    return min(n, per);
+}
+
 // Stage 3: one WAVE per 32x8 tile (4 pixels per lane, float4 image accesses, no workgroup barriers): sums the links'
 // values in link order, clamps, accumulates the frame loss, writes the mask, and back-propagates the tile's blended
 // pairs to 12 numbers per link which go to the view's fixed-point accumulators.  Persistent waves over
@@ -2584,8 +2611,8 @@ vb_refsum_kernel(BinGeom g, int B, const float* __restrict__ ref, int vec_ok, lo
 //   tsum != NULL (bound reference mask): the tiles of the views' link rectangles only; a tile that no link contributes
 //                 to is skipped without reading the reference -- its cached sum is already in vtot.  With a mask output
 //                 the tiles outside every rectangle are then filled with zeros (stores only, no reference read, no sums).
-// The workgroup that finishes LAST (a ticket per XCD, then one over the XCDs) runs the finish stage: accumulators ->
-// loss / grad_mvp [-> pose backward -> Adam], re-arms the link boxes.  vec_ok: W % 4 == 0 and 16-byte aligned images.
+// One designated workgroup of the call's last launch (the finisher, see below) runs the finish stage: accumulators ->
+// loss / grad_mvp [-> pose backward -> Adam]; the launch also re-arms the link boxes.  vec_ok: W % 4 == 0 and 16-byte aligned images.
 template <bool TAIL, bool FILL>
 __global__ void __launch_bounds__(256, FILL ? 5 : 6)
 vb_composite_kernel(VbCompArgs C, StepTail tail) {
@@ -2608,32 +2635,68 @@ vb_composite_kernel(VbCompArgs C, StepTail tail) {
     __syncthreads();
     const int nwg = gridDim.x, xcd = blockIdx.x & (VB_XCDS - 1);
     vb_composite_items<FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> VB_XCD_BITS) * 4 + wave, (nwg >> VB_XCD_BITS) * 4, nwg);
-    // ---- the workgroup whose atomics are performed last runs the finish stage.  Every wave first waits until its own
-    //      atomics have been performed (vmcnt covers them), then one lane takes a ticket on the XCD's counter and the
-    //      last of an XCD one on the top counter: two levels, because a few thousand arrivals on ONE address serialise
-    //      at ~12 ns each.  The accumulators are only ever touched by agent-scope atomics and read back with agent-scope
-    //      loads (acc_load), so no cache maintenance is needed between the two.
-    if (!C.do_finish) return;  // (not the last chunk of views: the kernel boundary orders its sums before the last chunk's finish)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __shared__ int s_last;
-    if (tid == 0) {
-        int last = 0;
-        const int per = nwg >> VB_XCD_BITS;  // workgroups per XCD counter (nwg is a multiple of VB_XCDS)
-        int* const xcd_ticket = vb_line(C.meta, VB_LINE_COMP_TICKET + xcd);
-        int* const top_ticket = vb_line(C.meta, VB_LINE_TOP_TICKET);
-        if (atomicAdd(xcd_ticket, 1) == per - 1) last = atomicAdd(top_ticket, 1) == VB_XCDS - 1;
-        s_last = last;
+    // ---- the finish stage: ONE designated workgroup, the finisher, runs it once every other workgroup's atomics have
+    //      been performed.  A workgroup that had work waits for its own atomics (vmcnt covers them), then one lane adds 1
+    //      to its XCD's arrival counter -- no value comes back, nobody waits for one -- and the workgroup is done.  A
+    //      workgroup without work does not arrive at all: how many of an XCD's workgroups have work follows from the
+    //      tables every workgroup holds (vb_comp_arrivals), so the finisher knows each counter's final value.  It requests
+    //      what the finish needs besides the accumulators (finish_prefetch) while the others composite, polls the eight
+    //      counters, then reduces.  One line per XCD counter: arrivals on one address serialise at ~12 ns each.
+    //      Forward progress does not depend on co-residency: only the finisher waits, and only for workgroups that wait
+    //      for nobody.  Dispatched early it holds one of a CU's slots while the others run; dispatched last it finds the
+    //      counters complete.  The accumulators are only ever touched by agent-scope atomics and read back with
+    //      agent-scope loads (acc_load), so no cache maintenance is needed between the two.
+    if (!vb_comp_params()->C.do_finish) return;  // (not the last chunk of views: the kernel boundary orders its sums before the last chunk's finish)
+    // (What follows reads its parameters where it needs them, through the kernarg pointer (vb_comp_params): taken from
+    //  the by-value struct they would be scalar registers kept -- spilled -- across the whole tile loop above.)
+    const VbCompParamsPtr Q = vb_comp_params();
+    const int per = nwg >> VB_XCD_BITS;  // workgroups per XCD (nwg is a multiple of VB_XCDS)
+    const int nitems = sparse ? min(s_jbase[U], Q->C.sl.jcap) : Q->C.B * Q->C.g.nt;
+    const int nfill = FILL ? Q->C.B * Q->C.g.nt : 0, nlbox = Q->C.lbox_all ? VB_LBOX_STRIDE * Q->C.B_all * Q->C.g.L : 0;
+    const int kblk = (int)(blockIdx.x >> VB_XCD_BITS);
+    const bool finisher = (int)blockIdx.x == nwg - VB_XCDS;  // the highest workgroup of XCD 0: the last to get an item there
+    const bool arrives = kblk < vb_comp_arrivals(xcd, per, nitems, nfill, nlbox);
+    if (!finisher) {
+        if (!arrives) return;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        // (relaxed, behind the vmcnt and the barrier: what the finisher reads was written by agent-scope atomics that
+        //  have been performed by now.  A release here makes every arriving workgroup write its L2 back first -- +12 us
+        //  a step, profiles/r08_waiting_finisher.md.)
+        if (tid == 0)
+            (void)__hip_atomic_fetch_add(vb_line(Q->C.meta, VB_LINE_COMP_ARRIVE + xcd), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
     }
-    __syncthreads();
-    if (!s_last) return;
-    if (C.ref_flag && tid == 0 && C.ref_flag[0]) atomicOr(&C.meta[EHR_META_OVERFLOW], 1);  // the bound reference's own sums overflowed
-    __syncthreads();
     __shared__ double S[4][17];
     __shared__ float red_lds[8];
     __shared__ float Js[6][16];
-    finish_body<TAIL>(C.g, C.B_all, C.facc_all, sparse ? C.vtot_all : nullptr, C.loss, C.grad_mvp, C.meta, tail, C.nls, nullptr,
-                      VB_LOSS_STRIDE, gpix_all[0], S, red_lds, Js);
+    const long long* const vtot = sparse ? Q->C.vtot_all : nullptr;
+    const BinGeom g = ((const VbCompParams*)Q)->C.g;  // (struct copies: through a generic pointer, still scalar loads)
+    const StepTail tl = ((const VbCompParams*)Q)->tail;
+    FinishPre pre;
+    __syncthreads();  // (every wave is done with its gpix: the link poses go there)
+    finish_prefetch<TAIL>(pre, g, Q->C.B_all, vtot, tl, Q->C.nls, Js, gpix_all[0]);
+    if (Q->C.ref_flag && tid == 0 && Q->C.ref_flag[0]) atomicOr(&Q->C.meta[EHR_META_OVERFLOW], 1);  // the bound reference's own sums overflowed
+    if (wave == 0) {
+        // lane x < 8 watches XCD x's counter (the finisher itself is not counted).  The wait is bounded: a count that
+        // never completes (it cannot, short of a fault elsewhere) is reported as an overflow -- loss = NaN, pose
+        // untouched -- after about a second instead of holding the device.
+        int* const ctr = vb_line(Q->C.meta, VB_LINE_COMP_ARRIVE + (lane & (VB_XCDS - 1)));
+        const int want = vb_comp_arrivals(lane & (VB_XCDS - 1), per, nitems, nfill, nlbox) - (((lane & (VB_XCDS - 1)) == 0 && arrives) ? 1 : 0);
+        bool done = false;
+        for (int polls = 0; polls < VB_FINISH_POLLS; polls++) {
+            const int have = (lane < VB_XCDS) ? __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
+            done = __ballot(have < want) == 0;
+            if (done) break;
+            __builtin_amdgcn_s_sleep(2);
+        }
+        if (lane < VB_XCDS) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next step (a graph replays this launch)
+        if (!done && lane == 0) atomicOr(&Q->C.meta[EHR_META_OVERFLOW], 1);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the finisher's own sums, if it had items)
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    finish_reduce<TAIL>(pre, g, Q->C.B_all, Q->C.facc_all, vtot, Q->C.loss, Q->C.grad_mvp, Q->C.meta, tl, Q->C.nls, VB_LOSS_STRIDE, S, red_lds, Js, gpix_all[0]);
 }
 
 // Content hash of the scoring op's mesh arrays: the cluster index holds copies of the vertex positions, so a mesh edited
@@ -3107,12 +3170,12 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         if (time_it) {
             for (int k = 3; k <= 4; k++) EHR_HIP(hipEventRecord(ev[k], stream));
         }
-        // stage 2: composite, loss, mask, backward.  In the call's last chunk its last-arriving workgroup runs the finish
+        // stage 2: composite, loss, mask, backward.  In the call's last chunk its finisher workgroup runs the finish
         // stage over ALL views (accumulators -> loss / grad_mvp, + pose backward and Adam in the solver-step form; re-arms
         // the link boxes).  With a bound reference mask and no mask output only tiles that hold a job are visited.
         int nwg = ctx->num_cus * VB_COMPOSITE_GRID;
         if (!sparse) nwg = std::min(nwg, (Bk * g.nt + 3) / 4);
-        nwg = std::max(VB_XCDS, vb_xcd_round_up(nwg));  // a multiple of VB_XCDS: the XCD split and the two-level arrival ticket rely on it
+        nwg = std::max(VB_XCDS, vb_xcd_round_up(nwg));  // a multiple of VB_XCDS: the XCD split and the per-XCD arrival counters rely on it
         const size_t dyn = (2 * (size_t)Bk * L + 1) * sizeof(int);  // link tables in LDS
         const bool fill = sparse && mask_k != nullptr;  // (FILL: the zero fill of the tiles no job owns, a variant of its own
                                                           //  so that the form without a mask output keeps its registers)

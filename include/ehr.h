@@ -174,7 +174,7 @@ int ehr_fused_bind_ref(ehr_ctx* ctx, const float* ref, void* stream);
  * and link boxes), ms[1] job kernel (one wave per (view, link, tile): box culling, LDS rasterizer, depth tests where the
  * silhouette analysis will look, and -- since round 5 -- the resolve stage of the job it has just drawn: silhouette analysis,
  * antialiased values, blended pairs; the dominant kernel), ms[4] composite kernel (link sum, clamp, loss, mask, backward; its
- * last-arriving workgroup runs the finish stage: accumulators -> loss / grad_mvp [-> pose backward -> Adam]).  ms[2] brackets
+ * finisher workgroup runs the finish stage: accumulators -> loss / grad_mvp [-> pose backward -> Adam]).  ms[2] brackets
  * the general-triangle pass and the resolve kernel of the jobs it redrew, which the solver step launches only once a step
  * has needed them: in the default chain it is an EMPTY pair of events and measures what a pair costs on this stack (every
  * other figure includes about as much); ms[3], ms[5], ms[6] are unused (~0).
