@@ -7,7 +7,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def problem(xarm7, B, H, W, scale):
+def problem(xarm7, B, H, W, scale, links=None):
+    """links: build the scene from the first `links` links of the robot only (default: all of them)."""
     from easyhec_amd import fused
     from easyhec_amd.config import XARM7_K_1280x720, Cfg
     from easyhec_amd.rb_solver import RBSolver
@@ -15,13 +16,16 @@ def problem(xarm7, B, H, W, scale):
     dev = torch.device("cuda:0")
     K = scaled_K(XARM7_K_1280x720, scale, W, H, True)
     _, lp = make_views(xarm7, B, seed=0)
+    meshes = xarm7.meshes
+    if links is not None:
+        lp, meshes = np.ascontiguousarray(lp[:, :links]), xarm7.meshes[:links]
     Tc = camera_Tc_c2b()
     cfg = Cfg()
     cfg.model.rbsolver.H, cfg.model.rbsolver.W = H, W
     cfg.model.rbsolver.init_Tc_c2b = perturb_pose(Tc).tolist()
 
     def make():
-        return RBSolver(cfg, meshes=xarm7.meshes).to(dev)
+        return RBSolver(cfg, meshes=meshes).to(dev)
 
     m0 = make()
     Kt = torch.tensor(K, dtype=torch.float32, device=dev)

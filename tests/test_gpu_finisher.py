@@ -63,6 +63,33 @@ def test_solver_step_equals_the_stateless_path_at_both_ends_of_the_arrival_count
     fused.check_status(fa.glctx)
 
 
+@pytest.mark.parametrize("B,L", [
+    (1, 1),     # one (view, link) pair: a single thread row of the pose backward has work
+    (22, 3),    # 66 pairs: two more than the finisher parks in LDS, and not a multiple of the 4 pairs a wave row takes
+    (9, 7),     # 63 pairs: one short of the LDS window
+])
+def test_solver_step_equals_the_stateless_path_at_odd_pair_counts(xarm7, B, L):
+    """The same bit-equality with the scene cut down to the first L links of the robot (reference masks rendered from that
+    scene), at 160x120: pair counts B * L below 4, just below and just above the 64 link poses the finisher reads from LDS."""
+    from easyhec_amd import fused
+    from easyhec_amd.fast import FusedPoseStep
+    cfg, make, batch = problem(xarm7, B, 120, 160, 0.125, links=L)
+    ma, mb = make(), make()
+    fa, fb = FusedPoseStep(ma, batch), FusedPoseStep(mb, batch)
+    assert fa.B * fa.L == B * L and fa.scene.num_links == L
+    fused.bind_ref(fb.glctx, fb.scene, None)
+    for it in range(4):
+        fa.step()
+        _piecewise_step(fb, mb)
+        torch.cuda.synchronize()
+        for name in STATE + ["hist_row"]:
+            assert torch.equal(getattr(fa, name), getattr(fb, name)), (it, name)
+        assert torch.equal(ma.dof.data, mb.dof.data)
+        assert bool(torch.isfinite(fa.loss).all()) and float(fa.loss_b.min()) >= 0
+    assert int(fa.step_t.item()) == 4 and float(fa.ref.sum()) > 0
+    fused.check_status(fa.glctx)
+
+
 def test_fifty_steps_eager_and_fifty_replayed_end_on_the_same_pose(xarm7):
     """The arrival counters are re-armed inside the launch: 50 eager steps and 50 replays of the captured step end on
     the same pose and optimiser state bit for bit, and the loss has moved (the steps were real ones)."""
