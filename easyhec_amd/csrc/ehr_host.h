@@ -117,8 +117,8 @@ struct ehr_ctx {
                              // the VB_LINES counter lines)
     ehr::Scratch vb_posc;    // float4 [B][V] clip-space vertices (eager plans only)
     bool vb_lazy = false;    // the plan computes clip-space vertices where they are looked up (VbLazy in ehr_vbuf.hip): V > 1.5 T
-    ehr::Scratch vb_jobs;    // job slots of a chunk and their tables: jval | jitems | jcov | jn | jspill | jid | jdesc | jbase |
-                             // jutile | slow_list (VbSlots, vb_slots)
+    ehr::Scratch vb_jobs;    // job slots of a chunk and their tables: jval | jitems | jn | jspill | jbase | jutile |
+                             // slow_list (VbSlots, vb_slots)
     ehr::Scratch vb_spill;   // blended pairs of jobs that exceed their slot
     int vb_spill_cap = 0;    // ... in items
     ehr::Scratch vb_refsum;  // cached sums of the bound reference mask: tsum i64 [B][nt] | vtot i64 [B] | flag

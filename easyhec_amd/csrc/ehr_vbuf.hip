@@ -7,8 +7,8 @@
 // project to micro-triangles (median bounding box 8 px, a fifth of the non-empty boxes cover no pixel centre at all), for
 // which building and draining per-tile queues cost more than the coverage tests themselves.  Instead ehr_fused_plan
 // groups every link's triangles ONCE into clusters of 64 spatially close ones (recursive median split of the centroids
-// in object space, valid for every pose), and a step is three launches per chunk of views (a fourth and a fifth only after a
-// step has met a triangle for the general path):
+// in object space, valid for every pose), and a step is three launches per chunk of views (a fourth only after a step
+// has met a triangle for the general path; the stateless render call always makes all four):
 //
 //   vb_vertex_kernel    [pose forward] + clip-space vertices (posc) + one wave per cluster: transforms the cluster's
 //                       triangles, snaps them, tests small boxes exactly (a triangle that covers no pixel centre is
@@ -26,9 +26,9 @@
 //   vb_slow_kernel      jobs that met a triangle for the general path: near-plane clipping, 64-bit edges (normally none; the
 //                       solver step launches it only once a step has needed it, see vb_put_aside).
 //   (resolve stage)     covered/uncovered pixel pairs by bit arithmetic on the coverage bitmap, silhouette analysis of the
-//                       hits, the link's 256 antialiased values + the blended pairs -> job slot: done by the job kernel's
-//                       wave for the job it has just drawn, from LDS (vb_resolve_from_lds); vb_resolve_kernel, one wave per
-//                       job, only for the jobs vb_slow_kernel redrew.
+//                       hits, the link's 256 antialiased values + the blended pairs -> job slot: no launch of its own, the
+//                       wave that drew a job (in either of the two kernels above) resolves it from LDS
+//                       (vb_resolve_from_lds).
 //   vb_composite_kernel one wave per tile that holds a job (every tile without a bound reference mask): sums the links'
 //                       values in link order, clamps, frame loss, mask write, back-propagates the tile's blended pairs
 //                       to 12 numbers per link in the view's fixed-point accumulators; its finisher workgroup runs
@@ -78,7 +78,7 @@ constexpr int VB_VERTEX_GRID = 5;      // (VB_VERTEX_WAVES)
 constexpr int VB_JOB_GRID = 4;         // (VB_JOB_WAVES: four workgroups' LDS fit a CU)
 constexpr int VB_COMPOSITE_GRID = 6;
 constexpr int VB_SCORE_COUNT_GRID = 4; // the scoring op's count kernel
-constexpr int VB_SLOW_GRID = 32;       // in total: the general-triangle kernel and the resolve of its jobs (normally idle)
+constexpr int VB_SLOW_GRID = 32;       // in total: the general-triangle kernel (normally idle)
 constexpr bool VB_XCD_SPLIT = true;    // vertex kernel: a chunk of VB_XCDS x k views gives every XCD the views its jobs go to (L2)
 constexpr int VB_FAST_EXTENT = 8192;   // snapped extent (1/16 px) up to which 32-bit edge functions are exact
 
@@ -130,29 +130,22 @@ struct VbCarve {
 struct VbSlots {
     float* jval;       // [jcap][256] the link's antialiased values of the tile
     VbItem* jitems;    // [jcap][VB_JOB_ITEMS] blended pairs for the backward pass
-    u64* jcov;         // [jcap][VB_WORDS] coverage bitmap of the region (region-linear)
     int* jn;           // [jcap] number of blended pairs (-1: the link contributes nothing to the tile)
     int* jspill;       // [jcap] the job's first item in the spill pool
-    unsigned* jid;     // [jcap][VB_RN] triangle ids of the region's pixels
-    int* jdesc;        // [jcap] (view, link) | tile column << 9 | tile row << 19, -1: nothing drawn
     int* jbase;        // [units + 1] first job of every (view, link) of the chunk
     unsigned* jutile;  // [units] its tile range
     int4* slow_list;   // [jcap] jobs put aside for vb_slow_kernel (NULL: that kernel is not launched, see vb_put_aside)
     int jcap;
 };
-constexpr size_t VB_SLOT_BYTES = 256 * sizeof(float) + VB_JOB_ITEMS * sizeof(VbItem) + VB_WORDS * sizeof(u64) + 2 * sizeof(int) +
-                                 VB_RN * sizeof(unsigned) + sizeof(int) + sizeof(int4);  // the [jcap] arrays of vb_slots
-static_assert(VB_SLOT_BYTES == 1024 + 1024 + 48 + 8 + 1360 + 4 + 16, "job slot: 3484 bytes");
+constexpr size_t VB_SLOT_BYTES = 256 * sizeof(float) + VB_JOB_ITEMS * sizeof(VbItem) + 2 * sizeof(int) + sizeof(int4);  // the [jcap] arrays of vb_slots
+static_assert(VB_SLOT_BYTES == 1024 + 1024 + 8 + 16, "job slot: 2072 bytes");
 static VbSlots vb_slots(void* base, size_t jcap, size_t units, size_t* bytes = nullptr) {
     VbCarve c{(uintptr_t)base};
     VbSlots s;
     s.jval = c.take<float>(jcap * 256);
     s.jitems = c.take<VbItem>(jcap * VB_JOB_ITEMS);
-    s.jcov = c.take<u64>(jcap * VB_WORDS);
     s.jn = c.take<int>(jcap);
     s.jspill = c.take<int>(jcap);
-    s.jid = c.take<unsigned>(jcap * VB_RN);
-    s.jdesc = c.take<int>(jcap);
     s.jbase = c.take<int>(units + 1);
     s.jutile = c.take<unsigned>(units);
     s.slow_list = c.take<int4>(jcap, 16);
@@ -768,7 +761,7 @@ __device__ __forceinline__ VbVertsT<false> vb_verts<false>(const VbLazy& z) {
 #define VB_SPAN_GW 4                   // boxes from this many 4-pixel units per row are walked by rows (solved spans), not by units
 constexpr int VB_DL = 640;             // deferred units per wave (LDS); a full list is flushed against the partial coverage
 constexpr int VB_SQ = 256;             // ring of culling survivors per wave (LDS): a whole group of candidate clusters' worth
-constexpr unsigned VB_ID_COVERED = 0xfffffffeu;  // published id of a covered pixel whose triangle nobody will ask for
+constexpr unsigned VB_ID_COVERED = 0xfffffffeu;  // id of a covered pixel whose triangle nobody will ask for
 constexpr u64 VB_ROW_MASK = (1ull << VB_RW) - 1ull;
 
 struct alignas(16) VbRaster {  // staging area of one rasterizer round (64 candidate triangles)
@@ -1291,12 +1284,6 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
     return n;
 }
 
-struct alignas(16) VbResolveLds {  // per wave of the resolve kernel
-    unsigned ids[VB_RN];         // triangle id of each region pixel (all-ones = uncovered), copied from the job's slot
-    float pairA[2 * VB_RN];      // blend weight of pair (q, d) at [d * RN + q]
-    unsigned short hits[2 * VB_RN];
-};
-
 // tiles (+ 1-pixel halo) a link's pixel box touches: the jobs of that (view, link)
 // (halo = 0: the scoring op's coverage-only jobs, which look at their tile alone)
 __device__ __forceinline__ bool vb_unit_tiles(const int* __restrict__ bx, int W, int H, int& tx0, int& ty0, int& nx, int& ny,
@@ -1310,17 +1297,15 @@ __device__ __forceinline__ bool vb_unit_tiles(const int* __restrict__ bx, int W,
     return true;
 }
 
-// Kernel-wide arguments of a job (what the job kernel's helpers need besides the job itself).
 constexpr int VB_CULL_BATCHES = 2;  // batches of 64 cluster boxes requested together
 constexpr int VB_CULL_GROUP = 8;    // candidate clusters whose triangle boxes are requested together
-// (vb_slow_kernel takes this struct by value: with this field order, behind `meta`, it spills 82 scalar registers; other
-//  orders up to 132, the flat argument list it replaces 127 -- compare tools/kres.py before and after touching it.)
+// Kernel-wide arguments of a job's rasterizer (what vb_job_raster needs besides the job itself); both kernels that draw jobs
+// assemble it from their own parameters.
 struct VbJobArgs {
     const float* verts;   // [V][3] object-space vertices
     const float* mvp;     // [B][L][16] the chunk's (view, link) matrices: clip-space vertices are computed on demand (VbLazy) ...
     VbRecs rc;
     int NC, V, W, H, L;
-    VbSlots sl;
     const int4* cvidx;    // [NC * 64] {v0, v1, v2, triangle} of every cluster slot
     const float4* posc;   // ... or read from here ([B][V]) where the plan keeps them (NULL: lazy)
     const int* lcoff;     // first cluster of every link (the job kernel: its copy in LDS)
@@ -1474,83 +1459,25 @@ __device__ __forceinline__ int vb_job_raster(const VbJobArgs& A, VbWaveLds& W_, 
     return drawn ? 1 : 0;
 }
 
-// A job vb_job_slow drew leaves, in its slot, the coverage rows of its region and the triangle id of every pixel the depth
-// test ran for (all-ones elsewhere), then its descriptor; vb_resolve_kernel takes it from there.
-__device__ __forceinline__ void vb_publish(const VbJobArgs& A, const u64* key_, const u64* cov_, int job, int u, int tx,
-                                           int ty) {
-    const int lane = lane_id();
-    VB_WAVE_SYNC();
-    unsigned* const dst = A.sl.jid + (size_t)job * VB_RN;
-#pragma unroll
-    for (int k = 0; k < VB_WORDS; k++) {
-        const unsigned i = 64u * k + lane;
-        if (i < (unsigned)VB_RN) dst[i] = (unsigned)key_[i];  // low word = triangle id; all-ones stays all-ones
-    }
-    // coverage in region-linear order (bit i = region pixel i), what the resolve kernel's bit arithmetic works on
-#pragma unroll
-    for (int k = 0; k < VB_WORDS; k++) {
-        const unsigned i = 64u * k + lane;
-        const unsigned row = (unsigned)vb_div_rw((int)i), col = i - row * VB_RW;
-        const u64 w = __ballot(i < (unsigned)VB_RN && ((cov_[row < (unsigned)VB_RH ? row : 0] >> col) & 1ull));
-        if (lane == 0) A.sl.jcov[(size_t)job * VB_WORDS + k] = w;
-    }
-    if (lane == 0) A.sl.jdesc[job] = u | (tx << 9) | (ty << 19);
-}
-
-// A whole job on one wave with the general triangle path compiled in (near-plane clipping, 64-bit edge functions): what a
-// job falls back to when the lean code meets such a triangle.  Runs in a kernel of its own (vb_slow_kernel) over the list
-// of such jobs: compiled into the job kernel -- inline or as a call, in the rounds or at the job loop's end -- the general
-// path cost the lean code 50-70 spilled registers and 13 us at 8 views.
-template <bool LAZY>
-__device__ __forceinline__ void vb_job_slow(const VbJobArgs& A, VbWaveLds& S, int job, int u, int tx, int ty) {
-    const int lane = lane_id();
-    const int b = u / A.L, l = u - b * A.L;
-    const int rx0 = tx * EHR_TILE_W - 1, ry0 = ty * EHR_TILE_H - 1;
-    VbRegion rg;
-    rg.x0 = max(rx0, 0);
-    rg.y0 = max(ry0, 0);
-    rg.x1 = min(rx0 + VB_RW - 1, A.W - 1);
-    rg.y1 = min(ry0 + VB_RH - 1, A.H - 1);
-    VB_WAVE_SYNC();
-#pragma unroll
-    for (int k = 0; k < VB_WORDS; k++) {
-        const unsigned i = 64u * k + lane;
-        if (i < (unsigned)VB_RN) S.key[i] = VB_EMPTY;
-    }
-    if (lane < VB_RH) S.cov[lane] = 0ull;
-    VB_WAVE_SYNC();
-    int nsurv = 0, dln = 0;
-    const int drawn = vb_job_raster<true, false, LAZY>(A, S, S.key, S.cov, b, l, rg, rx0, ry0, 0, 1, nsurv, dln);
-    if (dln > 0) vb_flush<false, LAZY>(S, S.key, S.cov, dln, VbLazy{A.verts, A.mvp + ((size_t)b * A.L + l) * 16, A.posc ? A.posc + (size_t)b * A.V : nullptr}, A.cvidx + (size_t)A.lcoff[l] * 64, A.W, A.H, rx0, ry0);
-    if (drawn > 0) {
-        vb_publish(A, S.key, S.cov, job, u, tx, ty);
-    } else if (lane == 0) {
-        A.sl.jn[job] = -1;
-        A.sl.jdesc[job] = -1;
-    }
-}
-
 // Stage 2: one WAVE per job = (view, link, 32x8 tile the link's screen box touches); persistent waves over the job list,
 // which is never materialised (every workgroup derives it from the link boxes with a prefix sum over B * L counts).
 // A job culls the link's cluster boxes, then the triangle boxes of the surviving clusters, and rasterizes the survivors
-// into the wave's LDS depth/id buffer (tile + 1-pixel halo).  It leaves, in the job's slot (view, link, tile), the
-// triangle id of every region pixel (jid) and a descriptor (jdesc; -1 and jn = -1 when nothing was drawn); the resolve
-// kernel takes it from there.  No workgroup barriers after the prologue except in the heavy-job phase; thousands of
-// independent waves hide each other's latency.
+// into the wave's LDS depth/id buffer (tile + 1-pixel halo); the same wave then resolves the job from there
+// (vb_resolve_from_lds), or marks the slot empty (jn = -1) when nothing was drawn.  No workgroup barriers after the prologue
+// except in the heavy-job phase; thousands of independent waves hide each other's latency.
 // A job that met a triangle for the general path goes on the list vb_slow_kernel works off.  The solver-step form of the
 // chain does not launch that kernel until a step has needed it (slow_list == NULL: an empty launch costs the step 1.7 us
 // and a robot in front of the camera never has such a triangle): then the job is marked empty and the step REPORTS it --
 // VB_FLAG_NEED_SLOW among the overflow bits, so loss and gradient come out NaN and the optimiser state stays as it was; ehr_fused_status() returns
 // EHR_ERR_RETRY and switches the pass on for the context's later calls.
 __device__ __forceinline__ void vb_put_aside(int4* __restrict__ slow_list, int* __restrict__ meta, int* __restrict__ jn,
-                                             int* __restrict__ jdesc, int job, int u, int tx, int ty) {
+                                             int job, int u, int tx, int ty) {
     if (slow_list) {
         int* const nslow = vb_line(meta, VB_LINE_SLOW_COUNT);
         slow_list[atomicAdd(nslow, 1)] = make_int4(job, u, tx, ty);
     } else {
         atomicOr(&meta[EHR_META_OVERFLOW], VB_FLAG_NEED_SLOW);
         jn[job] = -1;
-        jdesc[job] = -1;
     }
 }
 
@@ -1574,8 +1501,8 @@ struct VbResolveArgs {
 // analysis of the compacted hits (restates nvdiffrast's antialias mesh kernel), gather of the link's antialiased value per
 // pixel in the oracle's order.  Leaves in the job's slot the 256 values (jval), the blended pairs the backward pass needs
 // (jitems) and their number (jn; -1 = the link contributes nothing here).  pairA [2 * VB_RN] and hits [2 * VB_RN] are the
-// wave's LDS work areas.  Called by the job kernel right after a job's depth tests (the ids never leave LDS) and by
-// vb_resolve_kernel for the jobs vb_slow_kernel drew.
+// wave's LDS work areas.  Called right after a job's depth tests, by the wave that ran them (vb_resolve_from_lds: the ids
+// never leave LDS).
 template <bool LAZY = false>
 __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const unsigned* ids, float* pairA,
                                                unsigned short* hits, const u64 (&C)[VB_WORDS], size_t slot, int b,
@@ -1761,8 +1688,9 @@ __device__ __forceinline__ void vb_resolve_job(const VbResolveArgs& Q, const uns
 #undef KT
 }
 
-// The job kernel's call: the job's coverage rows (cov) and depth/id buffer (key) are complete in LDS; the ids move to the
-// (now idle) deferred list, the key buffer becomes the pair table, and the wave resolves the job it has just drawn.
+// The call of a wave that has drawn a job (vb_job_kernel, vb_job_slow): the job's coverage rows (cov) and depth/id buffer
+// (key) are complete in LDS; the ids move to the (now idle) deferred list, the key buffer becomes the pair table, and the
+// wave resolves the job it has just drawn.
 // Nothing of the job's region goes through global memory, and the resolve stage needs no launch of its own: it was a
 // 10 us kernel of one dependent chain per job behind a boundary; here the chain runs while other waves still rasterize.
 // (Resolve and rasterizer never overlap inside a wave: the live ranges of the two are disjoint, unlike round 2's fusion.)
@@ -1809,10 +1737,10 @@ __device__ __forceinline__ void vb_zero_tile_row(float* __restrict__ mask, size_
 }
 
 // What the composite stage needs besides its LDS tables.  vb_composite_kernel takes the struct by value, and the ORDER of the
-// fields (with StepTail behind the struct) is what the register allocator's result depends on: this order, found by trying
-// 160 random ones, is the one where every variant spills fewer scalar registers than the flat argument list it replaces
-// (<TAIL,FILL> 39, <TAIL> 37, <FILL> 37, <> 31; before 48 / 44 / 38 / 32; other orders 29-74).  Adding or moving a field
-// moves those figures: compare tools/kres.py before and after (profiles/r07_scratch_layout_refactor.md holds the table).
+// fields (with StepTail behind the struct) is what the register allocator's result depends on: this order was found by
+// trying random ones and, when VbSlots changed size, every position of `sl` (spilled scalar registers <TAIL,FILL> 21,
+// <TAIL> 20, <FILL> 20, <> 18; `sl` elsewhere 20-24).  Adding or moving a field moves those figures: compare tools/kres.py
+// before and after (profiles/r07_scratch_layout_refactor.md and r10_slow_pass_resolves_itself.md hold the tables).
 // (Read in place through the kernarg pointer instead, the fields are fetched again in the tile loop: 16-19 spilled, and
 // 0.5-1 % of the step slower.)
 struct VbCompArgs {
@@ -1821,11 +1749,11 @@ struct VbCompArgs {
     float* loss;         // (loss .. lbox_all, ref_flag: for the finish stage, run by the finisher workgroup of the call's
     int B;               //  last chunk of views -- do_finish -- over ALL views of the call)
     long long* facc;     // the chunk's accumulators
-    VbSlots sl;          // (read only here)
     int do_finish, B_all;
     const float* mvp;    // [B][L][16] (clip-space vertices on demand: VbLazy)
     int spill_cap;
     int* lbox_all;
+    VbSlots sl;          // (read only here)
     float* mask;
     const float* verts;
     const float* ref;
@@ -2078,6 +2006,13 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
 }
 
 constexpr int VB_JOB_WAVES = 4;
+// What the coverage-only form of the job kernel (COVER, the scoring op) writes instead of job slots; the buffers are
+// described by vb_score_misc.
+struct VbCoverOut {
+    u64* tcov;    // [candidate][tile][pose][4] coverage words the jobs OR their tile's interior into
+    int* sticky;  // [0]: raised by a job that met a triangle whose depth class does not let coverage decide
+    int S;        // poses per candidate
+};
 // The job kernel's parameters, ONE struct in the kernarg segment.  The kernel does not name its parameter; it reads the
 // fields through the kernarg segment pointer, made opaque to the optimiser at every use (vb_job_params), so that a field
 // is a scalar load where it is needed instead of one of ~60 scalar registers filled at kernel entry and kept -- i.e.
@@ -2094,6 +2029,7 @@ struct VbJobParams {
     VbSlotIdx si;
     int heavy_t, med_t0;
     VbResolveArgs rq;  // the scene, the job slots and the meta block: the resolve stage runs on the wave that drew the job
+    VbCoverOut co;     // COVER only (rq then holds the scene and the meta block, no slots)
 };
 typedef const VbJobParams __attribute__((address_space(4)))* VbJobParamsPtr;
 __device__ __forceinline__ VbJobParamsPtr vb_job_params() {
@@ -2107,8 +2043,7 @@ template <class T>
 __device__ __forceinline__ T vb_prm_copy(const T __attribute__((address_space(4)))* p) {
     return *(const T*)p;
 }
-// COVER (the scoring op): jcov = the (view, tile) coverage words [B][nt][4] the jobs OR their tile's interior into, jn = one
-// sticky flag raised by a job that met a triangle whose depth class does not let coverage decide; no slots, no lists.
+// COVER (the scoring op): no slots, no lists; the jobs' outputs are those of VbCoverOut.
 template <bool COVER, bool LAZY = false>
 __global__ void __launch_bounds__(256, VB_JOB_WAVES)
 vb_job_kernel(VbJobParams) {
@@ -2188,17 +2123,12 @@ vb_job_kernel(VbJobParams) {
     __syncthreads();
     total = upre[U];
     }
-    if (blockIdx.x == 0) {
+    if (!COVER && blockIdx.x == 0) {
         // job slots are numbered like the jobs: stage 3 finds a (view, link, tile) slot from the link's first job
         // (every entry this wave may read here it has written itself, or a barrier lies in between: see above)
-        if (!COVER) {
-            for (int u = tid; u <= U; u += 256) PRM(rq.sl.jbase)[u] = upre[u];
-            for (int u = tid; u < U; u += 256) PRM(rq.sl.jutile)[u] = utile[u];
-        }
-        if (tid == 0) {
-            PRM(rq.meta)[5] = total;  // number of jobs (the resolve kernel's loop bound)
-            if (!COVER && total > PRM(rq.sl.jcap)) PRM(rq.meta)[EHR_META_OVERFLOW] = 1;  // cannot happen with one slot per (view, link, tile)
-        }
+        for (int u = tid; u <= U; u += 256) PRM(rq.sl.jbase)[u] = upre[u];
+        for (int u = tid; u < U; u += 256) PRM(rq.sl.jutile)[u] = utile[u];
+        if (tid == 0 && total > PRM(rq.sl.jcap)) PRM(rq.meta)[EHR_META_OVERFLOW] = 1;  // cannot happen with one slot per (view, link, tile)
     }
     if (!COVER) total = min(total, PRM(rq.sl.jcap));
     // XCD-aware order (workgroup w runs on XCD w % VB_XCDS; used for L2 locality only): every XCD takes a contiguous
@@ -2217,14 +2147,13 @@ vb_job_kernel(VbJobParams) {
     A.posc = posc;
     A.cvidx = PRM(si.cvidx);
     A.lcoff = lcoff;
-    A.sl = vb_prm_copy(&PRM(rq.sl));
     A.NC = PRM(cl.NC);
     A.V = V;
     A.W = W;
     A.H = H;
     A.L = L;
     // ---- heavy jobs first, one workgroup each: the four waves share the job's depth/id buffer (wave 0's) and split the
-    //      candidate clusters; wave 0 publishes.  A job alone costs up to ~80 us on one wave (a thousand candidate
+    //      candidate clusters; wave 0 resolves it.  A job alone costs up to ~80 us on one wave (a thousand candidate
     //      triangles in one tile), which used to be the duration of this kernel at small batch sizes.
     __shared__ int s_heavy[2];  // drawn flag, survivors
     // Only when the machine is short of jobs (at most ~2 per wave): with many views per GPU the kernel is bound by the
@@ -2302,11 +2231,10 @@ vb_job_kernel(VbJobParams) {
         }
         if (wave == 0) {
             if (any_drawn & 2) {  // put aside for vb_slow_kernel
-                if (lane == 0) vb_put_aside(PRM(rq.sl.slow_list), PRM(rq.meta), PRM(rq.sl.jn), PRM(rq.sl.jdesc), job, u, tx, ty);
+                if (lane == 0) vb_put_aside(PRM(rq.sl.slow_list), PRM(rq.meta), PRM(rq.sl.jn), job, u, tx, ty);
             } else if (any_drawn) {
             } else if (lane == 0) {
                 PRM(rq.sl.jn)[job] = -1;
-                PRM(rq.sl.jdesc)[job] = -1;
             }
             if (lane == 0) {
                 s_heavy[0] = 0;
@@ -2417,7 +2345,7 @@ vb_job_kernel(VbJobParams) {
                 vb_flush<true, LAZY>(S, S.key, S.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
             VB_WAVE_SYNC();
             if (drawn < 0 || S.bad) {  // a triangle for the general path, or a drawn pixel with a depth <= 0: coverage cannot
-                if (lane == 0) PRM(rq.sl.jn)[0] = 1;  // decide here and the caller falls back for the whole call
+                if (lane == 0) PRM(co.sticky)[0] = 1;  // decide here and the caller falls back for the whole call
                 continue;
             }
             if (drawn > 0) {
@@ -2425,15 +2353,14 @@ vb_job_kernel(VbJobParams) {
                 VB_WAVE_SYNC();
                 if (lane < 4) {
                     const u64 w = ((S.cov[2 * lane + 1] >> 1) & 0xffffffffull) | (((S.cov[2 * lane + 2] >> 1) & 0xffffffffull) << 32);
-                    // (layout [candidate][tile][pose][4]: the count kernel reads a candidate's words of a tile in one piece;
-                    //  PRM(rq.sl.jcap) carries S, the poses per candidate, in this form)
-                    if (w) atomicOr((unsigned long long*)&PRM(rq.sl.jcov)[((((size_t)(b / PRM(rq.sl.jcap)) * gnt + (size_t)ty * gntx + tx) * PRM(rq.sl.jcap) + (b % PRM(rq.sl.jcap))) * 4 + lane)], w);
+                    // (layout [candidate][tile][pose][4]: the count kernel reads a candidate's words of a tile in one piece)
+                    if (w) atomicOr((unsigned long long*)&PRM(co.tcov)[((((size_t)(b / PRM(co.S)) * gnt + (size_t)ty * gntx + tx) * PRM(co.S) + (b % PRM(co.S))) * 4 + lane)], w);
                 }
             }
             continue;
         }
         if (drawn < 0) {  // a triangle for the general path (near-plane clipping, huge extent): put the job aside
-            if (lane == 0) vb_put_aside(PRM(rq.sl.slow_list), PRM(rq.meta), PRM(rq.sl.jn), PRM(rq.sl.jdesc), job, u, tx, ty);
+            if (lane == 0) vb_put_aside(PRM(rq.sl.slow_list), PRM(rq.meta), PRM(rq.sl.jn), job, u, tx, ty);
             continue;
         }
         if (dln > 0) vb_flush<false, LAZY>(S, S.key, S.cov, dln, VbLazy{pverts, pmvp + ((size_t)b * L + l) * 16, LAZY ? nullptr : posc + (size_t)b * V}, PRM(si.cvidx) + (size_t)lcoff[l] * 64, W, H, rx0, ry0);
@@ -2444,10 +2371,7 @@ vb_job_kernel(VbJobParams) {
                 remember_long(hint_id);
         }
         if (drawn == 0) {  // the link's box touches this tile, its triangles do not
-            if (lane == 0) {
-                PRM(rq.sl.jn)[slot] = -1;
-                PRM(rq.sl.jdesc)[slot] = -1;
-            }
+            if (lane == 0) PRM(rq.sl.jn)[slot] = -1;
             continue;
         }
         vb_resolve_from_lds<LAZY>(vb_prm_copy(&PRM(rq)), S, S.key, S.cov, slot, b, l, rx0, ry0);
@@ -2455,72 +2379,56 @@ vb_job_kernel(VbJobParams) {
 }
 #undef PRM
 
-// Stage 2a (normally empty): the jobs the lean code put aside, one wave each, with the general triangle path.
+// A whole job on one wave with the general triangle path compiled in (near-plane clipping, 64-bit edge functions): what a
+// job falls back to when the lean code meets such a triangle; the wave resolves the job it has redrawn like the job kernel's
+// waves do.  Runs in a kernel of its own (vb_slow_kernel) over the list of such jobs: compiled into the job kernel --
+// inline or as a call, in the rounds or at the job loop's end -- the general path cost the lean code 50-70 spilled
+// registers and 13 us at 8 views.
+template <bool LAZY>
+__device__ __forceinline__ void vb_job_slow(const VbJobArgs& A, const VbResolveArgs& Q, VbWaveLds& S, int job, int u, int tx,
+                                            int ty) {
+    const int lane = lane_id();
+    const int b = u / A.L, l = u - b * A.L;
+    const int rx0 = tx * EHR_TILE_W - 1, ry0 = ty * EHR_TILE_H - 1;
+    VbRegion rg;
+    rg.x0 = max(rx0, 0);
+    rg.y0 = max(ry0, 0);
+    rg.x1 = min(rx0 + VB_RW - 1, A.W - 1);
+    rg.y1 = min(ry0 + VB_RH - 1, A.H - 1);
+    VB_WAVE_SYNC();
+#pragma unroll
+    for (int k = 0; k < VB_WORDS; k++) {
+        const unsigned i = 64u * k + lane;
+        if (i < (unsigned)VB_RN) S.key[i] = VB_EMPTY;
+    }
+    if (lane < VB_RH) S.cov[lane] = 0ull;
+    VB_WAVE_SYNC();
+    int nsurv = 0, dln = 0;
+    const int drawn = vb_job_raster<true, false, LAZY>(A, S, S.key, S.cov, b, l, rg, rx0, ry0, 0, 1, nsurv, dln);
+    if (dln > 0) vb_flush<false, LAZY>(S, S.key, S.cov, dln, VbLazy{A.verts, A.mvp + ((size_t)b * A.L + l) * 16, A.posc ? A.posc + (size_t)b * A.V : nullptr}, A.cvidx + (size_t)A.lcoff[l] * 64, A.W, A.H, rx0, ry0);
+    if (drawn > 0)
+        vb_resolve_from_lds<LAZY>(Q, S, S.key, S.cov, (size_t)job, b, l, rx0, ry0);
+    else if (lane == 0)
+        Q.sl.jn[job] = -1;
+}
+
+// Stage 2a (normally empty): the jobs the lean code put aside, one wave each, with the general triangle path.  Takes the
+// resolve stage's arguments and what the rasterizer needs beyond them.  (Not a hot kernel: its scalar spills do not matter,
+// and both forms of the vertex look-up are compiled in, chosen per launch.)
 __global__ void __launch_bounds__(256)
-vb_slow_kernel(const int* __restrict__ meta, VbJobArgs A) {
-    const int n = *vb_line(const_cast<int*>(meta), VB_LINE_SLOW_COUNT);
+vb_slow_kernel(VbResolveArgs Q, VbRecs rc, int NC, const int4* __restrict__ cvidx, const int* __restrict__ lcoff) {
+    const int n = *vb_line(Q.meta, VB_LINE_SLOW_COUNT);  // jobs put aside (vb_put_aside)
     if (n == 0) return;
     __shared__ VbWaveLds lds_all[4];
     const int wave = threadIdx.x >> 6;
+    const VbJobArgs A = {Q.verts, Q.mvp, rc, NC, Q.V, Q.W, Q.H, Q.L, cvidx, Q.posc, lcoff};
     for (int i = blockIdx.x * 4 + wave; i < n; i += gridDim.x * 4) {
-        const int4 e = A.sl.slow_list[i];
-        if (A.posc)  // (not a hot kernel: both forms compiled in, chosen per launch)
-            vb_job_slow<false>(A, lds_all[wave], e.x, e.y, e.z, e.w);
-        else
-            vb_job_slow<true>(A, lds_all[wave], e.x, e.y, e.z, e.w);
-    }
-}
-
-// Stage 2b (normally empty): the resolve stage of the jobs vb_slow_kernel redrew with the general triangle path, one WAVE
-// per entry of slow_list.  Those jobs PUBLISHED their coverage and triangle ids to their slot (jid / jcov / jdesc); every
-// other job was resolved by the job kernel's wave that drew it, straight from LDS (vb_resolve_from_lds).  The solver step
-// launches this kernel only together with vb_slow_kernel.
-__global__ void __launch_bounds__(256)
-vb_resolve_kernel(VbResolveArgs Q) {
-    __shared__ VbResolveLds lds_all[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    VbResolveLds& S = lds_all[wave];
-    const int L = Q.L;
-    const int n = *vb_line(Q.meta, VB_LINE_SLOW_COUNT);  // jobs put aside (vb_put_aside)
-    for (int it = (int)blockIdx.x * 4 + wave; it < n; it += (int)gridDim.x * 4) {
-        const int job = Q.sl.slow_list[it].x;
-        if (job >= Q.sl.jcap) continue;
-        const size_t slot = (size_t)job;
-        // the ids are requested together with the descriptor (one round trip; an undrawn slot holds stale ids, unused)
-        unsigned idw[VB_WORDS];
-        {
-            const unsigned* const src = Q.sl.jid + slot * VB_RN;
-#pragma unroll
-            for (int k = 0; k < VB_WORDS; k++) {
-                const unsigned i = 64u * k + lane;
-                idw[k] = (i < (unsigned)VB_RN) ? src[i] : 0xffffffffu;
-            }
-        }
-        const u64 mycw = (lane < VB_WORDS) ? Q.sl.jcov[slot * VB_WORDS + lane] : 0ull;  // coverage bitmap of the region
-        const int de = Q.sl.jdesc[job];
-        if (de < 0) continue;  // nothing drawn: the job kernel has already marked the slot
-        const int u = de & 511, tx = (de >> 9) & 1023, ty = (de >> 19) & 4095;
-        const int b = u / L;
-        const int rx0 = tx * EHR_TILE_W - 1, ry0 = ty * EHR_TILE_H - 1;
-        u64 C[VB_WORDS];  // bit i = region pixel i is covered
-#pragma unroll
-        for (int k = 0; k < VB_WORDS; k++) {
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mycw, k);
-            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(mycw >> 32), k);
-            C[k] = ((u64)hi << 32) | lo;
-        }
-        VB_WAVE_SYNC();  // the previous job's reads of S are complete
-#pragma unroll
-        for (int k = 0; k < VB_WORDS; k++) {
-            const unsigned i = 64u * k + lane;
-            // covered pixels whose triangle was never asked for (no uncovered neighbour) carry a marker instead of an id
-            if (i < (unsigned)VB_RN)
-                S.ids[i] = (idw[k] != 0xffffffffu) ? idw[k] : (((C[k] >> lane) & 1ull) ? VB_ID_COVERED : 0xffffffffu);
-        }
+        const int4 e = Q.sl.slow_list[i];
+        if (e.x >= Q.sl.jcap) continue;  // (no slot of that number: nothing of it may be written)
         if (Q.posc)
-            vb_resolve_job<false>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
+            vb_job_slow<false>(A, Q, lds_all[wave], e.x, e.y, e.z, e.w);
         else
-            vb_resolve_job<true>(Q, S.ids, S.pairA, S.hits, C, slot, b, u - b * L, rx0, ry0);
+            vb_job_slow<true>(A, Q, lds_all[wave], e.x, e.y, e.z, e.w);
     }
 }
 
@@ -2985,7 +2893,7 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
     const int NC = std::max(ctx->vb_nc, 1);
     // The views of a call go through the chain in CHUNKS of Bc views (one chunk in the common case): the job kernel
     // keeps its (view, link) tables in LDS (VB_MAX_UNITS entries), and the per-chunk scratch -- clip-space vertices,
-    // raster records (vb_recs), job slots (vb_slots, 3.5 KB each) -- is bounded to 24 GB of the 288 (EHR_VB_SCRATCH_MB) however many views a
+    // raster records (vb_recs), job slots (vb_slots, 2 KB each) -- is bounded to 24 GB of the 288 (EHR_VB_SCRATCH_MB) however many views a
     // call brings: a chunk costs a pass of the chain with its own tails, so chunks are as large as they may be (the reference
     // batches all frames of a data set in one step, configs/xarm7/example.yaml: batch_size 100).  A job = a (link, tile)
     // pair whose boxes touch; by default (`slack` <= 0) one slot per (link, tile) is provided, so nothing can overflow;
@@ -3132,8 +3040,9 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         }
         EHR_LAUNCH_CHECK();
         if (time_it) EHR_HIP(hipEventRecord(ev[1], stream));
-        // stage 1: jobs = (view, link, tile) -> coverage and the triangle ids the silhouette analysis will ask for
-        VbResolveArgs rq;  // the resolve stage runs inside the job kernel, on the wave that drew the job
+        // stage 1: jobs = (view, link, tile) -> coverage, the triangle ids the silhouette analysis asks for, and the resolve
+        // stage on the wave that drew the job -> per-link values and blended pairs in the job's slot
+        VbResolveArgs rq;
         rq.verts = verts; rq.mvp = mvp_k; rq.posc = posc; rq.V = V; rq.L = L; rq.W = W; rq.H = H;
         rq.tri4 = (const int4*)ctx->vb_idx.ptr;
         rq.opp4 = (const int4*)ctx->vb_idx.ptr + T;
@@ -3143,7 +3052,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         rq.spill_cap = ctx->vb_spill_cap;
         rq.meta = meta;
         rq.want_grad = grad_mvp ? 1 : 0;
-        VbJobParams jp;
+        VbJobParams jp = {};
         jp.g = g; jp.B = Bk; jp.cl = cl; jp.si = si; jp.rc = recs; jp.lbox = lbox; jp.hv = hv;
         jp.use_hint = Bc == B;  // (the heavy-job hint names jobs by their dense id inside a chunk: off with more than one)
         jp.heavy_t = VB_HEAVY_T_DEFAULT;
@@ -3156,19 +3065,11 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         EHR_LAUNCH_CHECK();
         // stage 1a: jobs with a triangle that crosses the near plane or spans > 512 pixels (normally none: the kernel returns at once)
         if (with_slow) {
-            const VbJobArgs ja = {verts, mvp_k, recs, cl.NC, V, W, H, L, sl, si.cvidx, posc, cl.coff};
-            vb_slow_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(meta, ja);
+            vb_slow_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(rq, recs, cl.NC, si.cvidx, cl.coff);
             EHR_LAUNCH_CHECK();
         }
-        if (time_it) EHR_HIP(hipEventRecord(ev[2], stream));
-        // stage 1b: drawn jobs -> per-link values and blended pairs.  The job kernel has done that for the jobs it drew itself;
-        // only the jobs vb_slow_kernel redrew are left (none, normally: a launch of 32 workgroups that read a counter)
-        if (with_slow) {
-            vb_resolve_kernel<<<VB_SLOW_GRID, 256, 0, stream>>>(rq);
-            EHR_LAUNCH_CHECK();
-        }
-        if (time_it) {
-            for (int k = 3; k <= 4; k++) EHR_HIP(hipEventRecord(ev[k], stream));
+        if (time_it) {  // (ms[2] of the timing ABI, ev[2]..ev[3], is an empty pair: the resolve stage has no launch of its own)
+            for (int k = 2; k <= 4; k++) EHR_HIP(hipEventRecord(ev[k], stream));
         }
         // stage 2: composite, loss, mask, backward.  In the call's last chunk its finisher workgroup runs the finish
         // stage over ALL views (accumulators -> loss / grad_mvp, + pose backward and Adam in the solver-step form; re-arms
@@ -3322,9 +3223,7 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         jp.g = g; jp.B = Bk; jp.cl = cl; jp.si = si; jp.rc = recs; jp.lbox = lbox; jp.hv = hv;  // (use_hint = 0)
         jp.rq.verts = verts; jp.rq.posc = posc; jp.rq.V = V; jp.rq.meta = meta;
         jp.rq.mvp = mvp + (size_t)q0 * S * L * 16;
-        jp.rq.sl.jn = sticky;  // (the coverage-only form of the slots: see vb_job_kernel)
-        jp.rq.sl.jcov = tcov;
-        jp.rq.sl.jcap = S;
+        jp.co = {tcov, sticky, S};
         jp.heavy_t = 0x7fffffff;
         jp.med_t0 = 0x7fffffff;
         vb_job_kernel<true><<<job_wgs, 256, 0, stream>>>(jp);

@@ -132,7 +132,7 @@ class FusedPoseStep:
         self.grad = torch.zeros((6,), device=dev)
         self.mask = torch.empty((self.B, self.H, self.W), device=dev)
         # job slots: `slack` per view tile (default: half as many slots as a view has tiles) instead of one per (view,
-        # link, tile) -- 50 MB instead of 0.8 GB of scratch at 8 views 720p x 8 links; the workloads here use a tenth of
+        # link, tile) -- 30 MB instead of 0.48 GB of scratch at 8 views 720p x 8 links; the workloads here use a tenth of
         # that (a robot's links touch ~5 % of a frame's tiles).  A view that needs more (every pixel under more than
         # `slack` link boxes on average: a close-up) is REPORTED -- NaN loss, dof and Adam state untouched -- and
         # :meth:`recover_from_overflow` plans again with a slot for every (view, link, tile).  EHR_VB_SLACK overrides (0 = all).
@@ -241,7 +241,7 @@ class FusedPoseStep:
         dof = m.dof.data
         hist = m.history_ops
         # one C call = 3 launches: [pose fwd + vertices + raster records] -> jobs, resolved by the waves that drew them
-        # [-> general-triangle jobs + their resolve, once a step has needed them] -> composite [+ in its last workgroup:
+        # [-> general-triangle jobs, resolved likewise, once a step has needed them] -> composite [+ in its last workgroup:
         # accumulators + pose bwd (+ Adam)]
         _lib.check(lib.ehr_solver_step(
             self.glctx.handle, _lib.ptr(sc.verts), _lib.ptr(sc.tris), _lib.ptr(sc.tri_link), _lib.ptr(sc.vert_link),

@@ -140,7 +140,7 @@ int ehr_antialias_grad(const float* color, const float* rast, const float* pos, 
  * scene, the shape or the arrays change -- also when only the CONTENTS of verts / tris change: the index holds a copy
  * of every triangle's corners).  Limits, checked here: L <= 32, W <= 32736, H <= 32760, <= 262144 triangles per link.
  * Any number of views: a call's views go through the launch chain in chunks (one chunk up to 512 / L views; fewer per
- * chunk when the chunk's scratch -- clip-space vertices, raster records, 3.5 KB per (view, link, tile) job slot: 0.1 GB per
+ * chunk when the chunk's scratch -- clip-space vertices, raster records, 2 KB per (view, link, tile) job slot: 0.06 GB per
  * 1280x720 view of an 8-link robot -- would exceed 24 GB, EHR_VB_SCRATCH_MB), all inside the one call.  The hot calls never synchronise or allocate, so they can be
  * captured in a hipGraph; a new plan invalidates a captured graph.  `slack` <= 0 (default): one job slot per (view, link,
  * tile), nothing can overflow except the fixed-point accumulators (|sum| > 2^31) and a 16 MB spill pool for tiles with
@@ -172,12 +172,12 @@ int ehr_fused_bind_ref(ehr_ctx* ctx, const float* ref, void* stream);
  * milliseconds per stage since the last read and the number of calls covered, then resets.  Stages of the default
  * (visibility-buffer) chain: ms[0] vertex kernel (pose forward, clip-space vertices, per-triangle raster records, cluster
  * and link boxes), ms[1] job kernel (one wave per (view, link, tile): box culling, LDS rasterizer, depth tests where the
- * silhouette analysis will look, and -- since round 5 -- the resolve stage of the job it has just drawn: silhouette analysis,
- * antialiased values, blended pairs; the dominant kernel), ms[4] composite kernel (link sum, clamp, loss, mask, backward; its
- * finisher workgroup runs the finish stage: accumulators -> loss / grad_mvp [-> pose backward -> Adam]).  ms[2] brackets
- * the general-triangle pass and the resolve kernel of the jobs it redrew, which the solver step launches only once a step
- * has needed them: in the default chain it is an EMPTY pair of events and measures what a pair costs on this stack (every
- * other figure includes about as much); ms[3], ms[5], ms[6] are unused (~0).
+ * silhouette analysis will look, and the resolve stage of the job it has just drawn: silhouette analysis, antialiased
+ * values, blended pairs; the dominant kernel -- followed, once a step has needed it, by the general-triangle pass, whose
+ * waves likewise resolve what they redraw), ms[4] composite kernel (link sum, clamp, loss, mask, backward; its
+ * finisher workgroup runs the finish stage: accumulators -> loss / grad_mvp [-> pose backward -> Adam]).  ms[2] is the
+ * place of a resolve launch the chain does not have: always an EMPTY pair of events, it measures what a pair costs on
+ * this stack (every other figure includes about as much); ms[3], ms[5], ms[6] are unused (~0).
  * Not for use under graph capture. */
 #define EHR_FUSED_STAGES 7
 int ehr_fused_timing(ehr_ctx* ctx, int enable);
@@ -203,8 +203,8 @@ int ehr_pose_adam(float* dof, float* m, float* v, int32_t* step, const float* re
                   float eps, float weight_decay, float* loss_out, float* grad_out, void* stream);
 
 /* One whole optimisation step (trainer/rbsolver.py:29-43) as a chain of 3 launches (vertex + raster records; jobs, which
- * resolve themselves; composite + finish.  Two more -- the general-triangle pass for jobs with a triangle that crosses the
- * near plane or is wider than 512 pixels, and the resolve kernel of what it redrew -- join the chain once a step has needed them: that step is reported as NaN like an overflow -- loss,
+ * resolve themselves; composite + finish.  A fourth -- the general-triangle pass for jobs with a triangle that crosses the
+ * near plane or is wider than 512 pixels -- joins the chain once a step has needed it: that step is reported as NaN like an overflow -- loss,
  * gradient NaN, optimiser state untouched --, ehr_fused_status() then returns EHR_ERR_RETRY and switches the pass on for
  * the context's later calls; run the step again, and re-capture the chain if it was captured in a graph.  A robot in
  * front of the camera never has such a triangle; the stateless ehr_render_mask_loss always launches the pass):

@@ -14,7 +14,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHAIN = ["vb_vertex_kernel", "vb_job_kernel", "vb_slow_kernel", "vb_resolve_kernel", "vb_composite_kernel"]
+CHAIN = ["vb_vertex_kernel", "vb_job_kernel", "vb_slow_kernel", "vb_composite_kernel"]
 DOMINANT = "vb_job_kernel"
 
 
