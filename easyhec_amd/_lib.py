@@ -56,6 +56,9 @@ SIGNATURES = {
                               c_float, c_void_p, c_void_p, c_void_p]),
     "ehr_solver_step": (c_int, [c_void_p] * 9 + [c_int] * 6 + [c_float] * 2 + [c_void_p] * 5 + [c_int, c_void_p] +
                         [c_float] * 5 + [c_void_p] * 8 + [c_int, c_void_p]),
+    "ehr_solver_step_multi": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float] * 2 + [c_void_p] * 5 + [c_int, c_void_p] +
+                              [c_float] * 5 + [c_void_p] * 8 + [c_void_p]),
+    "ehr_fused_bind_ref_shared": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_mask_variance": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_comm_unique_id": (c_int, [c_void_p]),
     "ehr_comm_init": (c_int, [c_void_p, c_void_p, c_int, c_int]),
@@ -89,6 +92,15 @@ def lib():
             fn.argtypes = args
         _lib = l
     return _lib
+
+
+def has_multistart():
+    """True if the library has the multi-start step (``ehr_solver_step_multi``).  The ABI version did not change with it:
+    the symbol's presence is the capability check (looked up on the bare library, so it also answers for an ``EHR_LIB``
+    build that predates it, which :func:`lib` would refuse to bind)."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_solver_step_multi")
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

@@ -53,14 +53,14 @@ int ehr_fused_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
 static int fused_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
                        const int32_t* vert_link, const int32_t* opp, float* mvp, const float* ref, int B, int L, int V,
                        int T, int H, int W, float* mask, float* loss, float* grad_mvp, const StepHead* head,
-                       const StepTail* tail, void* stream_) {
+                       const StepTail* tail, void* stream_, int multi_views = 0) {
     if (!ctx) return fail(EHR_ERR_INVALID, "fused op: ctx is NULL");
     if (!verts || !tris || !tri_link || !vert_link || !opp || !mvp || !ref || !loss)
         return fail(EHR_ERR_INVALID, "fused op: NULL tensor");
     if (ctx->pB != B || ctx->pL != L || ctx->pV != V || ctx->pT != T || ctx->pH != H || ctx->pW != W)
         return fail(EHR_ERR_INVALID, "fused op: shape differs from the planned one; call ehr_fused_plan first");
     return vbuf_chain(ctx, verts, tris, vert_link, opp, mvp, ref, B, L, V, T, H, W, mask, loss, grad_mvp, head,
-                      tail, (hipStream_t)stream_);
+                      tail, (hipStream_t)stream_, multi_views);
 }
 
 int ehr_render_mask_loss(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
@@ -93,6 +93,8 @@ int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     head.f = far_;
     head.adam_step = step;
     head.hstate = (int*)ctx->vb_hstate.ptr;
+    head.view0 = 0;
+    head.nviews = B;
     StepTail tail;
     tail.K = K;
     tail.link_poses = link_poses;
@@ -116,7 +118,64 @@ int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
                        &head, &tail, stream);
 }
 
+int ehr_solver_step_multi(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
+                          const int32_t* vert_link, const int32_t* opp, const float* K, const float* link_poses,
+                          const float* ref, int P, int Bv, int L, int V, int T, int H, int W, float near_, float far_,
+                          float* dof, float* adam_m, float* adam_v, int32_t* step, float* history, int history_rows,
+                          int32_t* history_row, float lr, float beta1, float beta2, float eps, float weight_decay,
+                          float* mvp, float* tc_jac, float* mask, float* loss_b, float* grad_mvp, float* red,
+                          float* loss_out, float* grad_out, void* stream) {
+    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: ctx is NULL");
+    if (!K || !link_poses || !dof || !adam_m || !adam_v || !step || !tc_jac || !grad_mvp || !red)
+        return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: NULL tensor");
+    if (P <= 0 || Bv <= 0 || (long long)P * Bv > 0x7fffffffll / 64)
+        return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: bad P x Bv");
+    if (L > MAX_LINKS) return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: more than %d links", MAX_LINKS);
+    if (history && !history_row) return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: history given without history_row");
+    if (ctx->pB != P * Bv || ctx->vb_hstate_m.cap < (size_t)VB_HSTATE_INTS * P * sizeof(int))
+        return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: call ehr_fused_plan for B = P x Bv = %d views first", P * Bv);
+    StepHead head;
+    head.dof = dof;
+    head.K = K;
+    head.link_poses = link_poses;
+    head.tc_jac = tc_jac;
+    head.hist_row = history_row;
+    head.history = history;
+    head.history_rows = history_rows;
+    head.n = near_;
+    head.f = far_;
+    head.adam_step = step;
+    head.hstate = (int*)ctx->vb_hstate_m.ptr;
+    head.view0 = 0;
+    head.nviews = Bv;
+    StepTail tail;
+    tail.K = K;
+    tail.link_poses = link_poses;
+    tail.tc_jac = tc_jac;
+    tail.red = red;
+    tail.dof = dof;
+    tail.m = adam_m;
+    tail.v = adam_v;
+    tail.step = step;
+    tail.loss_out = loss_out;
+    tail.grad_out = grad_out;
+    tail.n = near_;
+    tail.f = far_;
+    tail.lr = lr;
+    tail.b1 = beta1;
+    tail.b2 = beta2;
+    tail.eps = eps;
+    tail.wd = weight_decay;
+    tail.defer_adam = 0;
+    return fused_chain(ctx, verts, tris, tri_link, vert_link, opp, mvp, ref, P * Bv, L, V, T, H, W, mask, loss_b, grad_mvp,
+                       &head, &tail, stream, Bv);
+}
+
 int ehr_fused_bind_ref(ehr_ctx* ctx, const float* ref, void* stream) {
+    return ehr_fused_bind_ref_shared(ctx, ref, ctx ? ctx->pB : 0, stream);
+}
+
+int ehr_fused_bind_ref_shared(ehr_ctx* ctx, const float* ref, int Bv, void* stream) {
     if (!ctx) return fail(EHR_ERR_INVALID, "ehr_fused_bind_ref: ctx is NULL");
     if (ctx->capturing) return fail(EHR_ERR_INVALID, "ehr_fused_bind_ref: not inside a graph capture");
     // A captured chain has the bound-reference form (and the cached sums' pointers) baked into its kernel arguments: binding,
@@ -131,7 +190,7 @@ int ehr_fused_bind_ref(ehr_ctx* ctx, const float* ref, void* stream) {
         return EHR_OK;
     }
     if (ctx->pB == 0) return fail(EHR_ERR_INVALID, "ehr_fused_bind_ref: call ehr_fused_plan first");
-    return vbuf_bind_ref(ctx, ref, (hipStream_t)stream);
+    return vbuf_bind_ref(ctx, ref, Bv, (hipStream_t)stream);
 }
 
 int ehr_fused_status(ehr_ctx* ctx) {

@@ -212,6 +212,25 @@ struct StepHead {  // inputs of the merged first stage (pose forward inside the 
     // step with no host-side rewind (which had to guess which rows to give back).
     const int* adam_step;  // [1] the optimiser's step counter
     int* hstate;           // [2] ctx->vb_hstate
+    // Multi-start form only (ehr_solver_step_multi; vb_vertex_kernel<true, true>): the launch's view b is virtual view
+    // view0 + b = p * nviews + j, hypothesis p looking at real view j.  dof, tc_jac, hist_row, history, adam_step and
+    // hstate (VB_HSTATE_INTS apart) are then arrays over p; link_poses holds the nviews real views.
+    int view0, nviews;
+};
+constexpr int VB_HSTATE_INTS = 4;  // ints of head state per hypothesis: the three of StepHead::hstate, padded
+
+// What one workgroup per hypothesis needs to finish a multi-start step (vb_finish_multi_kernel): the per-hypothesis
+// arrays are those of StepTail, strided by hypothesis; the accumulators, loss_b and grad_mvp by virtual view.
+struct MultiFinish {
+    const long long* facc_all;  // accumulators of all P * Bv virtual views
+    const long long* vtot_all;  // bound reference: the cached totals, tiled per virtual view (or NULL)
+    const int* ref_flag;
+    float* loss;                // [P * Bv]
+    float* grad_mvp;            // [P * Bv][L][16]
+    int* meta;
+    int* lbox_all;              // the link boxes of all virtual views, re-armed here
+    int P, Bv, nls;
+    BinGeom g;
 };
 
 

@@ -64,12 +64,13 @@ struct RasterShape {  // what makes two drop-in rasterize calls "the same frame 
 int vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float slack, const float* verts,
               const int32_t* tris, const int32_t* tri_link, const int32_t* opp);
 int vbuf_meta_read(ehr_ctx* ctx, int* meta4);
-int vbuf_bind_ref(ehr_ctx* ctx, const float* ref, hipStream_t stream);
+int vbuf_bind_ref(ehr_ctx* ctx, const float* ref, int views, hipStream_t stream);
 int vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp, int Q, int S,
                int L, int V, int T, int H, int W, long long* score, unsigned char* count, hipStream_t stream, int* handled);
 int vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
                const int32_t* opp, float* mvp, const float* ref, int B, int L, int V, int T, int H, int W, float* mask,
-               float* loss, float* grad_mvp, const StepHead* head, const StepTail* tail, hipStream_t stream);
+               float* loss, float* grad_mvp, const StepHead* head, const StepTail* tail, hipStream_t stream,
+               int multi_views = 0);  // > 0: the multi-start step, B = P x multi_views virtual views (ehr_solver_step_multi)
 
 }  // namespace ehr
 
@@ -123,8 +124,12 @@ struct ehr_ctx {
     int vb_spill_cap = 0;    // ... in items
     ehr::Scratch vb_refsum;  // cached sums of the bound reference mask: tsum i64 [B][nt] | vtot i64 [B] | flag
     const float* vb_ref = nullptr;  // the reference mask those sums belong to (ehr_fused_bind_ref), or NULL
+    int vb_ref_views = 0;    // images `vb_ref` holds: pB, or fewer where hypotheses share them (ehr_fused_bind_ref_shared: the
+                             // sums are then tiled, view b's are those of image b % vb_ref_views)
     ehr::Scratch vb_hstate;  // i32 [16], survives re-plans: [0] Adam's step counter + 1 as the previous solver step's head saw
                              // it, [1] whether that head advanced the history cursor, [2] where it left it (a REPORTED step's row is reused)
+    ehr::Scratch vb_hstate_m;  // i32 [pB][VB_HSTATE_INTS]: the same per hypothesis of a multi-start step (ehr_solver_step_multi; kept
+                               // across re-plans that do not grow it)
     // space-explorer scoring (ehr_mask_variance) keeps its own scratch so that it never disturbs a solver plan
     ehr::Scratch sc_counts, sc_offsets, sc_entries, sc_posc;
     size_t sc_entries_cap = 0;
@@ -150,7 +155,7 @@ struct ehr_ctx {
     unsigned long long scratch_moves() const {
         unsigned long long n = 0;
         for (const ehr::Scratch* s : {&counts, &offsets, &entries, &vb_clus, &vb_heavy, &vb_idx, &vb_boxes, &vb_units, &vb_acc,
-                                      &vb_posc, &vb_jobs, &vb_spill, &vb_refsum, &vb_hstate, &sc_counts, &sc_offsets, &sc_entries, &sc_posc, &sc_clus, &sc_misc})
+                                      &vb_posc, &vb_jobs, &vb_spill, &vb_refsum, &vb_hstate, &vb_hstate_m, &sc_counts, &sc_offsets, &sc_entries, &sc_posc, &sc_clus, &sc_misc})
             n += s->moves;
         return n;
     }

@@ -560,6 +560,7 @@ int ehr_ctx_destroy(ehr_ctx* c) {
     c->vb_units.release();
     c->vb_refsum.release();
     c->vb_hstate.release();
+    c->vb_hstate_m.release();
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++)
@@ -575,7 +576,7 @@ size_t ehr_ctx_scratch_bytes(ehr_ctx* c) {
     if (!c) return 0;
     size_t n = 0;
     for (const Scratch* s : {&c->counts, &c->ranges, &c->rkeys, &c->offsets, &c->entries, &c->vb_clus, &c->vb_heavy, &c->vb_idx, &c->vb_boxes, &c->vb_units,
-                             &c->vb_acc, &c->vb_posc, &c->vb_jobs, &c->vb_spill, &c->vb_refsum, &c->vb_hstate, &c->sc_counts, &c->sc_offsets,
+                             &c->vb_acc, &c->vb_posc, &c->vb_jobs, &c->vb_spill, &c->vb_refsum, &c->vb_hstate, &c->vb_hstate_m, &c->sc_counts, &c->sc_offsets,
                              &c->sc_entries, &c->sc_posc, &c->sc_clus, &c->sc_misc})
         n += s->cap;
     return n;

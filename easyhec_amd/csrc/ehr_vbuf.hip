@@ -365,7 +365,10 @@ enum VbRole {
     VB_ROLE_CHUNK_MASK = 3,
     VB_ROLE_POS_ONLY = 4,     // flag: the scoring op's chain (depth class "coverage decides")
 };
-template <bool HEAD>
+// MULTI (with HEAD): the multi-start step -- view b of the launch is virtual view head.view0 + b = p * head.nviews + j:
+// hypothesis p's pose (dof[p]) on real view j's link poses; the first workgroup of every hypothesis's first view writes
+// that hypothesis's tc_jac, history row and head state.  The step-wide housekeeping stays with the call's first workgroup.
+template <bool HEAD, bool MULTI = false>
 __global__ void __launch_bounds__(256, VB_VERTEX_WAVES)
 vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ vert_link,
                  const int32_t* __restrict__ tris, VbClusters cl, StepHead head, float* __restrict__ mvp, int V, int nvb,
@@ -390,6 +393,14 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
     chunk_role &= VB_ROLE_CHUNK_MASK;
     const bool first = bx == 0 && b == 0 && chunk_role == VB_ROLE_FIRST_CHUNK;
     const bool rearm = bx == 0 && b == 0 && chunk_role == VB_ROLE_LATER_CHUNK;
+    int hyp = 0, bview = b;  // MULTI: the hypothesis of this view and the real view it looks at
+    if (MULTI) {
+        const int bg = head.view0 + b;
+        hyp = bg / head.nviews;
+        bview = bg - hyp * head.nviews;
+        head.dof += 6 * hyp;
+    }
+    const bool first_head = MULTI ? (bx == 0 && bview == 0) : first;  // writes tc_jac, the history row and the head state
     // A view's work items: [0, nvb) blocks of 256 vertices (-> posc; nvb = 0 where the plan computes clip-space vertices on
     // demand, see VbLazy), then groups of four clusters (one wave per cluster, one lane per triangle).  The workgroup takes items bx, bx + gx, ...: the pose head above every item (exponential,
     // matrices: ~3 us of dependent arithmetic) is paid once per workgroup, not once per 256 vertices -- with one item per
@@ -445,7 +456,7 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
         float kv = 0.f;
 #pragma unroll
         for (int j = 0; j < 2; j++)
-            if (tid + 256 * j < L * 16) lpv[j] = head.link_poses[(size_t)b * L * 16 + tid + 256 * j];
+            if (tid + 256 * j < L * 16) lpv[j] = head.link_poses[(size_t)bview * L * 16 + tid + 256 * j];
         if (tid >= 64 && tid < 73) kv = head.K[tid - 64];
 #pragma unroll
         for (int j = 0; j < 2; j++)
@@ -457,7 +468,16 @@ vb_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ ve
         se3_exp_dual<1>(dofv, 1e-4f, T6, tid);
         if (tid == 0)
             for (int i = 0; i < 16; i++) Tc[i] = T6[i].v;
-        if (first) {
+        if (first_head) {
+            if (MULTI) {
+                head.tc_jac += 7 * 16 * hyp;
+                if (head.history && head.hist_row) {
+                    head.hist_row += hyp;
+                    head.history += (size_t)hyp * head.history_rows * 6;
+                }
+                head.adam_step += hyp;
+                head.hstate += VB_HSTATE_INTS * hyp;
+            }
             for (int i = 0; i < 16; i++) {
                 if (tid == 0) head.tc_jac[i] = T6[i].v;
                 head.tc_jac[16 * (tid + 1) + i] = T6[i].d[0];
@@ -1769,9 +1789,15 @@ struct VbCompArgs {
 
 // The composite stage's work items of ONE wave (slot `wslot` of the `nslots` wave slots its XCD has; `nwg` workgroups in
 // all): see vb_composite_kernel.  s_jbase / s_utile: the (view, link) tables in LDS; gpix: 256 floats of LDS of this wave.
-template <bool FILL>
+// SHARED (the multi-start step): the chunk's view b is virtual view sh.view0 + b and compares with real view
+// (sh.view0 + b) % sh.nviews of `ref` (which then holds sh.nviews images, passed whole); masks, sums and the bound
+// reference's cached sums stay per virtual view.
+struct VbSharedRef {
+    int view0, nviews;
+};
+template <bool FILL, bool SHARED = false>
 __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const int* s_jbase, const unsigned* s_utile, float* gpix,
-                                                   int xcd, int wslot, int nslots, int nwg) {
+                                                   int xcd, int wslot, int nslots, int nwg, VbSharedRef sh = {0, 1}) {
     const BinGeom& g = C.g;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const int W = g.W, H = g.H, L = g.L, B = C.B, U = B * L;
@@ -1863,19 +1889,20 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     const int ix = tx * EHR_TILE_W + c4, iy = ty * EHR_TILE_H + r;  // first of my 4 pixels (GL rows: y up)
     const bool row_in = iy < H;
     const size_t im = ((size_t)b * H + (H - 1 - (row_in ? iy : 0))) * W + ix;  // image convention: row 0 = top
+    const size_t imr = SHARED ? ((size_t)((sh.view0 + b) % sh.nviews) * H + (H - 1 - (row_in ? iy : 0))) * W + ix : im;
     float rf[4] = {0.f, 0.f, 0.f, 0.f};
     bool pin[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) pin[j] = row_in && (ix + j) < W;
     if (vec_ok) {
         if (pin[0]) {
-            const float4 r4 = *reinterpret_cast<const float4*>(ref + im);
+            const float4 r4 = *reinterpret_cast<const float4*>(ref + imr);
             rf[0] = r4.x; rf[1] = r4.y; rf[2] = r4.z; rf[3] = r4.w;
         }
     } else {
 #pragma unroll
         for (int j = 0; j < 4; j++)
-            if (pin[j]) rf[j] = ref[im + j];
+            if (pin[j]) rf[j] = ref[imr + j];
     }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     unsigned todo = tmask;
@@ -2521,9 +2548,9 @@ __device__ __forceinline__ int vb_comp_arrivals(int xcd, int per, int nitems, in
 //                 the tiles outside every rectangle are then filled with zeros (stores only, no reference read, no sums).
 // One designated workgroup of the call's last launch (the finisher, see below) runs the finish stage: accumulators ->
 // loss / grad_mvp [-> pose backward -> Adam]; the launch also re-arms the link boxes.  vec_ok: W % 4 == 0 and 16-byte aligned images.
-template <bool TAIL, bool FILL>
+template <bool TAIL, bool FILL, bool SHARED = false>
 __global__ void __launch_bounds__(256, FILL ? 5 : 6)
-vb_composite_kernel(VbCompArgs C, StepTail tail) {
+vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh) {
     __shared__ float gpix_all[4][EHR_TILE_W * EHR_TILE_H];
     extern __shared__ int s_dyn[];  // [U + 1] first job of every (view, link) | [U] its tile range
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2542,7 +2569,7 @@ vb_composite_kernel(VbCompArgs C, StepTail tail) {
             C.lbox_all[i] = (i & 2) ? INT_MIN : INT_MAX;  // one line per box: min x, min y, max x, max y, padding
     __syncthreads();
     const int nwg = gridDim.x, xcd = blockIdx.x & (VB_XCDS - 1);
-    vb_composite_items<FILL>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> VB_XCD_BITS) * 4 + wave, (nwg >> VB_XCD_BITS) * 4, nwg);
+    vb_composite_items<FILL, SHARED>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> VB_XCD_BITS) * 4 + wave, (nwg >> VB_XCD_BITS) * 4, nwg, sh);
     // ---- the finish stage: ONE designated workgroup, the finisher, runs it once every other workgroup's atomics have
     //      been performed.  A workgroup that had work waits for its own atomics (vmcnt covers them), then one lane adds 1
     //      to its XCD's arrival counter -- no value comes back, nobody waits for one -- and the workgroup is done.  A
@@ -2605,6 +2632,39 @@ vb_composite_kernel(VbCompArgs C, StepTail tail) {
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     finish_reduce<TAIL>(pre, g, Q->C.B_all, Q->C.facc_all, vtot, Q->C.loss, Q->C.grad_mvp, Q->C.meta, tl, Q->C.nls, VB_LOSS_STRIDE, S, red_lds, Js, gpix_all[0]);
+}
+
+// The finish stage of a multi-start step (ehr_solver_step_multi): ONE WORKGROUP PER HYPOTHESIS, a launch of its own behind
+// the call's last composite launch (which then has no finisher).  Workgroup p runs finish_prefetch / finish_reduce<TAIL> --
+// the bodies the single-pose finisher runs -- on hypothesis p's Bv views and state, so its sums are the expression tree of
+// a solo step with B = Bv, bit for bit, and the P accumulate -> reduce -> Adam chains run side by side.  The overflow word
+// is the step's: a reported step freezes every hypothesis.  Also re-arms the link boxes (the composite launch's job
+// where it finishes).
+__global__ void __launch_bounds__(256)
+vb_finish_multi_kernel(MultiFinish A, StepTail tail) {
+    __shared__ double S[4][17];
+    __shared__ float red_lds[8];
+    __shared__ float Js[6][16];
+    __shared__ float lp_lds[1024];
+    const int p = blockIdx.x, tid = threadIdx.x, L = A.g.L;
+    for (int i = p * 256 + tid; i < VB_LBOX_STRIDE * A.P * A.Bv * L; i += (int)gridDim.x * 256)
+        A.lbox_all[i] = (i & 2) ? INT_MIN : INT_MAX;
+    tail.tc_jac += 7 * 16 * p;
+    tail.red += 8 * p;
+    tail.dof += 6 * p;
+    tail.m += 6 * p;
+    tail.v += 6 * p;
+    tail.step += p;
+    if (tail.loss_out) tail.loss_out += p;
+    if (tail.grad_out) tail.grad_out += 6 * p;
+    const size_t v0 = (size_t)p * A.Bv;
+    const long long* const vtot = A.vtot_all ? A.vtot_all + v0 : nullptr;
+    FinishPre pre;
+    finish_prefetch<true>(pre, A.g, A.Bv, vtot, tail, A.nls, Js, lp_lds);
+    if (A.ref_flag && tid == 0 && A.ref_flag[0]) atomicOr(&A.meta[EHR_META_OVERFLOW], 1);  // the bound reference's own sums overflowed
+    __syncthreads();
+    finish_reduce<true>(pre, A.g, A.Bv, A.facc_all + v0 * vb_acc_stride(L, A.nls), vtot, A.loss + v0,
+                        A.grad_mvp + v0 * L * 16, A.meta, tail, A.nls, VB_LOSS_STRIDE, S, red_lds, Js, lp_lds);
 }
 
 // Content hash of the scoring op's mesh arrays: the cluster index holds copies of the vertex positions, so a mesh edited
@@ -2952,6 +3012,10 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
         if ((rc = ctx->vb_hstate.reserve(16 * sizeof(int)))) return rc;
         EHR_HIP(hipMemset(ctx->vb_hstate.ptr, 0, 16 * sizeof(int)));
     }
+    if (ctx->vb_hstate_m.cap < (size_t)VB_HSTATE_INTS * B * sizeof(int)) {  // (likewise: only a larger plan starts it afresh)
+        if ((rc = ctx->vb_hstate_m.reserve((size_t)VB_HSTATE_INTS * B * sizeof(int)))) return rc;
+        EHR_HIP(hipMemset(ctx->vb_hstate_m.ptr, 0, ctx->vb_hstate_m.cap));
+    }
     ctx->vb_plan_tris = tris;
     ctx->vb_plan_opp = opp;
     ctx->vb_plan_verts = verts;
@@ -2970,7 +3034,8 @@ int ehr::vbuf_meta_read(ehr_ctx* ctx, int* meta4) {
 
 int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const int32_t* opp, float* mvp, const float* ref, int B, int L, int V,
                     int T, int H, int W, float* mask, float* loss, float* grad_mvp, const StepHead* head,
-                    const StepTail* tail, hipStream_t stream) {
+                    const StepTail* tail, hipStream_t stream, int multi_views) {
+    const bool multi = multi_views > 0;  // B = P x multi_views virtual views; ref and head->link_poses hold multi_views real ones
     if (tris != ctx->vb_plan_tris || opp != ctx->vb_plan_opp || verts != ctx->vb_plan_verts)
         return fail(EHR_ERR_INVALID, "fused op: the scene arrays differ from the planned ones; call ehr_fused_plan again");
     BinGeom g = make_geom(H, W, L);
@@ -3001,7 +3066,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     hv.mcap = std::min(VB_MED_CAP, 2 * job_wgs);
     hv.heavy_base = VB_HEAVY_T_DEFAULT;
     hv.heavy_max = job_wgs / 2;
-    const bool sparse = ctx->vb_ref != nullptr && ctx->vb_ref == ref;
+    const bool sparse = ctx->vb_ref != nullptr && ctx->vb_ref == ref && ctx->vb_ref_views == (multi ? multi_views : B);
     const long long* const tsum_all = sparse ? (const long long*)ctx->vb_refsum.ptr : nullptr;
     const long long* const vtot_all = sparse ? tsum_all + (size_t)B * g.nt : nullptr;
     const int* const ref_flag = sparse ? (const int*)(vtot_all + B) : nullptr;
@@ -3020,7 +3085,7 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         long long* facc = facc_all + (size_t)b0 * acc_stride;
         int* lbox = lbox_all + (size_t)VB_LBOX_STRIDE * b0 * L;
         float* mvp_k = mvp + (size_t)b0 * L * 16;
-        const float* ref_k = ref + (size_t)b0 * H * W;
+        const float* ref_k = multi ? ref : ref + (size_t)b0 * H * W;  // (multi: the real views, indexed by VbSharedRef)
         float* mask_k = mask ? mask + (size_t)b0 * H * W : nullptr;
         const VbRecs recs = vb_recs(ctx->vb_boxes.ptr, Bk, NC1);
         // stage 0: [pose forward] + vertices + screen boxes
@@ -3028,7 +3093,13 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         const dim3 vgrid(vg.gx * Bk);
         const int nacc_ints = 2 * Bk * acc_stride;
         const int role = first_chunk ? VB_ROLE_FIRST_CHUNK : VB_ROLE_LATER_CHUNK;
-        if (head) {
+        if (head && multi) {
+            StepHead hk = *head;
+            hk.view0 = b0;
+            hk.nviews = multi_views;
+            vb_vertex_kernel<true, true><<<vgrid, 256, 0, stream>>>(verts, vert_link, tris, cl, hk, mvp_k, V, nvb, g, posc, recs, lbox,
+                                                                   (int*)facc, nacc_ints, meta, Bk, vg.gx, vg.xcd_views, hv, role);
+        } else if (head) {
             StepHead hk = *head;
             hk.link_poses = head->link_poses + (size_t)b0 * L * 16;
             vb_vertex_kernel<true><<<vgrid, 256, 0, stream>>>(verts, vert_link, tris, cl, hk, mvp_k, V, nvb, g, posc, recs, lbox,
@@ -3086,10 +3157,16 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         ca.meta = meta;
         ca.tsum = sparse ? tsum_all + (size_t)b0 * g.nt : nullptr;
         ca.ref_flag = ref_flag; ca.loss = loss; ca.grad_mvp = grad_mvp;
-        ca.do_finish = last_chunk ? 1 : 0; ca.B_all = B; ca.facc_all = facc_all; ca.vtot_all = vtot_all; ca.lbox_all = lbox_all;
-#define VB_COMPOSITE(TAILV, FILLV, tailarg) vb_composite_kernel<TAILV, FILLV><<<nwg, 256, dyn, stream>>>(ca, tailarg)
+        ca.do_finish = (last_chunk && !multi) ? 1 : 0; ca.B_all = B; ca.facc_all = facc_all; ca.vtot_all = vtot_all; ca.lbox_all = lbox_all;
+#define VB_COMPOSITE(TAILV, FILLV, tailarg) vb_composite_kernel<TAILV, FILLV><<<nwg, 256, dyn, stream>>>(ca, tailarg, VbSharedRef{0, 1})
         StepTail none = {};
-        if (tail) {
+        if (multi) {  // (no finisher: vb_finish_multi_kernel follows the last chunk)
+            const VbSharedRef sh = {b0, multi_views};
+            if (fill)
+                vb_composite_kernel<false, true, true><<<nwg, 256, dyn, stream>>>(ca, none, sh);
+            else
+                vb_composite_kernel<false, false, true><<<nwg, 256, dyn, stream>>>(ca, none, sh);
+        } else if (tail) {
             if (fill) VB_COMPOSITE(true, true, *tail); else VB_COMPOSITE(true, false, *tail);
         } else {
             if (fill) VB_COMPOSITE(false, true, none); else VB_COMPOSITE(false, false, none);
@@ -3097,8 +3174,16 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
 #undef VB_COMPOSITE
         EHR_LAUNCH_CHECK();
     }
+    if (ev) EHR_HIP(hipEventRecord(ev[5], stream));
+    if (multi) {  // the finish stage, one workgroup per hypothesis (ms[5] of the timing ABI)
+        MultiFinish mf;
+        mf.facc_all = facc_all; mf.vtot_all = vtot_all; mf.ref_flag = ref_flag; mf.loss = loss; mf.grad_mvp = grad_mvp;
+        mf.meta = meta; mf.lbox_all = lbox_all; mf.P = B / multi_views; mf.Bv = multi_views; mf.nls = VB_LOSS_SLOTS; mf.g = g;
+        vb_finish_multi_kernel<<<mf.P, 256, 0, stream>>>(mf, *tail);
+        EHR_LAUNCH_CHECK();
+    }
     if (ev) {
-        for (int k = 5; k <= 7; k++) EHR_HIP(hipEventRecord(ev[k], stream));
+        for (int k = 6; k <= 7; k++) EHR_HIP(hipEventRecord(ev[k], stream));
     }
     return EHR_OK;
 }
@@ -3250,18 +3335,25 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
 
 // Binds a reference mask to the plan (ehr_fused_bind_ref): one pass stores per (view, tile) the fixed-point sum(ref^2)
 // exactly as the composite kernel would add it for a tile no link touches, and per view the total.  ref == NULL unbinds.
-int ehr::vbuf_bind_ref(ehr_ctx* ctx, const float* ref, hipStream_t stream) {
+// views < B (ehr_fused_bind_ref_shared): ref holds `views` images which the plan's B = P x views virtual views share; the
+// sums are TILED -- computed once per hypothesis into the layout of a B-view reference -- so that every reader indexes
+// them by virtual view like any others (9.6 KB per 640x480 view).
+int ehr::vbuf_bind_ref(ehr_ctx* ctx, const float* ref, int views, hipStream_t stream) {
     ctx->vb_ref = nullptr;
     if (!ref) return EHR_OK;
     const int B = ctx->pB, H = ctx->pH, W = ctx->pW;
+    if (views <= 0 || B % views != 0) return fail(EHR_ERR_INVALID, "ehr_fused_bind_ref: the plan's %d views are not a multiple of %d", B, views);
     BinGeom g = make_geom(H, W, ctx->pL);
     long long* tsum = (long long*)ctx->vb_refsum.ptr;
     long long* vtot = tsum + (size_t)B * g.nt;
     EHR_HIP(hipMemsetAsync(vtot, 0, ((size_t)B + 1) * sizeof(long long), stream));
     const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0);
-    const int nw = B * g.nt;
-    vb_refsum_kernel<<<(nw + 3) / 4, 256, 0, stream>>>(g, B, ref, vec_ok, tsum, vtot, (int*)(vtot + B));
-    EHR_LAUNCH_CHECK();
+    const int nw = views * g.nt;
+    for (int b0 = 0; b0 < B; b0 += views) {
+        vb_refsum_kernel<<<(nw + 3) / 4, 256, 0, stream>>>(g, views, ref, vec_ok, tsum + (size_t)b0 * g.nt, vtot + b0, (int*)(vtot + B));
+        EHR_LAUNCH_CHECK();
+    }
     ctx->vb_ref = ref;
+    ctx->vb_ref_views = views;
     return EHR_OK;
 }

@@ -166,6 +166,11 @@ int ehr_fused_status(ehr_ctx* ctx); /* synchronises the device; 0, EHR_ERR_OVERF
  * ehr_fused_plan unbinds.  Calls with another pointer take the unbound path.  Enqueues on `stream`; not to be called
  * inside a graph capture. */
 int ehr_fused_bind_ref(ehr_ctx* ctx, const float* ref, void* stream);
+/* The same for a plan whose B = P x Bv views are P hypotheses looking at the SAME Bv images (ehr_solver_step_multi): ref
+ * [Bv,H,W] is read P times by this call and never copied; the cached sums (a few KB per view) are stored once per
+ * hypothesis, so that view p * Bv + j finds those of image j under its own index.  Bv must divide the planned B;
+ * Bv == B is ehr_fused_bind_ref.  A step only takes the bound path when it passes this pointer AND shares it the same way. */
+int ehr_fused_bind_ref_shared(ehr_ctx* ctx, const float* ref, int Bv, void* stream);
 
 /* Measurement hook (bench.py's roofline leg): when enabled, every ehr_render_mask_loss / ehr_solver_step call records
  * hipEvents around its kernels on the launch stream.  ehr_fused_timing_read synchronises, writes the ACCUMULATED
@@ -228,6 +233,38 @@ int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
                     int32_t* history_row, float lr, float beta1, float beta2, float eps, float weight_decay, float* mvp,
                     float* tc_jac, float* mask, float* loss_b, float* grad_mvp, float* red, float* loss_out,
                     float* grad_out, int defer_adam, void* stream);
+
+/* Multi-start solve: P hypotheses (start poses) of ONE problem of Bv views advance by one optimisation step each, in one
+ * launch chain whose length does not depend on P.  Hypothesis p on real view j is virtual view b = p * Bv + j of a
+ * P x Bv-view plan (ehr_fused_plan with B = P * Bv; chunked like any other call):
+ *     K [9], link_poses [Bv,L,16], ref [Bv,H,W]          passed ONCE, shared: view b reads real view b % Bv, no copies;
+ *     dof, adam_m, adam_v [P,6], step [P], history [P,history_rows,6] (may be NULL), history_row [P]   per hypothesis;
+ *     mvp, grad_mvp [P*Bv,L,16], loss_b [P*Bv], mask [P*Bv,H,W] (may be NULL)                           per virtual view;
+ *     tc_jac [P,7,16], red [P,8], loss_out [P], grad_out [P,6] (may be NULL)                            per hypothesis.
+ * The chain is ehr_solver_step's -- vertex kernel (its head reads dof[p]; the first workgroup of every hypothesis's first
+ * view writes that hypothesis's tc_jac and history row), jobs, [general-triangle pass], composite -- followed by ONE more
+ * small launch with a workgroup per hypothesis that runs the finish stage (accumulators -> loss_b / grad_mvp -> pose
+ * backward -> Adam) on that hypothesis's Bv views: 4 launches, 5 with the general-triangle pass.  Within a hypothesis every
+ * sum is the expression tree of ehr_solver_step with B = Bv, so hypothesis p's outputs and state equal, bit for bit,
+ * those of a solo solve from start p.
+ * Failure semantics.  A hypothesis whose own red[p] is not finite is frozen like a reported solo step (dof, moments, step
+ * untouched, loss_out[p] = NaN); the others proceed.  The capacity conditions -- job slots, the spill pool, the
+ * general-triangle pass switching on, the accumulator range flag -- are STEP-WIDE: the step is reported for every
+ * hypothesis (all NaN, all states untouched, every history row reused by the next call) and recovered as for
+ * ehr_solver_step (ehr_fused_status; plan again / call again, re-capture a graph).  Known limitation: the accumulator
+ * range flag is one word, so one hypothesis whose sums leave +-2^31 reports the step for all; Adam moves a coordinate by
+ * at most lr per step, so a hypothesis cannot run away within a solve.
+ * Works with ehr_fused_bind_ref_shared, ehr_fused_status, ehr_graph_* and ehr_fused_timing (ms[4] is the composite launch,
+ * ms[5] the finish launch) like ehr_solver_step; never synchronises or allocates.  There is no defer_adam: the
+ * data-parallel exchange of hypotheses is out of scope.  ehr_version() is unchanged: the presence of this symbol is the
+ * capability check. */
+int ehr_solver_step_multi(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
+                          const int32_t* vert_link, const int32_t* opp, const float* K, const float* link_poses,
+                          const float* ref, int P, int Bv, int L, int V, int T, int H, int W, float near_plane,
+                          float far_plane, float* dof, float* adam_m, float* adam_v, int32_t* step, float* history,
+                          int history_rows, int32_t* history_row, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, float* mvp, float* tc_jac, float* mask, float* loss_b, float* grad_mvp,
+                          float* red, float* loss_out, float* grad_out, void* stream);
 
 /* The data-parallel exchange (replaces the DDP gradient all-reduce of trainer/base.py:349-352 under the
  * one-process-per-GPU launch of tools/run_easyhec.py:41-50).  Views shard over the ranks; per step every rank runs
