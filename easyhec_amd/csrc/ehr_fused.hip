@@ -70,18 +70,19 @@ int ehr_render_mask_loss(ehr_ctx* ctx, const float* verts, const int32_t* tris, 
                        loss, grad_mvp, nullptr, nullptr, stream);
 }
 
-int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
-                    const int32_t* vert_link, const int32_t* opp, const float* K, const float* link_poses,
-                    const float* ref, int B, int L, int V, int T, int H, int W, float near_, float far_, float* dof,
-                    float* adam_m, float* adam_v, int32_t* step, float* history, int history_rows, int32_t* history_row,
-                    float lr, float beta1,
-                    float beta2, float eps, float weight_decay, float* mvp, float* tc_jac, float* mask, float* loss_b,
-                    float* grad_mvp, float* red, float* loss_out, float* grad_out, int defer_adam, void* stream) {
+// What ehr_solver_step and ehr_solver_step_multi share: the checks on their common arguments, and the head and tail of the
+// solver-step form.  `who` is the entry point's name (for messages); they differ in the context's head-state buffer, in how
+// many views one pose owns and in whether Adam is left to the caller.
+static int step_head_tail(const char* who, ehr_ctx* ctx, ehr::Scratch ehr_ctx::*hstate, int nviews, int defer_adam,
+                          int L, const float* K, const float* link_poses, float near_, float far_, float* dof, float* adam_m,
+                          float* adam_v, int32_t* step, float* history, int history_rows, int32_t* history_row, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, float* tc_jac, const float* grad_mvp,
+                          float* red, float* loss_out, float* grad_out, StepHead& head, StepTail& tail) {
+    if (!ctx) return fail(EHR_ERR_INVALID, "%s: ctx is NULL", who);
     if (!K || !link_poses || !dof || !adam_m || !adam_v || !step || !tc_jac || !grad_mvp || !red)
-        return fail(EHR_ERR_INVALID, "ehr_solver_step: NULL tensor");
-    if (L > MAX_LINKS) return fail(EHR_ERR_INVALID, "ehr_solver_step: more than %d links", MAX_LINKS);
-    if (history && !history_row) return fail(EHR_ERR_INVALID, "ehr_solver_step: history given without history_row");
-    StepHead head;
+        return fail(EHR_ERR_INVALID, "%s: NULL tensor", who);
+    if (L > MAX_LINKS) return fail(EHR_ERR_INVALID, "%s: more than %d links", who, MAX_LINKS);
+    if (history && !history_row) return fail(EHR_ERR_INVALID, "%s: history given without history_row", who);
     head.dof = dof;
     head.K = K;
     head.link_poses = link_poses;
@@ -92,10 +93,9 @@ int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     head.n = near_;
     head.f = far_;
     head.adam_step = step;
-    head.hstate = (int*)ctx->vb_hstate.ptr;
+    head.hstate = (int*)(ctx->*hstate).ptr;
     head.view0 = 0;
-    head.nviews = B;
-    StepTail tail;
+    head.nviews = nviews;
     tail.K = K;
     tail.link_poses = link_poses;
     tail.tc_jac = tc_jac;
@@ -114,6 +114,22 @@ int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     tail.eps = eps;
     tail.wd = weight_decay;
     tail.defer_adam = defer_adam;
+    return EHR_OK;
+}
+
+int ehr_solver_step(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
+                    const int32_t* vert_link, const int32_t* opp, const float* K, const float* link_poses,
+                    const float* ref, int B, int L, int V, int T, int H, int W, float near_, float far_, float* dof,
+                    float* adam_m, float* adam_v, int32_t* step, float* history, int history_rows, int32_t* history_row,
+                    float lr, float beta1,
+                    float beta2, float eps, float weight_decay, float* mvp, float* tc_jac, float* mask, float* loss_b,
+                    float* grad_mvp, float* red, float* loss_out, float* grad_out, int defer_adam, void* stream) {
+    StepHead head;
+    StepTail tail;
+    int rc = step_head_tail("ehr_solver_step", ctx, &ehr_ctx::vb_hstate, B, defer_adam, L, K, link_poses, near_, far_, dof,
+                            adam_m, adam_v, step, history, history_rows, history_row, lr, beta1, beta2, eps, weight_decay,
+                            tc_jac, grad_mvp, red, loss_out, grad_out, head, tail);
+    if (rc) return rc;
     return fused_chain(ctx, verts, tris, tri_link, vert_link, opp, mvp, ref, B, L, V, T, H, W, mask, loss_b, grad_mvp,
                        &head, &tail, stream);
 }
@@ -125,48 +141,16 @@ int ehr_solver_step_multi(ehr_ctx* ctx, const float* verts, const int32_t* tris,
                           int32_t* history_row, float lr, float beta1, float beta2, float eps, float weight_decay,
                           float* mvp, float* tc_jac, float* mask, float* loss_b, float* grad_mvp, float* red,
                           float* loss_out, float* grad_out, void* stream) {
-    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: ctx is NULL");
-    if (!K || !link_poses || !dof || !adam_m || !adam_v || !step || !tc_jac || !grad_mvp || !red)
-        return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: NULL tensor");
+    StepHead head;
+    StepTail tail;
+    int rc = step_head_tail("ehr_solver_step_multi", ctx, &ehr_ctx::vb_hstate_m, Bv, 0, L, K, link_poses, near_, far_, dof,
+                            adam_m, adam_v, step, history, history_rows, history_row, lr, beta1, beta2, eps, weight_decay,
+                            tc_jac, grad_mvp, red, loss_out, grad_out, head, tail);
+    if (rc) return rc;
     if (P <= 0 || Bv <= 0 || (long long)P * Bv > 0x7fffffffll / 64)
         return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: bad P x Bv");
-    if (L > MAX_LINKS) return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: more than %d links", MAX_LINKS);
-    if (history && !history_row) return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: history given without history_row");
     if (ctx->pB != P * Bv || ctx->vb_hstate_m.cap < (size_t)VB_HSTATE_INTS * P * sizeof(int))
         return fail(EHR_ERR_INVALID, "ehr_solver_step_multi: call ehr_fused_plan for B = P x Bv = %d views first", P * Bv);
-    StepHead head;
-    head.dof = dof;
-    head.K = K;
-    head.link_poses = link_poses;
-    head.tc_jac = tc_jac;
-    head.hist_row = history_row;
-    head.history = history;
-    head.history_rows = history_rows;
-    head.n = near_;
-    head.f = far_;
-    head.adam_step = step;
-    head.hstate = (int*)ctx->vb_hstate_m.ptr;
-    head.view0 = 0;
-    head.nviews = Bv;
-    StepTail tail;
-    tail.K = K;
-    tail.link_poses = link_poses;
-    tail.tc_jac = tc_jac;
-    tail.red = red;
-    tail.dof = dof;
-    tail.m = adam_m;
-    tail.v = adam_v;
-    tail.step = step;
-    tail.loss_out = loss_out;
-    tail.grad_out = grad_out;
-    tail.n = near_;
-    tail.f = far_;
-    tail.lr = lr;
-    tail.b1 = beta1;
-    tail.b2 = beta2;
-    tail.eps = eps;
-    tail.wd = weight_decay;
-    tail.defer_adam = 0;
     return fused_chain(ctx, verts, tris, tri_link, vert_link, opp, mvp, ref, P * Bv, L, V, T, H, W, mask, loss_b, grad_mvp,
                        &head, &tail, stream, Bv);
 }

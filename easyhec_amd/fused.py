@@ -143,21 +143,26 @@ STAGES = ("vertex", "job", "resolve", "unused3", "composite", "unused5", "unused
 DOMINANT_STAGE, DOMINANT_KERNEL = "job", "vb_job_kernel"
 
 
-def bind_ref(glctx, scene, ref):
+def bind_ref(glctx, scene, ref, views=None):
     """Bind a reference-mask batch to the context's plan (``ehr_fused_bind_ref``): the loss contribution of the tiles no
     link touches is cached once, and later calls with THIS tensor and no mask output only visit the tiles inside the
     views' link boxes -- bit-identical results (64-bit fixed-point sums).  The caller must not modify ``ref`` in place
-    while it is bound; ``ref=None`` unbinds.  The context keeps a reference to the tensor."""
+    while it is bound; ``ref=None`` unbinds.  The context keeps a reference to the tensor.  ``views``: how many views the
+    plan holds when that is a multiple of the masks given -- the poses of a multi-start step share them
+    (``ehr_fused_bind_ref_shared``)."""
     if ref is None:
         _lib.check(_lib.lib().ehr_fused_bind_ref(glctx.handle, None, None), "ehr_fused_bind_ref")
         glctx._bound_ref = None
         return
     dr._check_dev("ref", ref, torch.float32)
     dr._require(ref.dim() == 3 and ref.is_contiguous(), "ref must be a contiguous [B, H, W] tensor")
-    _ensure_plan(glctx, scene, ref.shape[0], ref.shape[1], ref.shape[2])
+    views = ref.shape[0] if views is None else views
+    dr._require(views % ref.shape[0] == 0, "views must be a multiple of ref.shape[0]")
+    _ensure_plan(glctx, scene, views, ref.shape[1], ref.shape[2])
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     with torch.cuda.device(glctx.device):
-        _lib.check(_lib.lib().ehr_fused_bind_ref(glctx.handle, _lib.ptr(ref), stream), "ehr_fused_bind_ref")
+        _lib.check(_lib.lib().ehr_fused_bind_ref_shared(glctx.handle, _lib.ptr(ref), ref.shape[0], stream),
+                   "ehr_fused_bind_ref")
     glctx._bound_ref = ref
 
 

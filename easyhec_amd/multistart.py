@@ -7,13 +7,13 @@ hypothesis p on real view j is virtual view ``p * Bv + j`` of a P x Bv-view plan
 shared, never copied, and every hypothesis reproduces its solo ``FusedPoseStep`` solve bit for bit
 (tests/test_gpu_multistart.py).  HIP only: CPU tensors or a missing device raise, there is no fallback."""
 import ctypes
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
-from . import _lib, fused
+from . import _lib
+from .chain_step import _ChainStep
 from .fast import _f
 from .se3 import se3_log_map
 from .synthetic import perturb_pose
@@ -55,11 +55,13 @@ def _starts_to_dof(starts):
     raise ValueError("starts must be [P,4,4] poses or [P,6] dofs")
 
 
-class MultiStartPoseStep:
-    """Mirrors :class:`easyhec_amd.fast.FusedPoseStep` for P hypotheses.  State lives in this object (``dof``, ``exp_avg``,
-    ``exp_avg_sq`` [P,6]; ``step_t``, ``hist_row`` [P]; ``history`` [P,rows,6], every hypothesis starting from a copy of the
-    model's ``history_ops``); the model is only read (meshes, image size, history) until :func:`solve_multistart` writes the
-    winner into it.  Single process: hypotheses are not exchanged across ranks."""
+class MultiStartPoseStep(_ChainStep):
+    """:class:`easyhec_amd.fast.FusedPoseStep` for P hypotheses, on the same :class:`easyhec_amd.chain_step._ChainStep`
+    (``step`` returns the [P] losses: NaN for a hypothesis that is frozen, all NaN for a reported step -- the conditions
+    are step-wide).  State lives in this object (``dof``, ``exp_avg``, ``exp_avg_sq`` [P,6]; ``step_t``, ``hist_row`` [P];
+    ``history`` [P,rows,6], every hypothesis starting from a copy of the model's ``history_ops``); the model is only read
+    (meshes, image size, history) until :func:`solve_multistart` writes the winner into it.  Single process: hypotheses are
+    not exchanged across ranks."""
 
     def __init__(self, model, batch, starts, lr=0.003, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0005, near=0.001,
                  far=10.0, slack=None):
@@ -102,27 +104,7 @@ class MultiStartPoseStep:
         self.loss = torch.zeros((P,), device=dev)
         self.grad = torch.zeros((P, 6), device=dev)
         self.mask = None  # [B,H,W], allocated by the first step that asks for masks
-        # job slots per VIRTUAL view: FusedPoseStep's default rule
-        if slack is None and "EHR_VB_SLACK" not in os.environ:
-            ntiles = ((self.W + 31) // 32) * ((self.H + 7) // 8)
-            self.slack = max(0.5, 256.0 / ntiles)
-        else:
-            self.slack = float(os.environ["EHR_VB_SLACK"]) if slack is None else float(slack)
-        self._plan_and_bind()
-        self._graph = None
-        self.check_every = 16
-        self._calls = 0
-        self._probe = torch.zeros(P, dtype=torch.float32).pin_memory()
-        self._probe_ev = None
-        self.recoveries = []
-
-    def _plan_and_bind(self):
-        fused._ensure_plan(self.glctx, self.scene, self.B, self.H, self.W, slack=self.slack)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        with torch.cuda.device(self.glctx.device):
-            _lib.check(_lib.lib().ehr_fused_bind_ref_shared(self.glctx.handle, _lib.ptr(self.ref), self.Bv, stream),
-                       "ehr_fused_bind_ref_shared")
-        self.glctx._bound_ref = self.ref
+        self._init_chain(slack)  # (job slots per VIRTUAL view)
 
     def _enqueue(self, want_mask, stream=None):
         if stream is None:
@@ -140,80 +122,6 @@ class MultiStartPoseStep:
             _f(self.wd), _lib.ptr(self.mvp), _lib.ptr(self.tc_jac), _lib.ptr(self.mask if want_mask else None),
             _lib.ptr(self.loss_b), _lib.ptr(self.grad_mvp), _lib.ptr(self.red), _lib.ptr(self.loss), _lib.ptr(self.grad),
             stream), "ehr_solver_step_multi")
-
-    def step(self, want_mask=False):
-        """Enqueue one optimisation step of every hypothesis.  Returns the (device, [P]) mean mask losses evaluated BEFORE
-        the update; NaN for a hypothesis that is frozen, all NaN for a reported step.  Never synchronises."""
-        with torch.cuda.device(self.dev):
-            if self._graph and not want_mask:
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                _lib.check(_lib.lib().ehr_graph_launch(self.glctx.handle, stream), "ehr_graph_launch")
-            else:
-                self._enqueue(want_mask)
-            self._calls += 1
-            if self._calls % self.check_every == 0:
-                self._poll()
-        return self.loss
-
-    def _poll(self):
-        """Non-blocking look at the losses of the step taken `check_every` steps ago (FusedPoseStep._poll): a step-wide
-        report -- every hypothesis NaN -- triggers recover_from_overflow()."""
-        if self._probe_ev is not None:
-            if not self._probe_ev.query():
-                return
-            self._probe_ev = None
-            if bool(torch.isnan(self._probe).all()):
-                what = self.recover_from_overflow()
-                if what:
-                    self.recoveries.append(what)
-        self._probe.copy_(self.loss, non_blocking=True)
-        self._probe_ev = torch.cuda.Event()
-        self._probe_ev.record()
-
-    def capture(self):
-        """Record the step's launch chain into the context's hipGraph (``ehr_graph_*``); ``step()`` then replays it."""
-        if self._graph:
-            return
-        lib = _lib.lib()
-        with torch.cuda.device(self.dev):
-            torch.cuda.synchronize()
-            cap = ctypes.c_void_p()
-            _lib.check(lib.ehr_graph_begin(self.glctx.handle, ctypes.byref(cap)), "ehr_graph_begin")
-            try:
-                self._enqueue(False, stream=cap)
-            except Exception:
-                lib.ehr_graph_release(self.glctx.handle)
-                raise
-            _lib.check(lib.ehr_graph_end(self.glctx.handle), "ehr_graph_end")
-        self._graph = True
-
-    def release_graph(self):
-        if self._graph:
-            _lib.check(_lib.lib().ehr_graph_release(self.glctx.handle), "ehr_graph_release")
-            self._graph = None
-
-    def recover_from_overflow(self):
-        """Call when a step came back NaN for every hypothesis.  Synchronises.  Same contract as
-        :meth:`easyhec_amd.fast.FusedPoseStep.recover_from_overflow`: the conditions are step-wide, every hypothesis's state
-        is untouched by a reported step and its history row is reused, so the caller simply steps again."""
-        with torch.cuda.device(self.glctx.device):
-            rc = _lib.lib().ehr_fused_status(self.glctx.handle)
-        if rc == 0:
-            return False
-        had_graph = bool(self._graph)
-        if rc == _lib.EHR_ERR_RETRY:
-            if had_graph:
-                self.release_graph()
-                self.capture()
-            return "general-triangle pass"
-        if self.slack == 0.0:
-            _lib.check(rc, "fused render")
-        self.release_graph()
-        self.slack = 0.0
-        self._plan_and_bind()
-        if had_graph:
-            self.capture()
-        return "job slots"
 
     @property
     def steps_done(self):
@@ -253,8 +161,8 @@ class MultiStartResult:
 
 
 def solve_multistart(cfg, model, batch, starts, num_steps, tail=20, slack=None):
-    """Runs ``num_steps`` effective steps of every start from a captured graph, with the recovery loop of
-    ``RBSolverTrainer.fit`` (a reported step is recovered from and run again), ranks the hypotheses by the mean of their
+    """Runs ``num_steps`` effective steps of every start from a captured graph, with the recovery loop
+    ``RBSolverTrainer.fit`` uses (a reported step is recovered from and run again), ranks the hypotheses by the mean of their
     last ``tail`` losses and writes the winner's pose into ``model.dof`` and its rows into ``model.history_ops`` -- so
     SpaceExplorer and checkpoints see an ordinary solve."""
     if cfg.solver.do_grad_clip or cfg.solver.optimizer != "Adam":
@@ -262,21 +170,11 @@ def solve_multistart(cfg, model, batch, starts, num_steps, tail=20, slack=None):
     ms = MultiStartPoseStep(model, batch, starts, lr=cfg.solver.max_lr, weight_decay=cfg.solver.weight_decay, slack=slack)
     ms.capture()
     logs = []
-    start, remaining, rounds = ms.steps_done, num_steps, 0
-    while remaining > 0:
+    for remaining, _ in ms.effective_rounds(num_steps, "solve_multistart"):
         log = torch.empty((remaining, ms.P), device=ms.dev)
         for it in range(remaining):
             log[it].copy_(ms.step())
         logs.append(log)
-        remaining = num_steps - (ms.steps_done - start)
-        if remaining > 0:
-            rounds += 1
-            what = ms.recover_from_overflow()
-            if what:
-                ms.recoveries.append(what)
-            if rounds > 4:
-                fused.check_status(ms.glctx)
-                raise RuntimeError(f"solve_multistart: {remaining} of {num_steps} steps keep being reported as not taken")
     hist = torch.cat(logs).cpu()
     hist = hist[~torch.isnan(hist).all(dim=1)]  # (reported steps: NaN for every hypothesis, taken by none)
     means = hist[-tail:].double().mean(dim=0) if hist.shape[0] > 0 else torch.full((ms.P,), float("nan"), dtype=torch.float64)

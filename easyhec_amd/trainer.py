@@ -202,15 +202,16 @@ class RBSolverTrainer:
         """Runs ``num_epochs`` EFFECTIVE steps (base.py:161 ``fit``); returns the list of logged (step, loss) pairs.
         A step the launch chain reports instead of taking (NaN loss; dof and Adam untouched: a slot-limited plan that
         overflowed, a view that needs the general-triangle pass) does not count: the chain recovers by itself
-        (FusedPoseStep._poll, every few steps, or here at a logged step) and the lost iterations are run again, so the
-        solve takes exactly the steps it was asked for -- on every rank alike (Adam's step counter is replicated)."""
+        (``_ChainStep._poll``, every few steps, or here at a logged step) and the lost iterations are run again
+        (``_ChainStep.effective_rounds``), so the solve takes exactly the steps it was asked for -- on every rank alike
+        (Adam's step counter is replicated)."""
         n = self.cfg.solver.num_epochs if num_steps is None else num_steps
         history = []
         begin = time.time()
         base_steps = self.global_steps
-        start = self.fast.steps_done if self.fast is not None else 0
-        remaining, rounds = n, 0
-        while remaining > 0:
+        rounds = self.fast.effective_rounds(n, "fit") if self.fast is not None else [(n, 0)]
+        for remaining, done in rounds:
+            self.global_steps = base_steps + done
             for it in range(remaining):
                 last = it == remaining - 1
                 do_log = (self.global_steps % self.cfg.solver.log_interval == 0) or last
@@ -218,36 +219,19 @@ class RBSolverTrainer:
                 if do_log:
                     lv = float(loss)
                     if lv != lv and self.fast is not None:
-                        what = self.fast.recover_from_overflow()
-                        if what:
-                            self.fast.recoveries.append(what)
-                        else:
+                        if not self.fast._recover_and_note():
                             from . import fused
                             fused.check_status(self.fast.glctx)  # raises with the context's message
                         continue
                     history.append((self.global_steps, lv))
                     if log is not None:
                         log(f"step {self.global_steps} mask_loss {lv:.4f} elapsed {time.time() - begin:.2f}s")
-            if self.fast is None:
-                break
-            done = self.fast.steps_done - start  # (synchronises: once per fit, twice if a step was reported)
-            if log is not None:
+            if self.fast is not None and log is not None:
                 while self._reported < len(self.fast.recoveries):
                     what = self.fast.recoveries[self._reported]
                     self._reported += 1
                     log("job slots overflowed; planned again with a slot per (view, link, tile)" if what == "job slots" else
                         "triangles at the near plane; the general-triangle pass joins the chain")
-            self.global_steps = base_steps + done
-            remaining = n - done
-            if remaining > 0:
-                rounds += 1
-                if rounds > 4:
-                    from . import fused
-                    fused.check_status(self.fast.glctx)
-                    raise RuntimeError(f"fit: {remaining} of {n} steps keep being reported as not taken (NaN loss)")
-                what = self.fast.recover_from_overflow()
-                if what:
-                    self.fast.recoveries.append(what)
         return history
 
     # checkpoint in the reference's layout: ckpt['model']['dof'] / ['history_ops'] (trainer/rbsolver.py:95-114)
@@ -275,7 +259,6 @@ class RBSolverTrainer:
             self.fast.exp_avg_sq.zero_()
             if "optimizer" in d:
                 self.fast.load_state_dict(d["optimizer"])
-            self.fast.mark_counts()
         elif self._cuda_graph is not None:
             # The captured graph updates the tensors it was recorded with: the restored state goes INTO them (a new state
             # dict would leave the graph stepping the old moments, and save() writing tensors no replay touches), and the

@@ -242,3 +242,68 @@ def test_solve_multistart_end_to_end(xarm7):
     assert torch.equal(model.history_ops[0].cpu(), _starts_to_dof(starts)[res.winner])
     if res.winner == 0:
         assert torch.equal(model.history_ops[:n], ref_model.history_ops[:n])
+
+
+@pytest.fixture(scope="module")
+def closeup(xarm7):
+    """The close-up of test_gpu_fused.py::test_an_unattended_stepping_loop_recovers_by_itself (64 x 96, two views, zoomed
+    2.5 x: under EHR_VB_SLACK=1.0 its steps are reported for want of job slots), two starts around its pose, and per start
+    the solo solve that has every slot from the beginning: 16 steps, computed once."""
+    from easyhec_amd.config import Cfg
+    from easyhec_amd.rb_solver import RBSolver
+    from test_gpu_fused import workload
+    dev = torch.device("cuda:0")
+    H, W, B = 64, 96, 2
+    K, lp, Tc, _ = workload(xarm7, H, W, 0.075, B, seed=3)
+    K = np.array(K, dtype=np.float64)
+    K[:2, :2] *= 2.5
+    cfg = Cfg()
+    cfg.model.rbsolver.H, cfg.model.rbsolver.W = H, W
+    cfg.model.rbsolver.init_Tc_c2b = np.asarray(Tc).tolist()
+    ref = torch.zeros((B, H, W), device=dev)
+    ref[:, 10:50, 20:70] = 1.0
+    batch = {"mask": ref, "link_poses": torch.tensor(lp, dtype=torch.float32, device=dev),
+             "K": torch.tensor(K, dtype=torch.float32, device=dev)[None].repeat(B, 1, 1)}
+    make = lambda: RBSolver(cfg, meshes=xarm7.meshes).to(dev)
+    starts = starts_for(cfg, 2)
+    solo = solo_states(cfg, make, batch, starts, steps=16, slack=0.0)
+    return cfg, make, batch, starts, solo
+
+
+def test_an_unattended_multi_start_loop_recovers_job_slots_by_itself(closeup, monkeypatch):
+    """48 step() calls and nobody looks: calls 1..32 are reported (the poll at call 16 starts the look, the one at call 32
+    sees it and plans again with every slot), calls 33..48 are the 16 steps of the solo solves."""
+    from easyhec_amd.fast import FusedPoseStep
+    from easyhec_amd.multistart import MultiStartPoseStep
+    cfg, make, batch, starts, solo = closeup
+    monkeypatch.setenv("EHR_VB_SLACK", "1.0")
+    cfg.model.rbsolver.init_Tc_c2b = np.asarray(starts[0]).tolist()
+    f = FusedPoseStep(make(), batch)  # the precondition: alone, start 0 is reported for want of job slots
+    assert f.slack == 1.0 and bool(torch.isnan(f.step()).all())
+    assert f.recover_from_overflow() == "job slots"
+    ms = MultiStartPoseStep(make(), batch, starts)
+    assert ms.slack == 1.0 and ms.check_every == 16 and (ms.P, ms.Bv) == (2, 2)
+    for i in range(48):
+        ms.step()
+        if i in (15, 31):
+            torch.cuda.synchronize()   # (so that the look started at call 16 has certainly arrived by call 32)
+    torch.cuda.synchronize()
+    assert ms.recoveries == ["job slots"] and ms.slack == 0.0
+    assert ms.steps_done == 16
+    assert_hypotheses_equal_solo(ms, solo, steps=16)
+
+
+def test_solve_multistart_takes_a_reported_step_again(closeup, monkeypatch):
+    """Five EFFECTIVE steps on the same close-up: the first round's steps are all reported, the loop recovers and runs them
+    again.  (Row r of a solo solve's history is its pose after r steps.)"""
+    from easyhec_amd.multistart import solve_multistart
+    cfg, make, batch, starts, solo = closeup
+    monkeypatch.setenv("EHR_VB_SLACK", "1.0")
+    model = make()
+    res = solve_multistart(cfg, model, batch, starts, num_steps=5)
+    assert res.steps == 5 and res.recoveries == ["job slots"]
+    assert torch.isfinite(res.loss_history).all()
+    for p in range(2):
+        assert torch.equal(res.dofs[p], solo[p]["history"][5].cpu()), p
+    assert torch.equal(model.dof.detach(), solo[res.winner]["history"][5])
+    assert torch.equal(model.history_ops[:5], solo[res.winner]["history"][:5])
