@@ -60,6 +60,7 @@ SIGNATURES = {
                               [c_float] * 5 + [c_void_p] * 8 + [c_void_p]),
     "ehr_fused_bind_ref_shared": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_mask_variance": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
+    "ehr_mask_overlap": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_comm_unique_id": (c_int, [c_void_p]),
     "ehr_comm_init": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "ehr_comm_allreduce": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
@@ -101,6 +102,14 @@ def has_multistart():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_solver_step_multi")
+
+
+def has_pose_search():
+    """True if the library has the pose search's overlap op (``ehr_mask_overlap``); the symbol's presence is the capability
+    check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_overlap")
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

@@ -67,6 +67,9 @@ int vbuf_meta_read(ehr_ctx* ctx, int* meta4);
 int vbuf_bind_ref(ehr_ctx* ctx, const float* ref, int views, hipStream_t stream);
 int vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp, int Q, int S,
                int L, int V, int T, int H, int W, long long* score, unsigned char* count, hipStream_t stream, int* handled);
+int vbuf_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+                 const float* ref, int Q, int S, int L, int V, int T, int H, int W, long long* overlap, long long* ref_area,
+                 hipStream_t stream, int* handled);
 int vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
                const int32_t* opp, float* mvp, const float* ref, int B, int L, int V, int T, int H, int W, float* mask,
                float* loss, float* grad_mvp, const StepHead* head, const StepTail* tail, hipStream_t stream,
@@ -132,9 +135,10 @@ struct ehr_ctx {
                                // across re-plans that do not grow it)
     // space-explorer scoring (ehr_mask_variance) keeps its own scratch so that it never disturbs a solver plan
     ehr::Scratch sc_counts, sc_offsets, sc_entries, sc_posc;
+    ehr::Scratch sc_img;  // pose search (ehr_mask_overlap), exact path only: a pass's masks u8 [views][H][W] | its score sink i64 [views]
     size_t sc_entries_cap = 0;
     // ... and, for the coverage-only chain of the scoring op (ehr_vbuf.hip: vbuf_score), the static cluster index of its mesh
-    ehr::Scratch sc_clus, sc_misc;  // (sc_misc: link boxes | meta block | hint lists | sticky flag | sums | coverage words, VbScoreMisc)
+    ehr::Scratch sc_clus, sc_misc;  // (sc_misc: link boxes | meta block | hint lists | sticky flag | sums | coverage words | the op's own, VbScoreMisc)
     int sc_nc = 0;
     const void* sc_key[3] = {nullptr, nullptr, nullptr};  // (verts, tris, vert_link) the index was built for
     int sc_key_n[3] = {0, 0, 0};                          // (V, T, L)
@@ -155,7 +159,7 @@ struct ehr_ctx {
     unsigned long long scratch_moves() const {
         unsigned long long n = 0;
         for (const ehr::Scratch* s : {&counts, &offsets, &entries, &vb_clus, &vb_heavy, &vb_idx, &vb_boxes, &vb_units, &vb_acc,
-                                      &vb_posc, &vb_jobs, &vb_spill, &vb_refsum, &vb_hstate, &vb_hstate_m, &sc_counts, &sc_offsets, &sc_entries, &sc_posc, &sc_clus, &sc_misc})
+                                      &vb_posc, &vb_jobs, &vb_spill, &vb_refsum, &vb_hstate, &vb_hstate_m, &sc_counts, &sc_offsets, &sc_entries, &sc_posc, &sc_clus, &sc_misc, &sc_img})
             n += s->moves;
         return n;
     }

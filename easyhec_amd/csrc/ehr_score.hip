@@ -159,25 +159,45 @@ score_tile_kernel(ClipSource src, BinGeom g, const int* __restrict__ counts, con
     }
 }
 
+// Pose search, exact path: a pass's masks (the count images of single-pose "candidates": 0 / 1, row 0 = top) against the
+// observed masks.  blockIdx.y = view of the pass, global view v0 + y = candidate * S + s; every wave adds its partial sums
+// with integer atomics (a few dozen per view).  The views of candidate 0 also count their observed mask's area.
+__global__ void __launch_bounds__(256)
+score_overlap_reduce_kernel(const unsigned char* __restrict__ img, const float* __restrict__ ref, int S, int HW, long long v0,
+                            unsigned long long* __restrict__ overlap, unsigned long long* __restrict__ ref_area) {
+    const long long v = v0 + blockIdx.y;
+    const int s = (int)(v % S);
+    const unsigned char* const m = img + (size_t)blockIdx.y * HW;
+    const float* const r = ref + (size_t)s * HW;
+    unsigned inter = 0, area = 0, ra = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        const unsigned on = m[i] != 0, fg = r[i] > 0.5f;
+        area += on;
+        inter += on & fg;
+        ra += fg;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        inter += __shfl_xor(inter, o, 64);
+        area += __shfl_xor(area, o, 64);
+        ra += __shfl_xor(ra, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (inter) atomicAdd(&overlap[2 * v], (unsigned long long)inter);
+        if (area) atomicAdd(&overlap[2 * v + 1], (unsigned long long)area);
+        if (v < S && ra) atomicAdd(&ref_area[s], (unsigned long long)ra);
+    }
+}
+
 }  // namespace ehr
 
 using namespace ehr;
 
-extern "C" int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
-                                 const float* mvp, int Q, int S, int L, int V, int T, int H, int W, int64_t* score,
-                                 uint8_t* count, int chunk_views, void* stream_) {
-    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_mask_variance: ctx is NULL");
-    if (!verts || !tris || !mvp || !score) return fail(EHR_ERR_INVALID, "ehr_mask_variance: NULL tensor");
-    if (Q <= 0 || L <= 0 || V <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(EHR_ERR_INVALID, "ehr_mask_variance: bad sizes");
-    if (S < 1 || S > SCORE_MAX_S) return fail(EHR_ERR_INVALID, "ehr_mask_variance: S must be in [1, %d]", SCORE_MAX_S);
-    if (H > 32768 || W > 32768) return fail(EHR_ERR_INVALID, "ehr_mask_variance: resolution above 32768 is unsupported");
-    hipStream_t stream = (hipStream_t)stream_;
-    {   // the coverage-only chain on the solver's cluster / job machinery, where the call allows it (ehr_vbuf.hip)
-        int handled = 0;
-        const int rc2 = vbuf_score(ctx, verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, (long long*)score, count, stream, &handled);
-        if (rc2) return rc2;
-        if (handled) return EHR_OK;
-    }
+// The per-triangle tile implementation of the scoring op: binning into (view, tile) queues and an exact z-buffer per tile,
+// in passes of about chunk_views rendered views, one synchronisation per pass.  `what` names the calling op in messages.
+static int score_tiles(ehr_ctx* ctx, const char* what, const float* verts, const int32_t* tris, const int32_t* vert_link,
+                       const float* mvp, int Q, int S, int L, int V, int T, int H, int W, int64_t* score, uint8_t* count,
+                       int chunk_views, hipStream_t stream) {
     BinGeom g;
     g.W = W;
     g.H = H;
@@ -189,7 +209,7 @@ extern "C" int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t
     if (chunk_views <= 0) chunk_views = 512;
     const int Qc = std::max(1, std::min(Q, chunk_views / S));
     const size_t views = (size_t)Qc * S, nkeys = views * g.nt;
-    if (nkeys > (size_t)0x7fffffff / 4) return fail(EHR_ERR_INVALID, "ehr_mask_variance: chunk too large");
+    if (nkeys > (size_t)0x7fffffff / 4) return fail(EHR_ERR_INVALID, "%s: chunk too large", what);
     int rc;
     // counts | cursors | tile_slow | meta          offsets | worklist (2 x Qc x nt)
     if ((rc = ctx->sc_counts.reserve((3 * nkeys + 2 * EHR_META_INTS) * sizeof(int)))) return rc;
@@ -241,7 +261,7 @@ extern "C" int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t
         EHR_HIP(hipStreamSynchronize(stream));
         const size_t total = (size_t)ctx->host_pinned[EHR_META_TOTAL];
         const int nwork = ctx->host_pinned[META_PAIRS], nslow = ctx->host_pinned[META_PAIRS_SLOW];
-        if (total > (size_t)0x7fffffff) return fail(EHR_ERR_INVALID, "ehr_mask_variance: %zu queue entries in one pass; lower chunk_views", total);
+        if (total > (size_t)0x7fffffff) return fail(EHR_ERR_INVALID, "%s: %zu queue entries in one pass; lower chunk_views", what, total);
         if (total > ctx->sc_entries_cap) {
             size_t want = total + total / 4;
             if ((rc = ctx->sc_entries.reserve(want * sizeof(int4)))) return rc;
@@ -266,6 +286,65 @@ extern "C" int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t
     EHR_HIP(hipMemcpyAsync(ctx->host_pinned, smeta, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
     EHR_HIP(hipStreamSynchronize(stream));
     const int sticky = ctx->host_pinned[EHR_META_OVERFLOW];
-    if (sticky) return fail(EHR_ERR_OVERFLOW, "ehr_mask_variance: internal queue overflow (results are invalid)");
+    if (sticky) return fail(EHR_ERR_OVERFLOW, "%s: internal queue overflow (results are invalid)", what);
+    return EHR_OK;
+}
+
+extern "C" int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
+                                 const float* mvp, int Q, int S, int L, int V, int T, int H, int W, int64_t* score,
+                                 uint8_t* count, int chunk_views, void* stream_) {
+    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_mask_variance: ctx is NULL");
+    if (!verts || !tris || !mvp || !score) return fail(EHR_ERR_INVALID, "ehr_mask_variance: NULL tensor");
+    if (Q <= 0 || L <= 0 || V <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(EHR_ERR_INVALID, "ehr_mask_variance: bad sizes");
+    if (S < 1 || S > SCORE_MAX_S) return fail(EHR_ERR_INVALID, "ehr_mask_variance: S must be in [1, %d]", SCORE_MAX_S);
+    if (H > 32768 || W > 32768) return fail(EHR_ERR_INVALID, "ehr_mask_variance: resolution above 32768 is unsupported");
+    hipStream_t stream = (hipStream_t)stream_;
+    {   // the coverage-only chain on the solver's cluster / job machinery, where the call allows it (ehr_vbuf.hip)
+        int handled = 0;
+        const int rc2 = vbuf_score(ctx, verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, (long long*)score, count, stream, &handled);
+        if (rc2) return rc2;
+        if (handled) return EHR_OK;
+    }
+    return score_tiles(ctx, "ehr_mask_variance", verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, score, count, chunk_views, stream);
+}
+
+extern "C" int ehr_mask_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
+                                const float* mvp, const float* ref, int Q, int S, int L, int V, int T, int H, int W,
+                                int64_t* overlap, int64_t* ref_area, int chunk_views, void* stream_) {
+    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_mask_overlap: ctx is NULL");
+    if (!verts || !tris || !mvp || !ref || !overlap || !ref_area) return fail(EHR_ERR_INVALID, "ehr_mask_overlap: NULL tensor");
+    if (Q <= 0 || L <= 0 || V <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(EHR_ERR_INVALID, "ehr_mask_overlap: bad sizes");
+    if (S < 1 || S > SCORE_MAX_S) return fail(EHR_ERR_INVALID, "ehr_mask_overlap: S must be in [1, %d]", SCORE_MAX_S);
+    if (H > 32768 || W > 32768) return fail(EHR_ERR_INVALID, "ehr_mask_overlap: resolution above 32768 is unsupported");
+    hipStream_t stream = (hipStream_t)stream_;
+    {   // the coverage-only chain, where the call allows it (ehr_vbuf.hip)
+        int handled = 0;
+        const int rc2 = vbuf_overlap(ctx, verts, tris, vert_link, mvp, ref, Q, S, L, V, T, H, W, (long long*)overlap,
+                                     (long long*)ref_area, stream, &handled);
+        if (rc2) return rc2;
+        if (handled) return EHR_OK;
+    }
+    // The exact path: every (candidate, view) is a single-pose candidate of the tile implementation, whose count image is
+    // then the mask; passes of at most chunk_views views, bounded by the scratch for their images (256 MiB) and the reducer's grid (32768).
+    if (chunk_views <= 0) chunk_views = 512;
+    const size_t HW = (size_t)H * W;
+    const long long views = (long long)Q * S;
+    const int pass = (int)std::max<long long>(1, std::min<long long>({views, (long long)chunk_views, 32768ll, (long long)(((size_t)256 << 20) / HW)}));
+    int rc;
+    const size_t img_bytes = ((size_t)pass * HW + 7) & ~(size_t)7;
+    if ((rc = ctx->sc_img.reserve(img_bytes + (size_t)pass * sizeof(int64_t)))) return rc;
+    uint8_t* img = (uint8_t*)ctx->sc_img.ptr;
+    int64_t* sink = (int64_t*)(img + img_bytes);  // (the variance of one mask: all zero)
+    EHR_HIP(hipMemsetAsync(overlap, 0, (size_t)views * 2 * sizeof(int64_t), stream));
+    EHR_HIP(hipMemsetAsync(ref_area, 0, (size_t)S * sizeof(int64_t), stream));
+    for (long long v0 = 0; v0 < views; v0 += pass) {
+        const int n = (int)std::min<long long>(pass, views - v0);
+        if ((rc = score_tiles(ctx, "ehr_mask_overlap", verts, tris, vert_link, mvp + (size_t)v0 * L * 16, n, 1, L, V, T, H, W, sink, img,
+                              chunk_views, stream)))
+            return rc;
+        score_overlap_reduce_kernel<<<dim3((unsigned)std::min<size_t>((HW + 2047) / 2048, 16), n), 256, 0, stream>>>(
+            img, ref, S, (int)HW, v0, (unsigned long long*)overlap, (unsigned long long*)ref_area);
+        EHR_LAUNCH_CHECK();
+    }
     return EHR_OK;
 }

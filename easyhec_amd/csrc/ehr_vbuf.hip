@@ -1,5 +1,5 @@
 // ehr_vbuf.hip -- the fused hot path: the kernels and the launch chain behind ehr_render_mask_loss / ehr_solver_step
-// (host entry points: ehr_fused.hip) and the coverage-only chain of ehr_mask_variance (vbuf_score).  Restates
+// (host entry points: ehr_fused.hip) and the coverage-only chain of ehr_mask_variance / ehr_mask_overlap (vb_cov_chain).  Restates
 //   /root/reference/easyhec/modeling/models/rb_solve/rb_solver.py:60-72   (per-link render, sum, clamp, SSE)
 //   /root/reference/easyhec/structures/nvdiffrast_renderer.py:33-47        (rasterize -> interpolate -> antialias -> flip)
 //   /root/reference/easyhec/utils/nvdiffrast_utils.py:14-18                (transform_pos)
@@ -112,7 +112,7 @@ struct VbItem {
 };
 
 // Scratch layouts.  Every scratch buffer of the chain is described ONCE, by a host function that carves its arrays, in
-// order, from a base pointer (vb_recs, vb_heavy, vb_slots, vb_score_misc below); over a null base the end of the last
+// order, from a base pointer (vb_recs, vb_heavy, vb_slots, vb_score_misc, vb_overlap_misc below); over a null base the end of the last
 // array is the byte size the plan reserves.  (The bases come from hipMalloc: aligned beyond anything asked for here.)
 struct VbCarve {
     uintptr_t at;
@@ -2747,6 +2747,110 @@ vb_score_count_kernel(BinGeom g, int nq, int S, const u64* __restrict__ tcov, un
     }
 }
 
+static_assert(EHR_TILE_W == 32 && EHR_TILE_H == 8, "coverage words: four u64 per tile, word r >> 1 holds row r at bit (r & 1) * 32 + col");
+
+// Pose search (ehr_mask_overlap), once per call: the observed masks ref [S][H][W] (row 0 = top; foreground iff > 0.5f, so
+// NaN is background) in the bit layout of the coverage words, rbits [S][nt][4], and their areas.  One wave per tile, lane
+// = (tile row, four columns) as in the count kernel above: eight lanes read 128 contiguous bytes of an image row, the 16
+// lanes of a word OR their shifted nibbles together.  Pixels beyond W / H pack as 0.  blockIdx.y = view; a wave adds
+// its tiles' popcounts up and issues one atomic.
+__global__ void __launch_bounds__(256)
+vb_overlap_pack_ref_kernel(BinGeom g, const float* __restrict__ ref, u64* __restrict__ rbits,
+                           unsigned long long* __restrict__ ref_area) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = blockIdx.y;
+    const int r = lane >> 3, c4 = (lane & 7) * 4;
+    const int sh = (r & 1) * 32 + c4;
+    const float* const img = ref + (size_t)s * g.H * g.W;
+    unsigned n = 0;
+    for (int tile = blockIdx.x * 4 + wave; tile < g.nt; tile += gridDim.x * 4) {
+        const int tx = tile % g.ntx, ty = tile / g.ntx;
+        const int ix = tx * EHR_TILE_W + c4, iy = ty * EHR_TILE_H + r;
+        unsigned bits = 0;
+        if (iy < g.H) {
+            const float* const row = img + (size_t)(g.H - 1 - iy) * g.W;  // tile rows count from the image's bottom
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (ix + j < g.W && row[ix + j] > 0.5f) bits |= 1u << j;
+        }
+        u64 w = (u64)bits << sh;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) w |= __shfl_xor(w, o, 64);
+        if ((lane & 15) == 0) {
+            rbits[((size_t)s * g.nt + tile) * 4 + (lane >> 4)] = w;
+            n += __popcll(w);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if (lane == 0 && n) atomicAdd(&ref_area[s], (unsigned long long)n);
+}
+
+// Pose search, last stage of a chunk: per (candidate, view) the integers |render| and |render & ref|.  Persistent waves;
+// a wave owns `per_wave` CONSECUTIVE (candidate, tile) items, lane 4 s + k fetches coverage word k of view s (16 views per
+// round trip, four tiles in flight) and, where the tile holds anything at all, the matching word of rbits (L2 resident,
+// shared by every candidate).  Each lane keeps the popcounts of its own word in two registers across the tiles of a
+// candidate; only when the candidate changes or the range ends are the four lanes of a view summed and flushed with ONE
+// 64-bit integer atomic, area << 32 | inter (both <= H W <= 2^30, so the halves never carry into each other), on a
+// 128-byte line of the (candidate, view)'s own -- the serialisation the comment in vb_score_count_kernel records, divided
+// by per_wave.  S > 16: the range is walked once per block of 16 views, so the registers do not grow with S.  Like
+// vb_score_count_kernel it re-arms the link boxes and hands the PREVIOUS chunk's sums to the caller's packed [.,S,2] array
+// with plain stores (the last launch has nq = 0).
+__global__ void __launch_bounds__(256)
+vb_overlap_count_kernel(BinGeom g, int nq, int S, int per_wave, const u64* __restrict__ tcov, const u64* __restrict__ rbits,
+                        unsigned long long* __restrict__ oacc, int* __restrict__ lbox, int nlbox,
+                        unsigned long long* __restrict__ prev_oacc, long long* __restrict__ prev_out, int prev_n) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nlbox; i += gridDim.x * 256) lbox[i] = (i & 2) ? INT_MIN : INT_MAX;
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < prev_n; i += 256) {
+            const unsigned long long v = prev_oacc[16 * (size_t)i];
+            prev_out[2 * (size_t)i] = (long long)(v & 0xffffffffull);
+            prev_out[2 * (size_t)i + 1] = (long long)(v >> 32);
+            prev_oacc[16 * (size_t)i] = 0ull;
+        }
+    const long long total = (long long)nq * g.nt;
+    const long long first = (long long)(blockIdx.x * 4 + wave) * per_wave;
+    if (first >= total) return;
+    const int i0 = (int)first, i1 = (int)min(total, first + per_wave);
+    const int k = lane & 3;
+    for (int s0 = 0; s0 < S; s0 += 16) {
+        const int ls = s0 + (lane >> 2);
+        const bool on = ls < S;
+        const u64* const cov = tcov + (size_t)(on ? ls : 0) * 4 + k;            // + item * S * 4
+        const u64* const rb = rbits + (size_t)(on ? ls : 0) * g.nt * 4 + k;     // + tile * 4
+        unsigned inter = 0, area = 0;
+        int q = i0 / g.nt, tile = i0 - q * g.nt;
+        auto flush = [&]() {
+            inter += __shfl_xor(inter, 1, 64);
+            inter += __shfl_xor(inter, 2, 64);
+            area += __shfl_xor(area, 1, 64);
+            area += __shfl_xor(area, 2, 64);
+            if (k == 0 && area) atomicAdd(&oacc[16 * ((size_t)q * S + ls)], ((unsigned long long)area << 32) | inter);
+            inter = area = 0;
+        };
+        for (int i = i0; i < i1; i += 4) {
+            u64 m[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) m[j] = (on && i + j < i1) ? cov[(size_t)(i + j) * S * 4] : 0ull;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (i + j >= i1) break;                       // (wave-uniform)
+                if (__ballot(m[j] != 0ull) != 0) {            // (most tiles hold nothing)
+                    const u64 rw = on ? rb[(size_t)tile * 4] : 0ull;
+                    area += __popcll(m[j]);
+                    inter += __popcll(m[j] & rw);
+                }
+                if (++tile == g.nt) {                         // the candidate changes
+                    flush();
+                    tile = 0;
+                    q++;
+                }
+            }
+        }
+        if (tile != 0) flush();
+    }
+}
+
 // [T][3] int32 -> [T] int4 (one aligned 16-byte gather per triangle in the silhouette analysis)
 __global__ void vb_pad_kernel(const int32_t* __restrict__ a, int T, int4* __restrict__ out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3188,17 +3292,18 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     return EHR_OK;
 }
 
-// The scoring chain's small scratch (ehr_ctx::sc_misc), for a chunk of Qc candidates x S poses = Bc views
+// The coverage chain's small scratch (ehr_ctx::sc_misc), for a chunk of Qc candidates x S poses = Bc views
 struct VbScoreMisc {
     int* lbox;                  // [Bc][L][VB_LBOX_STRIDE] link boxes
     int* meta;                  // a meta block (VB_META_BYTES)
     VbHeavy hv;                 // the heavy-job hint's counters and lists (no stamps: the hint is off)
     int* sticky;                // [16] [0]: a triangle needs the exact z-buffer
     size_t zero_bytes;          // hv .. sticky, cleared at the start of a call
-    unsigned long long* sacc;   // [2][Qc][16] per-candidate sums, double buffered
+    unsigned long long* sacc;   // [2][Qc][16] per-candidate sums of the variance op, double buffered
     u64* tcov;                  // [Bc][nt][4] coverage words of the (view, tile)s
+    void* own;                  // `own_bytes` of the op's last stage (128-byte aligned; VbOverlapMisc)
 };
-static VbScoreMisc vb_score_misc(void* base, size_t Qc, size_t Bc, int L, int nt, size_t* bytes = nullptr) {
+static VbScoreMisc vb_score_misc(void* base, size_t Qc, size_t Bc, int L, int nt, size_t own_bytes, size_t* bytes = nullptr) {
     VbCarve c{(uintptr_t)base};
     VbScoreMisc m;
     m.lbox = c.take<int>((size_t)VB_LBOX_STRIDE * Bc * L);
@@ -3211,27 +3316,56 @@ static VbScoreMisc vb_score_misc(void* base, size_t Qc, size_t Bc, int L, int nt
     m.zero_bytes = c.at - (uintptr_t)m.hv.gen;
     m.sacc = c.take<unsigned long long>(2 * 16 * Qc, 128);
     m.tcov = c.take<u64>(Bc * nt * 4);
+    m.own = c.take<char>(own_bytes, 128);
     if (bytes) *bytes = c.at - (uintptr_t)base;
     return m;
 }
 
-// The scoring op (ehr_mask_variance, csrc/ehr_score.hip) on the solver's machinery: the static cluster index of the packed
-// mesh, then per chunk of candidates the vertex kernel (records + link boxes; depth class "coverage decides": every
-// coverable pixel of the triangle has z/w in (0, 1]), the job kernel in its coverage-only form (no deferred units, no
-// depth, no slots: a job ORs its tile's coverage into the view's word) and the count kernel.  *handled = 0 if the call
-// cannot take this road (then nothing the caller sees was touched beyond `score` / `count`, which it rewrites): links
-// not grouped, too many views per candidate for one chunk, or -- known only afterwards -- a triangle whose depth class
-// needs the exact z-buffer (geometry within two near-plane distances of the camera, or crossing the far plane).
-int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp, int Q,
-                    int S, int L, int V, int T, int H, int W, long long* score, unsigned char* count, hipStream_t stream,
-                    int* handled) {
+// The pose search's own part of that scratch
+struct VbOverlapMisc {
+    unsigned long long* oacc;   // [2][Bc][16] area << 32 | inter of a (candidate, view), one 128-byte line each, double buffered
+    u64* rbits;                 // [S][nt][4] the observed masks in the coverage words' bit layout (32 B per (view, tile))
+};
+static VbOverlapMisc vb_overlap_misc(void* base, size_t Bc, int S, int nt, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbOverlapMisc m;
+    m.oacc = c.take<unsigned long long>(2 * 16 * Bc, 128);
+    m.rbits = c.take<u64>((size_t)S * nt * 4, 128);
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return m;
+}
+
+// What a chunk's last stage gets to see of the coverage chain
+struct VbCovChunk {
+    BinGeom g;
+    int S, Qc, Bc, nlbox, num_cus;
+    VbScoreMisc m;
+};
+
+// The coverage-only chain on the solver's machinery, shared by the scoring op (ehr_mask_variance) and the pose search
+// (ehr_mask_overlap), both in csrc/ehr_score.hip: the static cluster index of the packed mesh, then per chunk of
+// candidates the vertex kernel (records + link boxes; depth class "coverage decides": every coverable pixel of the
+// triangle has z/w in (0, 1]), the job kernel in its coverage-only form (no deferred units, no depth, no slots: a job ORs
+// its tile's coverage into the view's word) and the op's own last stage, which also re-arms the link boxes:
+//   st.op                           the op's name, for messages
+//   st.own_bytes(Bc, nt)            scratch of its own (VbScoreMisc::own)
+//   st.begin(c, stream)             clears its outputs and sums, arms the link boxes
+//   st.chunk(c, q0, nq, stream)     consumes the coverage words of candidates [q0, q0 + nq)
+//   st.end(c, stream)               hands the last chunk's sums over
+// *handled = 0 if the call cannot take this road (then nothing the caller sees was touched beyond the op's outputs, which
+// it rewrites): links not grouped, too many views per candidate for one chunk, or -- known only afterwards -- a triangle
+// whose depth class needs the exact z-buffer (geometry within two near-plane distances of the camera, or crossing the
+// far plane).
+template <class Stage>
+static int vb_cov_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp, int Q,
+                        int S, int L, int V, int T, int H, int W, hipStream_t stream, int* handled, Stage& st) {
     *handled = 0;
     // EHR_SCORE_PATH (tests, A/B): "tile" = always the per-triangle queue path of ehr_score.hip, "chain" = this one or an error
     const char* const want = getenv("EHR_SCORE_PATH");
     const bool must = want && !strcmp(want, "chain");
     if (want && !strcmp(want, "tile")) return EHR_OK;
     if (!vert_link || L > 32 || S * L > VB_MAX_UNITS || H > 32760 || W > 32736)
-        return must ? fail(EHR_ERR_INVALID, "ehr_mask_variance: EHR_SCORE_PATH=chain, but the call's sizes do not allow it") : EHR_OK;
+        return must ? fail(EHR_ERR_INVALID, "%s: EHR_SCORE_PATH=chain, but the call's sizes do not allow it", st.op) : EHR_OK;
     int rc;
     unsigned long long hash = 0;
     {
@@ -3263,8 +3397,10 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         ctx->sc_hash = hash;
     }
     if (ctx->sc_mixed || ctx->sc_nc <= 0)
-        return must ? fail(EHR_ERR_INVALID, "ehr_mask_variance: EHR_SCORE_PATH=chain, but the mesh's links are not grouped") : EHR_OK;
-    const BinGeom g = make_geom(H, W, L);
+        return must ? fail(EHR_ERR_INVALID, "%s: EHR_SCORE_PATH=chain, but the mesh's links are not grouped", st.op) : EHR_OK;
+    VbCovChunk c;
+    c.g = make_geom(H, W, L);
+    const BinGeom& g = c.g;
     const int NC = ctx->sc_nc;
     const auto [cl, si] = vb_cluster_index(ctx->sc_clus, NC, L);
     // candidates per chunk: (view, link) units of a chunk fit the job kernel's LDS tables; scratch bounded like the solver's
@@ -3277,60 +3413,157 @@ int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
     if ((rc = ctx->sc_posc.reserve((size_t)Bc * V * sizeof(float4)))) return rc;
     vb_recs(nullptr, Bc, NC, &bytes);
     if ((rc = ctx->sc_entries.reserve(bytes))) return rc;
-    vb_score_misc(nullptr, Qc, Bc, L, g.nt, &bytes);
+    const size_t own_bytes = st.own_bytes(Bc, g.nt);
+    vb_score_misc(nullptr, Qc, Bc, L, g.nt, own_bytes, &bytes);
     if ((rc = ctx->sc_misc.reserve(bytes))) return rc;
     ctx->sc_entries_cap = 0;  // (the per-triangle path sizes its queues again if it runs after this)
-    const auto [lbox, meta, hv, sticky, zero_bytes, sacc0, tcov] = vb_score_misc(ctx->sc_misc.ptr, Qc, Bc, L, g.nt);
+    c.m = vb_score_misc(ctx->sc_misc.ptr, Qc, Bc, L, g.nt, own_bytes);
+    c.S = S; c.Qc = Qc; c.Bc = Bc; c.nlbox = VB_LBOX_STRIDE * Bc * L; c.num_cus = ctx->num_cus;
+    const VbScoreMisc& m = c.m;
     float4* posc = (float4*)ctx->sc_posc.ptr;
-    EHR_HIP(hipMemsetAsync(hv.gen, 0, zero_bytes, stream));
-    EHR_HIP(hipMemsetAsync(sacc0, 0, 2 * 16 * (size_t)Qc * sizeof(unsigned long long), stream));
-    EHR_HIP(hipMemsetAsync(score, 0, (size_t)Q * sizeof(long long), stream));
-    if (count) EHR_HIP(hipMemsetAsync(count, 0, (size_t)Q * H * W, stream));
+    EHR_HIP(hipMemsetAsync(m.hv.gen, 0, m.zero_bytes, stream));
     const int nvb = (std::max(V, 1) + 255) / 256;
     const int nitems = nvb + (NC + 3) / 4;
     const int job_wgs = vb_xcd_round_up(ctx->num_cus * VB_JOB_GRID);
-    // link boxes start empty (afterwards the count kernel re-arms them)
-    vb_score_count_kernel<<<64, 256, 0, stream>>>(g, 0, S, tcov, sacc0, nullptr, lbox, VB_LBOX_STRIDE * Bc * L, sacc0, score, 0);
-    EHR_LAUNCH_CHECK();
-    unsigned long long* prev_sacc = sacc0;
-    long long* prev_score = score;
-    int prev_nq = 0, flip = 0;
+    if ((rc = st.begin(c, stream))) return rc;  // (link boxes start empty; afterwards the last stage re-arms them)
     for (int q0 = 0; q0 < Q; q0 += Qc) {
         const int nq = std::min(Qc, Q - q0), Bk = nq * S;
         const VbRecs recs = vb_recs(ctx->sc_entries.ptr, Bk, NC);
         const VbVertexGrid vg = vb_vertex_grid(ctx->num_cus, nitems, Bk);
         StepHead none = {};
         vb_vertex_kernel<false><<<dim3(vg.gx * Bk), 256, 0, stream>>>(verts, vert_link, tris, cl, none, const_cast<float*>(mvp) + (size_t)q0 * S * L * 16,
-                                                                   V, nvb, g, posc, recs, lbox, (int*)tcov, Bk * g.nt * 8, meta, Bk, vg.gx,
-                                                                   vg.xcd_views, hv, VB_ROLE_FIRST_CHUNK | VB_ROLE_POS_ONLY);
+                                                                   V, nvb, g, posc, recs, m.lbox, (int*)m.tcov, Bk * g.nt * 8, m.meta, Bk, vg.gx,
+                                                                   vg.xcd_views, m.hv, VB_ROLE_FIRST_CHUNK | VB_ROLE_POS_ONLY);
         EHR_LAUNCH_CHECK();
         VbJobParams jp = {};
-        jp.g = g; jp.B = Bk; jp.cl = cl; jp.si = si; jp.rc = recs; jp.lbox = lbox; jp.hv = hv;  // (use_hint = 0)
-        jp.rq.verts = verts; jp.rq.posc = posc; jp.rq.V = V; jp.rq.meta = meta;
+        jp.g = g; jp.B = Bk; jp.cl = cl; jp.si = si; jp.rc = recs; jp.lbox = m.lbox; jp.hv = m.hv;  // (use_hint = 0)
+        jp.rq.verts = verts; jp.rq.posc = posc; jp.rq.V = V; jp.rq.meta = m.meta;
         jp.rq.mvp = mvp + (size_t)q0 * S * L * 16;
-        jp.co = {tcov, sticky, S};
+        jp.co = {m.tcov, m.sticky, S};
         jp.heavy_t = 0x7fffffff;
         jp.med_t0 = 0x7fffffff;
         vb_job_kernel<true><<<job_wgs, 256, 0, stream>>>(jp);
         EHR_LAUNCH_CHECK();
-        unsigned long long* const sacc = sacc0 + (size_t)flip * 16 * Qc;
-        vb_score_count_kernel<<<std::min((nq * g.nt + 3) / 4, VB_SCORE_COUNT_GRID * ctx->num_cus), 256, 0, stream>>>(
-            g, nq, S, tcov, sacc, count ? count + (size_t)q0 * H * W : nullptr, lbox, VB_LBOX_STRIDE * Bc * L, prev_sacc, prev_score, prev_nq);
+        if ((rc = st.chunk(c, q0, nq, stream))) return rc;
+    }
+    if ((rc = st.end(c, stream))) return rc;
+    EHR_HIP(hipMemcpyAsync(ctx->host_pinned, m.sticky, sizeof(int), hipMemcpyDeviceToHost, stream));
+    EHR_HIP(hipMemcpyAsync(ctx->host_pinned + 1, m.meta + EHR_META_OVERFLOW, sizeof(int), hipMemcpyDeviceToHost, stream));
+    EHR_HIP(hipStreamSynchronize(stream));
+    if (ctx->host_pinned[0] || ctx->host_pinned[1])  // a triangle needs the exact z-buffer: the other path redoes the call
+        return must ? fail(EHR_ERR_INVALID, "%s: EHR_SCORE_PATH=chain, but a triangle needs the exact z-buffer", st.op) : EHR_OK;
+    *handled = 1;
+    return EHR_OK;
+}
+
+// Last stage of the scoring op: vb_score_count_kernel, sums collected per chunk in m.sacc and handed to `score` by the
+// next launch.
+struct VbVarianceStage {
+    const char* op = "ehr_mask_variance";
+    long long* score;
+    unsigned char* count;
+    int Q, H, W;
+    unsigned long long* prev_sacc = nullptr;
+    long long* prev_score = nullptr;
+    int prev_nq = 0, flip = 0;
+    size_t own_bytes(int, int) const { return 0; }
+    int begin(const VbCovChunk& c, hipStream_t stream) {
+        EHR_HIP(hipMemsetAsync(c.m.sacc, 0, 2 * 16 * (size_t)c.Qc * sizeof(unsigned long long), stream));
+        EHR_HIP(hipMemsetAsync(score, 0, (size_t)Q * sizeof(long long), stream));
+        if (count) EHR_HIP(hipMemsetAsync(count, 0, (size_t)Q * H * W, stream));
+        vb_score_count_kernel<<<64, 256, 0, stream>>>(c.g, 0, c.S, c.m.tcov, c.m.sacc, nullptr, c.m.lbox, c.nlbox, c.m.sacc, score, 0);
+        EHR_LAUNCH_CHECK();
+        prev_sacc = c.m.sacc;
+        prev_score = score;
+        return EHR_OK;
+    }
+    int chunk(const VbCovChunk& c, int q0, int nq, hipStream_t stream) {
+        unsigned long long* const sacc = c.m.sacc + (size_t)flip * 16 * c.Qc;
+        vb_score_count_kernel<<<std::min((nq * c.g.nt + 3) / 4, VB_SCORE_COUNT_GRID * c.num_cus), 256, 0, stream>>>(
+            c.g, nq, c.S, c.m.tcov, sacc, count ? count + (size_t)q0 * H * W : nullptr, c.m.lbox, c.nlbox, prev_sacc, prev_score, prev_nq);
         EHR_LAUNCH_CHECK();
         prev_sacc = sacc;
         prev_score = score + q0;
         prev_nq = nq;
         flip ^= 1;
+        return EHR_OK;
     }
-    vb_score_count_kernel<<<1, 256, 0, stream>>>(g, 0, S, tcov, sacc0, nullptr, lbox, 0, prev_sacc, prev_score, prev_nq);
-    EHR_LAUNCH_CHECK();
-    EHR_HIP(hipMemcpyAsync(ctx->host_pinned, sticky, sizeof(int), hipMemcpyDeviceToHost, stream));
-    EHR_HIP(hipMemcpyAsync(ctx->host_pinned + 1, meta + EHR_META_OVERFLOW, sizeof(int), hipMemcpyDeviceToHost, stream));
-    EHR_HIP(hipStreamSynchronize(stream));
-    if (ctx->host_pinned[0] || ctx->host_pinned[1])  // a triangle needs the exact z-buffer: the other path redoes the call
-        return must ? fail(EHR_ERR_INVALID, "ehr_mask_variance: EHR_SCORE_PATH=chain, but a triangle needs the exact z-buffer") : EHR_OK;
-    *handled = 1;
-    return EHR_OK;
+    int end(const VbCovChunk& c, hipStream_t stream) {
+        vb_score_count_kernel<<<1, 256, 0, stream>>>(c.g, 0, c.S, c.m.tcov, c.m.sacc, nullptr, c.m.lbox, 0, prev_sacc, prev_score, prev_nq);
+        EHR_LAUNCH_CHECK();
+        return EHR_OK;
+    }
+};
+
+int ehr::vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp, int Q,
+                    int S, int L, int V, int T, int H, int W, long long* score, unsigned char* count, hipStream_t stream,
+                    int* handled) {
+    VbVarianceStage st;
+    st.score = score; st.count = count; st.Q = Q; st.H = H; st.W = W;
+    return vb_cov_chain(ctx, verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, stream, handled, st);
+}
+
+// Last stage of the pose search: the observed masks packed once per call (begin), then vb_overlap_count_kernel per chunk,
+// sums collected in VbOverlapMisc::oacc and handed to `overlap` [Q][S][2] by the next launch.
+constexpr int VB_OVERLAP_WAVE_ITEMS = 32;  // (candidate, tile) items a wave of the count kernel owns, at least: a candidate's
+                                           // line then takes nt / 32 atomics (113 at 1280x720) instead of one per tile
+struct VbOverlapStage {
+    const char* op = "ehr_mask_overlap";
+    const float* ref;
+    long long* overlap;
+    long long* ref_area;
+    int Q, S;
+    VbOverlapMisc o = {};
+    unsigned long long* prev_oacc = nullptr;
+    long long* prev_out = nullptr;
+    int prev_n = 0, flip = 0;
+    size_t own_bytes(int Bc, int nt) const {
+        size_t bytes;
+        vb_overlap_misc(nullptr, Bc, S, nt, &bytes);
+        return bytes;
+    }
+    int begin(const VbCovChunk& c, hipStream_t stream) {
+        o = vb_overlap_misc(c.m.own, c.Bc, c.S, c.g.nt);
+        EHR_HIP(hipMemsetAsync(o.oacc, 0, 2 * 16 * (size_t)c.Bc * sizeof(unsigned long long), stream));
+        EHR_HIP(hipMemsetAsync(overlap, 0, (size_t)Q * c.S * 2 * sizeof(long long), stream));
+        EHR_HIP(hipMemsetAsync(ref_area, 0, (size_t)c.S * sizeof(long long), stream));
+        vb_overlap_pack_ref_kernel<<<dim3(std::min((c.g.nt + 3) / 4, 16), c.S), 256, 0, stream>>>(c.g, ref, o.rbits,
+                                                                                                  (unsigned long long*)ref_area);
+        EHR_LAUNCH_CHECK();
+        vb_overlap_count_kernel<<<64, 256, 0, stream>>>(c.g, 0, c.S, 1, c.m.tcov, o.rbits, o.oacc, c.m.lbox, c.nlbox, o.oacc, overlap, 0);
+        EHR_LAUNCH_CHECK();
+        prev_oacc = o.oacc;
+        prev_out = overlap;
+        return EHR_OK;
+    }
+    int chunk(const VbCovChunk& c, int q0, int nq, hipStream_t stream) {
+        unsigned long long* const oacc = o.oacc + (size_t)flip * 16 * c.Bc;
+        const long long total = (long long)nq * c.g.nt;
+        const long long max_waves = 4ll * VB_SCORE_COUNT_GRID * c.num_cus;
+        const int per_wave = (int)std::max<long long>(VB_OVERLAP_WAVE_ITEMS, (total + max_waves - 1) / max_waves);
+        const int wgs = (int)((total + 4ll * per_wave - 1) / (4ll * per_wave));
+        vb_overlap_count_kernel<<<wgs, 256, 0, stream>>>(c.g, nq, c.S, per_wave, c.m.tcov, o.rbits, oacc, c.m.lbox, c.nlbox, prev_oacc,
+                                                         prev_out, prev_n);
+        EHR_LAUNCH_CHECK();
+        prev_oacc = oacc;
+        prev_out = overlap + (size_t)q0 * c.S * 2;
+        prev_n = nq * c.S;
+        flip ^= 1;
+        return EHR_OK;
+    }
+    int end(const VbCovChunk& c, hipStream_t stream) {
+        vb_overlap_count_kernel<<<1, 256, 0, stream>>>(c.g, 0, c.S, 1, c.m.tcov, o.rbits, o.oacc, c.m.lbox, 0, prev_oacc, prev_out, prev_n);
+        EHR_LAUNCH_CHECK();
+        return EHR_OK;
+    }
+};
+
+int ehr::vbuf_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+                      const float* ref, int Q, int S, int L, int V, int T, int H, int W, long long* overlap, long long* ref_area,
+                      hipStream_t stream, int* handled) {
+    VbOverlapStage st;
+    st.ref = ref; st.overlap = overlap; st.ref_area = ref_area; st.Q = Q; st.S = S;
+    return vb_cov_chain(ctx, verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, stream, handled, st);
 }
 
 // Binds a reference mask to the plan (ehr_fused_bind_ref): one pass stores per (view, tile) the fixed-point sum(ref^2)

@@ -341,6 +341,29 @@ int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t* tris, con
                       const float* mvp, int Q, int S, int L, int V, int T, int H, int W, int64_t* score,
                       uint8_t* count, int chunk_views, void* stream);
 
+/* Pose search: mask overlap of Q candidate camera poses with the observed masks of S real views -- the question the local
+ * solve cannot answer, "which of these few thousand candidate poses is most worth refining?".  The render rule is exactly
+ * ehr_mask_variance's (packed mesh, no antialiasing, a pixel is set iff its nearest fragment has z/w > 0); a pixel of ref
+ * is foreground iff ref > 0.5f (NaN is background; dataset masks are 0/1 floats, so any threshold inside (0, 1) agrees).
+ *   mvp [Q,S,L,16]: candidate pose q seen in real view s, = proj(K) @ opencv2blender @ Tc_c2b[q] @ link_pose[s,l];
+ *   ref [S,H,W] float32 observed masks, row 0 = top (the form ehr_render_mask_loss takes);
+ *   overlap [Q,S,2] int64 (device): {inter, area} with area = |render|, inter = |render & ref_s|;
+ *   ref_area [S] int64 (device): |ref_s|.
+ * From these, |render xor ref| = area + ref_area - 2 inter is the SSE the solver minimises, without antialiasing, and
+ * inter / (area + ref_area - inter) the silhouette IoU.  All outputs are exact integers, independent of launch order.
+ * Same two implementations, same conditions and same argument limits as ehr_mask_variance.  On the solver's machinery
+ * the masks are packed once per call into the bit layout of the job kernel's coverage words (32 bytes per view and
+ * 32x8 tile), and per chunk of candidates a count kernel ANDs and popcounts the words: no image reaches memory and no
+ * float atomic is used.  If coverage cannot decide a pixel (see above), the WHOLE call is redone by the per-triangle tile
+ * implementation on the Q x S single-pose views, in passes of at most chunk_views views (<= 0: default 512), each reduced
+ * against ref to the same integers.  EHR_SCORE_PATH=tile / =chain means the same thing.
+ * Like ehr_mask_variance the call synchronises (the mesh's content hash at the start, the "coverage could not decide" flag
+ * at the end, the queue sizes of every pass of the exact path) and may allocate: it is NOT capturable in a hipGraph.
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+int ehr_mask_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+                     const float* ref, int Q, int S, int L, int V, int T, int H, int W, int64_t* overlap,
+                     int64_t* ref_area, int chunk_views, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
