@@ -11,8 +11,10 @@ namespace ehr {
 // Per-view sums (frame loss, 12 gradient numbers per link) are accumulated in 64-bit FIXED POINT with integer atomics:
 // integer addition is associative, so the result does not depend on which workgroup adds first -- bit-reproducible like
 // a fixed-order reduction, but without a reduction pass over all tiles.  Scale 2^32: addends are rounded to 2.3e-10
-// (absolute), sums up to +-2.1e9 fit; larger magnitudes raise the overflow flag (loss = NaN), never wrap silently.
-// The flag is raised with an atomic: the finish stage reads it inside the same launch.
+// (absolute), sums up to +-2.1e9 fit.  The guard below is PER ADDEND: an addend of 1e9 or more (or a NaN) raises the
+// overflow flag (loss = NaN).  The total is not guarded: many addends below 1e9 can take it past 2^31 and wrap.  The
+// contract is that a view's SSE (and each gradient sum) stays below 2^31, which any mask in a bounded range meets by orders
+// of magnitude.  The flag is raised with an atomic: the finish stage reads it inside the same launch.
 #define EHR_FIX_SCALE 4294967296.0
 __device__ __forceinline__ long long fix_of(float v) { return __double2ll_rn((double)v * EHR_FIX_SCALE); }
 __device__ __forceinline__ void fix_add(long long* acc, float v, int* meta) {

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import fused_loss_reference
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +56,9 @@ def test_fused_matches_oracle(env, oracle, xarm7, H, W, scale, B):
     assert np.abs(loss - l_ref).max() <= 1e-6 * np.abs(l_ref).max()  # float vs double accumulation
     assert np.abs(grad - g_ref).max() <= 1e-5 * np.abs(g_ref).max()
     assert (grad[:, :, 2, :] == 0).all()
+    if H < 720:   # every (view, link) block against its own bar (the 720p case: oracle time for no new coverage)
+        blocks = fused_loss_reference.block_reference(oracle, xarm7.meshes, mvp, ref)
+        fused_loss_reference.check_blocks(grad, blocks, f"test_fused_matches_oracle {H}x{W}")
 
 
 def test_fused_slow_tiles_match_oracle(env, oracle, xarm7):
@@ -135,6 +139,7 @@ def test_span_walker_on_slivers_and_axis_aligned_edges(env, oracle):
     assert (mask == m_ref).all()
     assert np.abs(loss - l_ref).max() <= 1e-6 * np.abs(l_ref).max()
     assert np.abs(grad - g_ref).max() <= 1e-5 * np.abs(g_ref).max()
+    fused_loss_reference.check_blocks(grad, fused_loss_reference.block_reference(oracle, [(v, f)], mvp, ref), "span walker")
 
 
 def test_fused_golden_fixtures(env, xarm7):
