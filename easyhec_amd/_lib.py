@@ -59,6 +59,7 @@ SIGNATURES = {
     "ehr_solver_step_multi": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float] * 2 + [c_void_p] * 5 + [c_int, c_void_p] +
                               [c_float] * 5 + [c_void_p] * 8 + [c_void_p]),
     "ehr_fused_bind_ref_shared": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "ehr_fused_bind_weight": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_mask_variance": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_mask_overlap": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_comm_unique_id": (c_int, [c_void_p]),
@@ -110,6 +111,14 @@ def has_pose_search():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_overlap")
+
+
+def has_weighted_loss():
+    """True if the library has the per-pixel weights of the mask loss (``ehr_fused_bind_weight``); the symbol's presence is
+    the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_fused_bind_weight")
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

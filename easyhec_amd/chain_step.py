@@ -5,7 +5,8 @@ slot-limited plan overflowed, or the view needs the general-triangle pass) -- th
 recovery, and the loop that takes an exact number of effective steps.
 
 A subclass sets ``glctx``, ``scene``, ``dev``, ``H``, ``W``, ``B`` (the views the plan holds), ``ref`` (the masks, shared by
-``B / ref.shape[0]`` poses) and ``loss`` (one element per pose), provides ``_enqueue(want_mask, stream=None)`` and
+``B / ref.shape[0]`` poses), ``weight`` (per-pixel weights of the loss shaped like ``ref``, or None) and ``loss`` (one element
+per pose), provides ``_enqueue(want_mask, stream=None)`` and
 ``steps_done`` (Adam's own counter, which only advances on real steps; reading it synchronises), and ends its constructor
 with :meth:`_init_chain`."""
 import ctypes
@@ -45,7 +46,11 @@ class _ChainStep:
     def _plan_and_bind(self):
         fused._ensure_plan(self.glctx, self.scene, self.B, self.H, self.W, slack=self.slack)
         # the reference masks are constants of the solve: the loss of the tiles no link touches is cached once
-        # (bit-identical results).  self.ref is this object's private copy, never written to.
+        # (bit-identical results).  self.ref is this object's private copy, never written to.  The weights, if any, first:
+        # binding them unbinds the reference, whose cached sums are sums of w ref^2.
+        weight = getattr(self, "weight", None)
+        if weight is not None or getattr(self.glctx, "_bound_weight", None) is not None:
+            fused.bind_weight(self.glctx, self.scene, weight, views=self.B)
         fused.bind_ref(self.glctx, self.scene, self.ref, views=self.B)
 
     def _host_copies_stale(self):
@@ -55,6 +60,14 @@ class _ChainStep:
         """Enqueue one optimisation step.  Returns the (device) mean mask loss of every pose, evaluated BEFORE the update
         like ``loss`` in trainer/rbsolver.py:33-41; all NaN for a reported step.  Never synchronises."""
         self._host_copies_stale()
+        if getattr(self.glctx, "_bound_weight", None) is not getattr(self, "weight", None):
+            # the weights are state of the CONTEXT, and somebody else used it since (the model's forward with other
+            # weights, or none): bind this solve's again -- never step on weights that are not its own
+            had_graph = bool(self._graph)
+            self.release_graph()
+            self._plan_and_bind()
+            if had_graph:
+                self.capture()
         with torch.cuda.device(self.dev):
             if self._graph and not want_mask:
                 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -111,7 +124,7 @@ class _ChainStep:
         """Call when a step's loss came back NaN (for every pose).  Synchronises.  If the context reports that the step
         needed the general-triangle pass (EHR_ERR_RETRY: the context launches it from now on) the graph, if any, is
         re-captured; if it reports an overflow and the plan was slot-limited, plans again with a slot for every (view, link,
-        tile), re-binds the reference masks and re-captures.  Returns what it did (a non-empty string) in both cases, False
+        tile), re-binds the weights and the reference masks and re-captures.  Returns what it did (a non-empty string) in both cases, False
         if the context reports nothing: the steps since the report changed nothing (dof, Adam moments and step counter stay
         untouched on a NaN, and the chain's head writes the unchanged pose to the SAME history row again: include/ehr.h,
         ehr_solver_step), so the caller simply goes on stepping.  Raises on any other overflow."""

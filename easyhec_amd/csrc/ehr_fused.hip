@@ -177,6 +177,28 @@ int ehr_fused_bind_ref_shared(ehr_ctx* ctx, const float* ref, int Bv, void* stre
     return vbuf_bind_ref(ctx, ref, Bv, (hipStream_t)stream);
 }
 
+int ehr_fused_bind_weight(ehr_ctx* ctx, const float* weight, int Bv, void* stream) {
+    (void)stream;  // (nothing is enqueued: the weights are read by the calls that follow, and by the next ehr_fused_bind_ref)
+    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_fused_bind_weight: ctx is NULL");
+    if (ctx->capturing) return fail(EHR_ERR_INVALID, "ehr_fused_bind_weight: not inside a graph capture");
+    if (weight) {
+        if (ctx->pB == 0) return fail(EHR_ERR_INVALID, "ehr_fused_bind_weight: call ehr_fused_plan first");
+        if (Bv <= 0 || ctx->pB % Bv != 0)
+            return fail(EHR_ERR_INVALID, "ehr_fused_bind_weight: the plan's %d views are not a multiple of %d", ctx->pB, Bv);
+    }
+    // A captured chain has the weighted or the unweighted kernels and the weights' pointer baked in: the graph goes, as
+    // under ehr_fused_bind_ref.  A bound reference's cached sums are sums of w ref^2: they are stale, so the reference is
+    // unbound (calls take the unbound path until the caller binds it again, which then caches the weighted sums).
+    if (ctx->gexec) {
+        EHR_HIP(hipGraphExecDestroy(ctx->gexec));
+        ctx->gexec = nullptr;
+    }
+    ctx->vb_ref = nullptr;
+    ctx->vb_weight = weight;
+    ctx->vb_weight_views = weight ? Bv : 0;
+    return EHR_OK;
+}
+
 int ehr_fused_status(ehr_ctx* ctx) {
     if (!ctx) return fail(EHR_ERR_INVALID, "ehr_fused_status: ctx is NULL");
     if (ctx->pB == 0) return EHR_OK;

@@ -129,6 +129,8 @@ struct ehr_ctx {
     const float* vb_ref = nullptr;  // the reference mask those sums belong to (ehr_fused_bind_ref), or NULL
     int vb_ref_views = 0;    // images `vb_ref` holds: pB, or fewer where hypotheses share them (ehr_fused_bind_ref_shared: the
                              // sums are then tiled, view b's are those of image b % vb_ref_views)
+    const float* vb_weight = nullptr;  // per-pixel weights of the loss, [vb_weight_views][H][W] (ehr_fused_bind_weight), or NULL: sticky,
+    int vb_weight_views = 0;           // read by every fused call on this plan; view b reads image b % vb_weight_views
     ehr::Scratch vb_hstate;  // i32 [16], survives re-plans: [0] Adam's step counter + 1 as the previous solver step's head saw
                              // it, [1] whether that head advanced the history cursor, [2] where it left it (a REPORTED step's row is reused)
     ehr::Scratch vb_hstate_m;  // i32 [pB][VB_HSTATE_INTS]: the same per hypothesis of a multi-start step (ehr_solver_step_multi; kept

@@ -1795,7 +1795,37 @@ struct VbCompArgs {
 struct VbSharedRef {
     int view0, nviews;
 };
-template <bool FILL, bool SHARED = false>
+// The bound per-pixel weights of the loss (ehr_fused_bind_weight): `nviews` images [H][W], row 0 = top; the
+// chunk's view b is view view0 + b of the call and reads image (view0 + b) % nviews -- the reference's sharing rule with the
+// weights' own count.  The kernels' LAST parameter, behind StepTail / VbSharedRef, and never copied into VbCompArgs (see
+// there): the WEIGHTED instantiations read it in place, through the kernarg pointer, where a tile needs it; the others
+// never look at it.
+struct VbWeight {
+    const float* w;
+    int view0, nviews;
+};
+struct VbCompParamsW;  // (the composite kernel's kernarg segment down to the weights: below, with VbCompParams)
+typedef const VbCompParamsW __attribute__((address_space(4)))* VbCompParamsWPtr;
+__device__ __forceinline__ VbCompParamsWPtr vb_comp_params_w();
+__device__ __forceinline__ VbWeight vb_comp_weight(VbCompParamsWPtr p);
+// a lane's four weights of a tile row (the reference's read: one float4 where vec_ok, which then also vouches for `w`)
+__device__ __forceinline__ void vb_read_weights(const VbWeight& wt, int b, int H, int W, int row, int ix, const bool* pin, int vec_ok, float* wf) {
+    const size_t imw = ((size_t)((wt.view0 + b) % wt.nviews) * H + row) * W + ix;
+    if (vec_ok) {
+        if (pin[0]) {
+            const float4 w4 = *reinterpret_cast<const float4*>(wt.w + imw);
+            wf[0] = w4.x; wf[1] = w4.y; wf[2] = w4.z; wf[3] = w4.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (pin[j]) wf[j] = wt.w[imw + j];
+    }
+}
+// WEIGHTED: loss = sum w (mask - ref)^2 with the bound weights; per pixel  e = m - r; we = w * e; e2 += we * e;
+// gv = gate ? 2 we : 0  (w == 1.0f: the unweighted expression bit for bit).  The unweighted instantiations are the code
+// they were before the weights existed.
+template <bool FILL, bool SHARED = false, bool WEIGHTED = false>
 __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const int* s_jbase, const unsigned* s_utile, float* gpix,
                                                    int xcd, int wslot, int nslots, int nwg, VbSharedRef sh = {0, 1}) {
     const BinGeom& g = C.g;
@@ -1820,6 +1850,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     const int acc_stride = vb_acc_stride(L, nls);
     const int r = lane >> 3, c4 = (lane & 7) * 4;
     const float invL = __builtin_amdgcn_rcpf((float)L);  // (u / L by vb_div_small)
+    const VbCompParamsWPtr wparams = vb_comp_params_w();  // (WEIGHTED: where the weights' descriptor is read from)
     for (int item = ibeg + wslot; item < iend; item += istep) {
     int b, tx, ty;
     if (sparse) {
@@ -1904,6 +1935,8 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         for (int j = 0; j < 4; j++)
             if (pin[j]) rf[j] = ref[imr + j];
     }
+    float wf[4] = {0.f, 0.f, 0.f, 0.f};
+    if (WEIGHTED) vb_read_weights(vb_comp_weight(wparams), b, H, W, H - 1 - (row_in ? iy : 0), ix, pin, vec_ok, wf);
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     unsigned todo = tmask;
     while (todo) {  // sum in link order
@@ -1926,8 +1959,14 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         if (pin[j]) {
             const float m = acc[j] > 1.f ? 1.f : acc[j];
             const float e = m - rf[j];
-            e2 += e * e;
-            gv[j] = (acc[j] <= 1.f) ? 2.f * e : 0.f;
+            if (WEIGHTED) {
+                const float we = wf[j] * e;
+                e2 += we * e;
+                gv[j] = (acc[j] <= 1.f) ? 2.f * we : 0.f;
+            } else {
+                e2 += e * e;
+                gv[j] = (acc[j] <= 1.f) ? 2.f * e : 0.f;
+            }
             mv[j] = m;
         }
     }
@@ -2465,9 +2504,12 @@ vb_slow_kernel(VbResolveArgs Q, VbRecs rc, int NC, const int4* __restrict__ cvid
 // not change during a solve, so these are constants of the solve (ehr_fused_bind_ref); with them the composite kernel only
 // visits tiles inside the view's link boxes and adds fix(new) - cached there.  Integer sums are associative: bit-identical
 // to streaming every tile.
+// WEIGHTED (weights bound, ehr_fused_bind_weight): the cached value is sum(w ref^2), with the composite's own expression
+// (e = 0 - r; we = w * e; e2 += we * e); view b of this launch is view wt.view0 + b of the plan.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256)
 vb_refsum_kernel(BinGeom g, int B, const float* __restrict__ ref, int vec_ok, long long* __restrict__ tsum,
-                 long long* __restrict__ vtot, int* __restrict__ flag) {
+                 long long* __restrict__ vtot, int* __restrict__ flag, VbWeight wt) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gw = blockIdx.x * 4 + wave;
     if (gw >= B * g.nt) return;
@@ -2492,12 +2534,19 @@ vb_refsum_kernel(BinGeom g, int B, const float* __restrict__ ref, int vec_ok, lo
         for (int j = 0; j < 4; j++)
             if (pin[j]) rf[j] = ref[im + j];
     }
+    float wf[4] = {0.f, 0.f, 0.f, 0.f};
+    if (WEIGHTED) vb_read_weights(wt, b, H, W, H - 1 - (row_in ? iy : 0), ix, pin, vec_ok, wf);
     float e2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; j++)
         if (pin[j]) {
             const float e = 0.f - rf[j];
-            e2 += e * e;
+            if (WEIGHTED) {
+                const float we = wf[j] * e;
+                e2 += we * e;
+            } else {
+                e2 += e * e;
+            }
         }
     const float s = wave_sum(e2);
     if (lane == 0) {
@@ -2516,6 +2565,22 @@ struct VbCompParams {
     VbCompArgs C;
     StepTail tail;
 };
+struct VbCompParamsW {  // ... and as a WEIGHTED instantiation reads its last parameter
+    VbCompArgs C;
+    StepTail tail;
+    VbSharedRef sh;
+    VbWeight wt;
+};
+__device__ __forceinline__ VbCompParamsWPtr vb_comp_params_w() {
+    return (VbCompParamsWPtr)__builtin_amdgcn_kernarg_segment_ptr();
+}
+__device__ __forceinline__ VbWeight vb_comp_weight(VbCompParamsWPtr p) {
+    VbWeight wt;
+    wt.w = p->wt.w;
+    wt.view0 = p->wt.view0;
+    wt.nviews = p->wt.nviews;
+    return wt;
+}
 typedef const VbCompParams __attribute__((address_space(4)))* VbCompParamsPtr;
 __device__ __forceinline__ VbCompParamsPtr vb_comp_params() {
     VbCompParamsPtr p = (VbCompParamsPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -2547,10 +2612,11 @@ __device__ __forceinline__ int vb_comp_arrivals(int xcd, int per, int nitems, in
 //                 to is skipped without reading the reference -- its cached sum is already in vtot.  With a mask output
 //                 the tiles outside every rectangle are then filled with zeros (stores only, no reference read, no sums).
 // One designated workgroup of the call's last launch (the finisher, see below) runs the finish stage: accumulators ->
-// loss / grad_mvp [-> pose backward -> Adam]; the launch also re-arms the link boxes.  vec_ok: W % 4 == 0 and 16-byte aligned images.
-template <bool TAIL, bool FILL, bool SHARED = false>
+// loss / grad_mvp [-> pose backward -> Adam]; the launch also re-arms the link boxes.  vec_ok: W % 4 == 0 and 16-byte aligned images
+// (reference, mask output and, where bound, weights).
+template <bool TAIL, bool FILL, bool SHARED = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(256, FILL ? 5 : 6)
-vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh) {
+vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh, VbWeight wt) {
     __shared__ float gpix_all[4][EHR_TILE_W * EHR_TILE_H];
     extern __shared__ int s_dyn[];  // [U + 1] first job of every (view, link) | [U] its tile range
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2569,7 +2635,7 @@ vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh) {
             C.lbox_all[i] = (i & 2) ? INT_MIN : INT_MAX;  // one line per box: min x, min y, max x, max y, padding
     __syncthreads();
     const int nwg = gridDim.x, xcd = blockIdx.x & (VB_XCDS - 1);
-    vb_composite_items<FILL, SHARED>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> VB_XCD_BITS) * 4 + wave, (nwg >> VB_XCD_BITS) * 4, nwg, sh);
+    vb_composite_items<FILL, SHARED, WEIGHTED>(C, s_jbase, s_utile, gpix, xcd, (int)(blockIdx.x >> VB_XCD_BITS) * 4 + wave, (nwg >> VB_XCD_BITS) * 4, nwg, sh);
     // ---- the finish stage: ONE designated workgroup, the finisher, runs it once every other workgroup's atomics have
     //      been performed.  A workgroup that had work waits for its own atomics (vmcnt covers them), then one lane adds 1
     //      to its XCD's arrival counter -- no value comes back, nobody waits for one -- and the workgroup is done.  A
@@ -3099,6 +3165,8 @@ int ehr::vbuf_plan(ehr_ctx* ctx, int B, int L, int V, int T, int H, int W, float
     {  // a bound reference mask's cached sums: tsum [B][nt] | vtot [B] | flag
         if ((rc = ctx->vb_refsum.reserve(((size_t)B * gp.nt + B + 1) * sizeof(long long)))) return rc;
         ctx->vb_ref = nullptr;  // a new plan forgets the binding
+        ctx->vb_weight = nullptr;  // ... and the weights (ehr_fused_bind_weight)
+        ctx->vb_weight_views = 0;
     }
     ctx->vb_jcap = (int)(jobs_per_view * Bc);
     vb_slots(nullptr, (size_t)ctx->vb_jcap, (size_t)Bc * L, &bytes);
@@ -3165,7 +3233,9 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         ctx->ev_used = need;
         EHR_HIP(hipEventRecord(ev[0], stream));
     }
-    const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0) && (!mask || ((uintptr_t)mask & 15) == 0);
+    const float* const weight = ctx->vb_weight;  // per-pixel weights of the loss (ehr_fused_bind_weight), or NULL
+    const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0) && (!mask || ((uintptr_t)mask & 15) == 0) &&
+                       (((uintptr_t)weight & 15) == 0);
     const int job_wgs = vb_xcd_round_up(ctx->num_cus * VB_JOB_GRID);
     hv.mcap = std::min(VB_MED_CAP, 2 * job_wgs);
     hv.heavy_base = VB_HEAVY_T_DEFAULT;
@@ -3262,20 +3332,29 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         ca.tsum = sparse ? tsum_all + (size_t)b0 * g.nt : nullptr;
         ca.ref_flag = ref_flag; ca.loss = loss; ca.grad_mvp = grad_mvp;
         ca.do_finish = (last_chunk && !multi) ? 1 : 0; ca.B_all = B; ca.facc_all = facc_all; ca.vtot_all = vtot_all; ca.lbox_all = lbox_all;
-#define VB_COMPOSITE(TAILV, FILLV, tailarg) vb_composite_kernel<TAILV, FILLV><<<nwg, 256, dyn, stream>>>(ca, tailarg, VbSharedRef{0, 1})
+        const VbWeight wt = {weight, b0, weight ? ctx->vb_weight_views : 1};  // (the weighted instantiations alone read it)
+#define VB_COMPOSITE_W(TAILV, FILLV, SHAREDV, tailarg, sharg)                                                      \
+    do {                                                                                                             \
+        if (weight)                                                                                                  \
+            vb_composite_kernel<TAILV, FILLV, SHAREDV, true><<<nwg, 256, dyn, stream>>>(ca, tailarg, sharg, wt);     \
+        else                                                                                                         \
+            vb_composite_kernel<TAILV, FILLV, SHAREDV><<<nwg, 256, dyn, stream>>>(ca, tailarg, sharg, wt);           \
+    } while (0)
+#define VB_COMPOSITE(TAILV, FILLV, tailarg) VB_COMPOSITE_W(TAILV, FILLV, false, tailarg, (VbSharedRef{0, 1}))
         StepTail none = {};
         if (multi) {  // (no finisher: vb_finish_multi_kernel follows the last chunk)
             const VbSharedRef sh = {b0, multi_views};
             if (fill)
-                vb_composite_kernel<false, true, true><<<nwg, 256, dyn, stream>>>(ca, none, sh);
+                VB_COMPOSITE_W(false, true, true, none, sh);
             else
-                vb_composite_kernel<false, false, true><<<nwg, 256, dyn, stream>>>(ca, none, sh);
+                VB_COMPOSITE_W(false, false, true, none, sh);
         } else if (tail) {
             if (fill) VB_COMPOSITE(true, true, *tail); else VB_COMPOSITE(true, false, *tail);
         } else {
             if (fill) VB_COMPOSITE(false, true, none); else VB_COMPOSITE(false, false, none);
         }
 #undef VB_COMPOSITE
+#undef VB_COMPOSITE_W
         EHR_LAUNCH_CHECK();
     }
     if (ev) EHR_HIP(hipEventRecord(ev[5], stream));
@@ -3580,10 +3659,15 @@ int ehr::vbuf_bind_ref(ehr_ctx* ctx, const float* ref, int views, hipStream_t st
     long long* tsum = (long long*)ctx->vb_refsum.ptr;
     long long* vtot = tsum + (size_t)B * g.nt;
     EHR_HIP(hipMemsetAsync(vtot, 0, ((size_t)B + 1) * sizeof(long long), stream));
-    const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0);
+    const float* const weight = ctx->vb_weight;  // bound weights: the cached sums are sum(w ref^2)
+    const int vec_ok = ((W & 3) == 0) && (((uintptr_t)ref & 15) == 0) && (((uintptr_t)weight & 15) == 0);
     const int nw = views * g.nt;
     for (int b0 = 0; b0 < B; b0 += views) {
-        vb_refsum_kernel<<<(nw + 3) / 4, 256, 0, stream>>>(g, views, ref, vec_ok, tsum + (size_t)b0 * g.nt, vtot + b0, (int*)(vtot + B));
+        const VbWeight wt = {weight, b0, weight ? ctx->vb_weight_views : 1};
+        if (weight)
+            vb_refsum_kernel<true><<<(nw + 3) / 4, 256, 0, stream>>>(g, views, ref, vec_ok, tsum + (size_t)b0 * g.nt, vtot + b0, (int*)(vtot + B), wt);
+        else
+            vb_refsum_kernel<false><<<(nw + 3) / 4, 256, 0, stream>>>(g, views, ref, vec_ok, tsum + (size_t)b0 * g.nt, vtot + b0, (int*)(vtot + B), wt);
         EHR_LAUNCH_CHECK();
     }
     ctx->vb_ref = ref;

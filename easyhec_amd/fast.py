@@ -77,6 +77,13 @@ def choose_exchange(rccl, p2p, comm_env, try_rccl, distributed, backend):
     return Exchange(try_p2p, try_p2p and bool(p2p), want_rccl, bool(rccl), distributed and rccl is None)
 
 
+def _private_weight(batch, dev):
+    """``batch["weight"]`` as a private contiguous float32 clone on ``dev`` (the sums ``bind_ref`` caches depend on it), or
+    None."""
+    w = batch.get("weight")
+    return None if w is None else w.to(dev, torch.float32).contiguous().clone()
+
+
 class FusedPoseStep(_ChainStep):
     def __init__(self, model, batch, lr=0.003, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0005, near=0.001, far=10.0,
                  process_group=None, rccl=None, slack=None, p2p=None):
@@ -90,10 +97,13 @@ class FusedPoseStep(_ChainStep):
         # a private copy, always (``.to`` / ``.contiguous`` return the caller's own tensor when nothing has to change, and
         # the sums cached by ``bind_ref`` must not go stale under an in-place edit of ``batch["mask"]``)
         self.ref = batch["mask"].to(dev, torch.float32).contiguous().clone()
+        # optional per-pixel weights of the loss (batch["weight"], 0 = an occluded or unreliable pixel): private like ref
+        self.weight = _private_weight(batch, dev)
         self.link_poses = batch["link_poses"].to(dev, torch.float32).contiguous()
         self.K = batch["K"][0].to(dev, torch.float32).contiguous()
         self.B, self.L = self.link_poses.shape[0], self.link_poses.shape[1]
         assert self.L == self.scene.num_links and self.ref.shape == (self.B, self.H, self.W)
+        assert self.weight is None or self.weight.shape == self.ref.shape
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.near, self.far = near, far
         self.pg = process_group

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib, dr
 
-__all__ = ["LinkScene", "render_mask_loss", "mvp_matrices"]
+__all__ = ["LinkScene", "render_mask_loss", "mvp_matrices", "bind_ref", "bind_weight"]
 
 
 class LinkScene:
@@ -70,6 +70,7 @@ def _ensure_plan(glctx, scene, B, H, W, slack=None):
     if not same or (slack is not None and getattr(plan, "slack", 0.0) != float(slack)):
         glctx._plan = _Plan(glctx, scene, B, H, W, slack=0.0 if slack is None else slack)
         glctx._bound_ref = None  # ehr_fused_plan forgets a bound reference mask
+        glctx._bound_weight = None  # ... and bound weights
 
 
 def check_status(glctx):
@@ -114,16 +115,34 @@ class _RenderMaskLoss(torch.autograd.Function):
         return None, None, grad * gloss[:, None, None, None], None, None
 
 
-def render_mask_loss(glctx, scene, mvp, ref, want_mask=True):
+def _same_tensor(a, b):
+    return a is b or (a is not None and b is not None and a.data_ptr() == b.data_ptr() and a.shape == b.shape)
+
+
+def render_mask_loss(glctx, scene, mvp, ref, want_mask=True, weight=None):
     """mvp [B,L,4,4] (= proj @ opencv2blender @ Tc_c2b @ link_pose), ref [B,H,W] float masks (row 0 = top).
     Returns ``(mask [B,H,W], loss [B])`` with ``loss[b] = sum((mask[b] - ref[b])**2)``; differentiable w.r.t. mvp
-    (the rendered mask is returned detached, as the reference only back-propagates the loss)."""
+    (the rendered mask is returned detached, as the reference only back-propagates the loss).
+
+    ``weight`` [B,H,W] (or [Bv,H,W] with Bv dividing B: view b reads image b % Bv), float, finite and >= 0: per-pixel
+    weights, ``loss[b] = sum(weight[b] * (mask[b] - ref[b])**2)`` -- 0 where the observed mask is not to be trusted
+    (:func:`bind_weight`; the mask returned does not depend on them).  The weights are state of the context: they are
+    bound when the argument differs from what is bound, and unbound when it is None while some are bound."""
     dr._check_dev("mvp", mvp, torch.float32)
     dr._check_dev("ref", ref, torch.float32)
     dr._require(mvp.dim() == 4 and mvp.shape[1] == scene.num_links and mvp.shape[2:] == (4, 4),
                 "mvp must have shape [B, num_links, 4, 4]")
     dr._require(ref.dim() == 3 and ref.shape[0] == mvp.shape[0], "ref must have shape [B, H, W]")
     dr._require(mvp.device == scene.device and ref.device == scene.device, "mvp/ref must be on the scene's device")
+    if weight is not None or getattr(glctx, "_bound_weight", None) is not None:
+        _ensure_plan(glctx, scene, ref.shape[0], ref.shape[1], ref.shape[2])  # (a new plan forgets the weights)
+        if weight is not None:
+            dr._check_dev("weight", weight, torch.float32)
+            dr._require(weight.dim() == 3 and weight.shape[1:] == ref.shape[1:] and weight.device == scene.device,
+                        "weight must have shape [Bv, H, W] on the scene's device")
+            weight = weight.contiguous()
+        if not _same_tensor(weight, getattr(glctx, "_bound_weight", None)):
+            bind_weight(glctx, scene, weight, views=ref.shape[0])
     return _RenderMaskLoss.apply(glctx, scene, mvp.contiguous(), ref.contiguous(), want_mask)
 
 
@@ -164,6 +183,32 @@ def bind_ref(glctx, scene, ref, views=None):
         _lib.check(_lib.lib().ehr_fused_bind_ref_shared(glctx.handle, _lib.ptr(ref), ref.shape[0], stream),
                    "ehr_fused_bind_ref")
     glctx._bound_ref = ref
+
+
+def bind_weight(glctx, scene, weight, views=None):
+    """Bind per-pixel weights [Bv,H,W] (float32, finite, >= 0, row 0 = top) to the context's plan
+    (``ehr_fused_bind_weight``): until the next call, every fused call on this context -- ``render_mask_loss``, the launch
+    chains of :class:`easyhec_amd.fast.FusedPoseStep` and :class:`easyhec_amd.multistart.MultiStartPoseStep` -- computes
+    ``sum(weight * (mask - ref)**2)``.  ``views``: how many views the plan holds, a multiple of ``weight.shape[0]``
+    (view b reads image b % Bv), as for :func:`bind_ref`.  The call UNBINDS a bound reference (its cached sums would be
+    stale): bind the weights first, then the reference.  The caller must not modify ``weight`` in place while it is bound;
+    ``weight=None`` unbinds.  The context keeps a reference to the tensor."""
+    if weight is None:
+        _lib.check(_lib.lib().ehr_fused_bind_weight(glctx.handle, None, 0, None), "ehr_fused_bind_weight")
+        glctx._bound_weight = None
+        glctx._bound_ref = None
+        return
+    dr._check_dev("weight", weight, torch.float32)
+    dr._require(weight.dim() == 3 and weight.is_contiguous(), "weight must be a contiguous [Bv, H, W] tensor")
+    views = weight.shape[0] if views is None else views
+    dr._require(views % weight.shape[0] == 0, "views must be a multiple of weight.shape[0]")
+    _ensure_plan(glctx, scene, views, weight.shape[1], weight.shape[2])
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with torch.cuda.device(glctx.device):
+        _lib.check(_lib.lib().ehr_fused_bind_weight(glctx.handle, _lib.ptr(weight), weight.shape[0], stream),
+                   "ehr_fused_bind_weight")
+    glctx._bound_weight = weight
+    glctx._bound_ref = None
 
 
 def set_timing(glctx, enable):

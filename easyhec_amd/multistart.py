@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .chain_step import _ChainStep
-from .fast import _f
+from .fast import _f, _private_weight
 from .se3 import se3_log_map
 from .synthetic import perturb_pose
 
@@ -81,10 +81,12 @@ class MultiStartPoseStep(_ChainStep):
         self.dev = dev
         self.H, self.W = model.H, model.W
         self.ref = batch["mask"].to(dev, torch.float32).contiguous().clone()  # private: its cached sums must not go stale
+        self.weight = _private_weight(batch, dev)  # optional per-pixel weights [Bv,H,W], shared by the hypotheses like ref
         self.link_poses = batch["link_poses"].to(dev, torch.float32).contiguous()
         self.K = batch["K"][0].to(dev, torch.float32).contiguous()
         self.Bv, self.L = self.link_poses.shape[0], self.link_poses.shape[1]
         assert self.L == self.scene.num_links and self.ref.shape == (self.Bv, self.H, self.W)
+        assert self.weight is None or self.weight.shape == self.ref.shape
         self.dof = _starts_to_dof(starts).to(dev)
         self.P = self.dof.shape[0]
         self.B = self.P * self.Bv  # virtual views

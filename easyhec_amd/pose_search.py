@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from .multistart import rank_losses, sample_starts, solve_multistart
 
-__all__ = ["mask_overlap", "overlap_scores", "candidate_mvps", "search_starts", "solve_global", "PoseSearchResult"]
+__all__ = ["mask_overlap", "mask_overlap_valid", "overlap_scores", "candidate_mvps", "search_starts", "solve_global", "PoseSearchResult"]
 
 
 def mask_overlap(glctx, scene, mvp, ref, chunk_views=0):
@@ -50,6 +50,20 @@ def mask_overlap(glctx, scene, mvp, ref, chunk_views=0):
                                                scene.num_verts, scene.num_tris, H, W, _lib.ptr(overlap), _lib.ptr(ref_area),
                                                int(chunk_views), stream), "ehr_mask_overlap")
     return overlap[..., 0], overlap[..., 1], ref_area
+
+
+def mask_overlap_valid(glctx, scene, mvp, ref, weight, chunk_views=0):
+    """:func:`mask_overlap` restricted to the pixels a per-pixel loss weight trusts, ``valid = weight > 0`` ([S,H,W], the
+    ``batch['weight']`` of a weighted solve): ``inter`` = |render & ref & valid|, ``area`` = |render & valid|, ``ref_area`` =
+    |ref & valid|, so that :func:`overlap_scores` gives ``xor_valid = |render & valid| + |ref & valid| - 2 |render & ref &
+    valid|`` and the IoU on the valid pixels.  Two ``ehr_mask_overlap`` calls, exact integers: one against ``valid`` as the
+    reference, one against ``ref & valid``."""
+    if weight.shape != ref.shape or weight.device != ref.device:
+        raise ValueError("weight must have ref's shape and device")
+    valid = (weight > 0).float()
+    area_v, _, _ = mask_overlap(glctx, scene, mvp, valid, chunk_views=chunk_views)
+    inter_v, _, ref_area_v = mask_overlap(glctx, scene, mvp, (ref > 0.5).float() * valid, chunk_views=chunk_views)
+    return inter_v, area_v, ref_area_v
 
 
 def overlap_scores(inter, area, ref_area):
@@ -91,7 +105,9 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
     """Scores Q candidate poses around ``Tc_init`` (:func:`easyhec_amd.multistart.sample_starts`: candidate 0 is ``Tc_init``
     itself; ``extra`` [E,4,4]: further poses of the caller's, scored after them) against ``batch['mask']`` in one
     :func:`mask_overlap` call and returns the P starts for :func:`easyhec_amd.multistart.solve_multistart`: start 0 is
-    ALWAYS ``Tc_init``, then the best P - 1 other candidates by ``xor`` (ascending, ties by index)."""
+    ALWAYS ``Tc_init``, then the best P - 1 other candidates by ``xor`` (ascending, ties by index).  With per-pixel weights
+    (``batch['weight']``) the candidates are ranked on the valid pixels only (:func:`mask_overlap_valid`); the integers
+    returned are then the restricted ones."""
     for k in ("mask", "link_poses", "K"):
         if not torch.is_tensor(batch[k]) or batch[k].device.type != "cuda":
             raise RuntimeError(f"search_starts: batch['{k}'] must be a tensor on the HIP device (there is no CPU path)")
@@ -106,8 +122,12 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
     ref = batch["mask"].to(dev, torch.float32)
     lp = batch["link_poses"].to(dev, torch.float32)
     mvp = candidate_mvps(batch["K"][0].to(dev, torch.float32), H, W, torch.tensor(cands, dtype=torch.float32, device=dev), lp)
-    inter, area, ref_area = mask_overlap(model._ensure_renderer().glctx, model._ensure_scene(), mvp, ref,
-                                         chunk_views=chunk_views)
+    if batch.get("weight") is not None:
+        inter, area, ref_area = mask_overlap_valid(model._ensure_renderer().glctx, model._ensure_scene(), mvp, ref,
+                                                   batch["weight"].to(dev, torch.float32), chunk_views=chunk_views)
+    else:
+        inter, area, ref_area = mask_overlap(model._ensure_renderer().glctx, model._ensure_scene(), mvp, ref,
+                                             chunk_views=chunk_views)
     xor, iou = overlap_scores(inter, area, ref_area)
     xor, iou = xor.cpu(), iou.cpu()
     ranking = rank_losses(xor.numpy())

@@ -40,6 +40,12 @@ class _LinkComposite(torch.autograd.Function):
         return (g,) * ctx.n
 
 
+def _sse(si, ref, w=None):
+    """A frame's loss in the three-op forms: ``sum((si - ref)**2)`` (rb_solver.py:70), ``sum(w * (si - ref)**2)`` with weights."""
+    sq = (si - ref) ** 2
+    return (sq if w is None else w * sq).sum()
+
+
 class RBSolver(nn.Module):
     def __init__(self, cfg, meshes=None):
         """cfg: :class:`easyhec_amd.config.Cfg` (fields of defaults.py ``model.rbsolver``).
@@ -102,7 +108,7 @@ class RBSolver(nn.Module):
     def Tc_c2b(self):
         return se3_exp_map(self.dof[None]).permute(0, 2, 1)[0]
 
-    def _forward_three_ops(self, renderer, Tc_c2b, link_poses, K, masks_ref):
+    def _forward_three_ops(self, renderer, Tc_c2b, link_poses, K, masks_ref, weight=None):
         """The reference's own schedule (rb_solver.py:60-72): one rasterize / interpolate / antialias round trip per
         (frame, link) through the drop-in ops, links summed and clamped, SSE per frame, mean over frames."""
         per_frame_loss, per_frame_mask = [], []
@@ -142,7 +148,7 @@ class RBSolver(nn.Module):
                     for k in range(self.nlinks)
                 ]
                 composite = _LinkComposite.apply(*silhouettes)
-                frame_loss = ((composite - masks_ref[frame].float()) ** 2).sum()
+                frame_loss = _sse(composite, masks_ref[frame].float(), None if weight is None else weight[frame])
             if lanes:
                 composite.record_stream(here)
                 frame_loss.record_stream(here)
@@ -178,7 +184,7 @@ class RBSolver(nn.Module):
         self._batched_cache = (key, ent)
         return ent
 
-    def _forward_three_ops_batched(self, renderer, Tc_c2b, link_poses, K, masks_ref):
+    def _forward_three_ops_batched(self, renderer, Tc_c2b, link_poses, K, masks_ref, weight=None):
         """``batched_ops``: the reference's three ops called once each over all B x L (frame, link) images (range mode), then
         rb_solver.py:66-72's sum over links, clamp, SSE per frame and mean -- on [B, L, H, W] at once."""
         from . import dr
@@ -196,10 +202,11 @@ class RBSolver(nn.Module):
         aa = dr.antialias(color, rast, pos, st["tri"], topology_hash=st["topology"])                 # [B L, H, W, 1]
         si = aa.view(B, self.nlinks, self.H, self.W)
         masks = torch.flip(si.sum(1).clamp(max=1), dims=[1])                                     # row 0 = top
-        loss = ((masks - masks_ref.float()) ** 2).sum(dim=(1, 2)).mean()
+        sq = (masks - masks_ref.float()) ** 2
+        loss = (sq if weight is None else weight * sq).sum(dim=(1, 2)).mean()
         return masks, loss
 
-    def _forward_per_call(self, renderer, Tc_c2b, link_poses, K, masks_ref):
+    def _forward_per_call(self, renderer, Tc_c2b, link_poses, K, masks_ref, weight=None):
         """``cfg.model.rbsolver.reference_schedule``: the schedule of rb_solver.py:58-71 with no host-side batching -- one
         pose product and one ``render_mask`` call (flip included) per (frame, link), the links stacked, summed and clamped
         per frame, a squared-error sum per frame, their mean."""
@@ -209,7 +216,7 @@ class RBSolver(nn.Module):
             layers = torch.stack([renderer.render_mask(v, t, K=K, object_pose=Tc_c2b @ link_poses[f, k])
                                   for k, (v, t) in enumerate(meshes)])
             frames.append(layers.sum(0).clamp(max=1))
-            sse.append(((frames[-1] - target.float()) ** 2).sum())
+            sse.append(_sse(frames[-1], target.float(), None if weight is None else weight[f]))
         return torch.stack(frames), torch.stack(sse).mean()
 
     # -- forward -------------------------------------------------------------------------------------------------
@@ -231,22 +238,26 @@ class RBSolver(nn.Module):
         link_poses = dps["link_poses"]
         K = dps["K"][0]
         batch_size = masks_ref.shape[0]
+        # optional per-pixel weights of the loss, [B,H,W]: 0 where the observed mask is not to be trusted (an occluder)
+        weight = dps.get("weight")
+        if weight is not None:
+            weight = weight.float()
 
         if self.cfg.use_fused:
             scene = self._ensure_scene()
             mvp = fused.mvp_matrices(K, self.H, self.W, Tc_c2b, link_poses)
             rendered, losses = fused.render_mask_loss(renderer.glctx, scene, mvp, masks_ref.float(),
-                                                      want_mask=with_outputs)
+                                                      want_mask=with_outputs, weight=weight)
             loss = losses.mean()
             all_frame_all_link_si = rendered if with_outputs else None
         elif renderer.plain:
-            rendered, loss = self._forward_per_call(renderer, Tc_c2b, link_poses, K, masks_ref)
+            rendered, loss = self._forward_per_call(renderer, Tc_c2b, link_poses, K, masks_ref, weight)
             all_frame_all_link_si = rendered
         elif getattr(self.cfg, "batched_ops", False):
-            rendered, loss = self._forward_three_ops_batched(renderer, Tc_c2b, link_poses, K, masks_ref)
+            rendered, loss = self._forward_three_ops_batched(renderer, Tc_c2b, link_poses, K, masks_ref, weight)
             all_frame_all_link_si = rendered
         else:
-            rendered, loss = self._forward_three_ops(renderer, Tc_c2b, link_poses, K, masks_ref)
+            rendered, loss = self._forward_three_ops(renderer, Tc_c2b, link_poses, K, masks_ref, weight)
             all_frame_all_link_si = rendered
 
         output = {}

@@ -172,6 +172,25 @@ int ehr_fused_bind_ref(ehr_ctx* ctx, const float* ref, void* stream);
  * Bv == B is ehr_fused_bind_ref.  A step only takes the bound path when it passes this pointer AND shares it the same way. */
 int ehr_fused_bind_ref_shared(ehr_ctx* ctx, const float* ref, int Bv, void* stream);
 
+/* Per-pixel weights of the mask loss, for pixels whose observed mask cannot be trusted (an occluder, motion blur, the
+ * frame's edge; 0 = "don't know").  weight [Bv,H,W] float32, row 0 = top like ref.  STICKY state of the plan: until the
+ * next call of this function every ehr_render_mask_loss, ehr_solver_step and ehr_solver_step_multi on this context computes
+ *     loss[b]          = sum_px  w[b % Bv, px] * (mask[b, px] - ref[b, px])^2
+ *     d loss / d mask  = 2 w (mask - ref)   where the links' sum is <= 1, else 0          (the clamp's gate is unchanged)
+ * per pixel in float32 as  e = m - r; we = w * e; loss += we * e; g = 2.f * we  -- with w == 1.0f the unweighted
+ * expression bit for bit; with w == 0 the pixel adds nothing and its blended pairs are skipped.  The rendered mask does
+ * not depend on the weights.  Bv must divide the planned B (view b reads image b % Bv: Bv == B for a solo solve, the Bv of
+ * ehr_solver_step_multi for hypotheses that share their images).  weight == NULL unbinds; ehr_fused_plan unbinds.
+ * Domain: finite, w >= 0.  Nothing is validated: a NaN, an infinite or a huge weight meets the accumulators' per-addend
+ * guard (|addend| >= 1e9) like a bad reference value does, and the step is REPORTED -- NaN loss, optimiser state
+ * untouched, ehr_fused_status raised -- never silently wrong.
+ * The call UNBINDS a bound reference (its cached sums are sums of w ref^2 and would be stale): bind the weights first,
+ * then the reference, which then caches the weighted sums with the composite stage's own expression, so the bound path
+ * stays bit-identical to the unbound one.  It also destroys a captured graph (ehr_graph_*), like ehr_fused_bind_ref, and
+ * is refused inside a capture.  The caller promises not to modify the weights while they are bound.  Enqueues nothing.
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+int ehr_fused_bind_weight(ehr_ctx* ctx, const float* weight, int Bv, void* stream);
+
 /* Measurement hook (bench.py's roofline leg): when enabled, every ehr_render_mask_loss / ehr_solver_step call records
  * hipEvents around its kernels on the launch stream.  ehr_fused_timing_read synchronises, writes the ACCUMULATED
  * milliseconds per stage since the last read and the number of calls covered, then resets.  Stages of the default

@@ -23,8 +23,10 @@ for line in out.stderr.splitlines():
     elif cur and ":" in t:
         k, v = t.split(":", 1)
         rows[cur][k.strip()] = v.strip()
-for k, v in rows.items():
-    name = re.sub(r"^_ZN3ehrL?\d+", "", k)[:34]
-    print(f"{name:36s} " + " ".join(f"{a} {v.get(b)}" for a, b in [
-        ("VGPR", "VGPRs"), ("SGPR", "SGPRs"), ("spillV", "VGPRs Spill"), ("spillS", "SGPRs Spill"),
+# demangled, without the parameter list: the template arguments tell the instantiations of one kernel apart
+names = subprocess.run(["c++filt"], input="\n".join(rows), capture_output=True, text=True).stdout.splitlines()
+for (k, v), name in zip(rows.items(), names):
+    name = re.sub(r"\(.*", "", name).replace("void ", "").replace("ehr::", "")
+    print(f"{name:48s} " + " ".join(f"{a} {v.get(b)}" for a, b in [
+        ("VGPR", "VGPRs"), ("SGPR", "TotalSGPRs"), ("spillV", "VGPRs Spill"), ("spillS", "SGPRs Spill"),
         ("scratch", "ScratchSize [bytes/lane]"), ("LDS", "LDS Size [bytes/block]"), ("occ", "Occupancy [waves/SIMD]")]))

@@ -1,5 +1,7 @@
 """Stage timings of the solver step (the chain bench.py times) on a bench workload, without the CPU baseline:
-    [EHR_LIB=ab/libehr_x.so] python tools/step_bench.py [workload] [steps]"""
+    [EHR_LIB=ab/libehr_x.so] python tools/step_bench.py [workload] [steps] [--weight]
+--weight: the same step with per-pixel weights bound (ehr_fused_bind_weight; uniform in [0, 2], a fifth of them zero): the
+composite stage then runs its weighted instantiation."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -7,11 +9,19 @@ import time
 import torch
 import bench
 from easyhec_amd import fused
-wl = sys.argv[1] if len(sys.argv) > 1 else bench.WORKLOAD
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+weighted = "--weight" in sys.argv
+args = [a for a in sys.argv[1:] if a != "--weight"]
+wl = args[0] if len(args) > 0 else bench.WORKLOAD
+steps = int(args[1]) if len(args) > 1 else 200
 dev = torch.device("cuda", 0)
 p = bench.build_problem(0, 1, dev, graph=False, workload=wl)
 tr = p["trainer"]
+if weighted:
+    g = torch.Generator(device="cpu").manual_seed(0)
+    w = torch.rand(tuple(tr.fast.ref.shape), generator=g) * 2
+    w[torch.rand(tuple(w.shape), generator=g) < 0.2] = 0
+    tr.fast.weight = w.to(dev).contiguous()
+    tr.fast._plan_and_bind()  # weights, then the reference (its cached sums are sums of w ref^2)
 for _ in range(20):
     tr.step()
 torch.cuda.synchronize()
@@ -25,5 +35,5 @@ fused.set_timing(p["glctx"], True)
 for _ in range(steps):
     tr.step()
 ms, n = fused.read_timing(p["glctx"])
-print(os.environ.get("EHR_LIB", "default"), wl, f"{el / steps * 1e6:.1f} us/step {p['n_views'] * steps / el:.0f} frames/s",
+print(os.environ.get("EHR_LIB", "default"), wl, "weighted" if weighted else "unweighted", f"{el / steps * 1e6:.1f} us/step {p['n_views'] * steps / el:.0f} frames/s",
       {k: round(v / n * 1e3, 1) for k, v in ms.items() if not k.startswith("unused")}, "loss", float(tr.last_loss), flush=True)
