@@ -66,9 +66,9 @@ def scene_arrays(robot):
     return verts, tris, toff, voff
 
 
-def mvp_numpy(K, H, W, Tc_c2b, link_poses):
-    """[B,L,4,4] float32 = proj @ opencv2blender @ Tc_c2b @ link_pose in float64, rounded once."""
-    proj = projection(np.asarray(K, dtype=np.float64), H, W)
+def mvp_numpy(K, H, W, Tc_c2b, link_poses, n=0.001, f=10.0):
+    """[B,L,4,4] float32 = proj @ opencv2blender @ Tc_c2b @ link_pose in float64, rounded once (n, f: the depth planes)."""
+    proj = projection(np.asarray(K, dtype=np.float64), H, W, n=n, f=f)
     o2b = np.diag([1.0, -1.0, -1.0, 1.0])
     return (proj @ o2b @ np.asarray(Tc_c2b, dtype=np.float64) @ np.asarray(link_poses, dtype=np.float64)).astype(
         np.float32)
