@@ -76,6 +76,9 @@ SIGNATURES = {
     "ehr_graph_release": (c_int, [c_void_p]),
     "ehr_fused_timing": (c_int, [c_void_p, c_int]),
     "ehr_fused_timing_read": (c_int, [c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_int)]),
+    "ehr_joint_forward": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "ehr_joint_backward_adam": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 10 + [c_float] * 5 +
+                                [c_void_p, c_void_p]),
 }
 
 
@@ -119,6 +122,15 @@ def has_weighted_loss():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_fused_bind_weight")
+
+
+def has_joint_offsets():
+    """True if the library has the joint-offset kernels (``ehr_joint_forward`` / ``ehr_joint_backward_adam``); the symbols'
+    presence is the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
+    return hasattr(l, "ehr_joint_forward") and hasattr(l, "ehr_joint_backward_adam")
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

@@ -1,0 +1,273 @@
+// ehr_joint.hip -- joint-offset calibration: the two small kernels that surround the solver step's launch chain when the
+// joint zero errors are fitted together with the camera pose (easyhec_amd/joint_calib.py).
+//
+//   joint_forward      : qpos[b] + offset -> forward kinematics of the flat table (UrdfChain.joint_table), in float64 ->
+//                        link_poses [B,L,16] float32 (what ehr_solver_step reads) and joint_frames [B,J,6] float32 = the
+//                        world axis a and a world point p on the axis of every active joint.
+//   joint_backward_adam: grad_mvp [B,L,16] (written by the chain) -> d(sum_b loss_b) / d offset_j =
+//                        sum_{b,l: j upstream of l} <(PF @ Tc)^T grad_mvp[b,l], D_blj>, with
+//                            revolute  D = [[a]x R_l | a x (t_l - p); 0 0],   prismatic  D = [0 | a; 0 0]
+//                        -> the Adam update of pose_adam_apply on the free joints' offsets.
+//                        <G, D> is evaluated as a . (tau + (t_l - p) x f) (revolute) and a . f (prismatic) with
+//                        tau = vee(G3 R_l^T - R_l G3^T), f = G[0:3,3]: per (view, link) pair once, then three products per joint.
+//
+// Neither kernel allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
+#include "ehr_host.h"
+#include "ehr_pose_core.h"
+
+#define EHR_JOINT_MAX_LINKS 64
+#define EHR_JOINT_MAX_JOINTS 32
+#define EHR_JOINT_TILE 256  // (view, link) pairs whose wrench one pass of the backward kernel keeps in LDS
+
+namespace ehr {
+
+// One wave per view.  OM[i] = origin_i @ motion_i(q) has no dependency between links and is formed by all lanes; the walk
+// F[i] = F[parent_i] @ OM[i] is serial in i and takes 16 lanes, one per entry.  Frames live in LDS (2 x 8 KB), never in a
+// per-thread array.  Malformed tables (a parent that does not precede its child, an index out of range) are the caller's
+// to refuse; here they only ever read inside the arrays and give NaN.
+__global__ void __launch_bounds__(64) joint_forward_kernel(const int* __restrict__ parent, const double* __restrict__ origin,
+                                                          const int* __restrict__ kind, const double* __restrict__ axis,
+                                                          const int* __restrict__ qidx, const int* __restrict__ use, int N,
+                                                          int J, int L, const double* __restrict__ qpos,
+                                                          const float* __restrict__ offset, float* __restrict__ link_poses,
+                                                          float* __restrict__ joint_frames) {
+    __shared__ double OM[EHR_JOINT_MAX_LINKS][16];
+    __shared__ double F[EHR_JOINT_MAX_LINKS][16];
+    __shared__ double sc[EHR_JOINT_MAX_LINKS][3];  // sin, cos, q of the link's joint
+    __shared__ int jlink[EHR_JOINT_MAX_JOINTS];    // the link active joint j moves
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (lane < EHR_JOINT_MAX_JOINTS) jlink[lane] = -1;
+    __syncthreads();
+    if (lane < N) {
+        const int c = qidx[lane];
+        double q = 0.0;
+        if (c >= 0 && c < J) {
+            q = qpos[(size_t)b * J + c] + (double)offset[c];
+            jlink[c] = lane;  // (one writer per joint: the host refuses a table in which two links share an active joint)
+        }
+        sc[lane][0] = sin(q);
+        sc[lane][1] = cos(q);
+        sc[lane][2] = q;
+    }
+    __syncthreads();
+    for (int e = lane; e < N * 16; e += 64) {
+        const int i = e >> 4, r = (e >> 2) & 3, c = e & 3;
+        const double ax = axis[3 * i], ay = axis[3 * i + 1], az = axis[3 * i + 2];
+        const int k = (qidx[i] >= 0 && qidx[i] < J) ? kind[i] : 0;
+        // column c of the motion: I + sin(q) [a]x + (1 - cos q) [a]x^2 (revolute), a translation by q a (prismatic)
+        double M[4] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0, c == 3 ? 1.0 : 0.0};
+        if (k == 1 && c < 3) {
+            // (entries picked with selects, never by a run-time index into a per-thread array: that would be scratch)
+            const double s = sc[i][0], v = 1.0 - sc[i][1], aa = (ax * ax + ay * ay) + az * az;
+            const double ac = c == 0 ? ax : (c == 1 ? ay : az);
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                const double am = m == 0 ? ax : (m == 1 ? ay : az);
+                const int o = 3 - m - c;  // [a]x[m][c] = -+ a[3 - m - c] off the diagonal, minus where c follows m cyclically
+                const double ao = o == 0 ? ax : (o == 1 ? ay : az);
+                const double kx = m == c ? 0.0 : (((c - m + 3) % 3 == 1) ? -ao : ao);
+                const double k2 = am * ac - (m == c ? aa : 0.0);  // ([a]x^2)[m][c] = a_m a_c - delta_mc |a|^2
+                M[m] = ((m == c ? 1.0 : 0.0) + s * kx) + v * k2;
+            }
+        } else if (k == 2 && c == 3) {
+            M[0] = ax * sc[i][2];
+            M[1] = ay * sc[i][2];
+            M[2] = az * sc[i][2];
+        }
+        const double* O = origin + (size_t)i * 16 + 4 * r;
+        OM[i][4 * r + c] = ((O[0] * M[0] + O[1] * M[1]) + O[2] * M[2]) + O[3] * M[3];
+    }
+    __syncthreads();
+    for (int i = 0; i < N; i++) {  // (uniform trip count: every lane meets every barrier)
+        if (lane < 16) {
+            const int r = lane >> 2, c = lane & 3;
+            const int p = parent[i];
+            double t;
+            if (p < 0) {
+                t = OM[i][lane];
+            } else if (p < i) {
+                const double* A = F[p] + 4 * r;
+                t = ((A[0] * OM[i][c] + A[1] * OM[i][4 + c]) + A[2] * OM[i][8 + c]) + A[3] * OM[i][12 + c];
+            } else {
+                t = __longlong_as_double(0x7ff8000000000000ll);
+            }
+            F[i][lane] = t;
+        }
+        __syncthreads();
+    }
+    // one rounding, at the end
+    for (int e = lane; e < L * 16; e += 64) {
+        const int u = use[e >> 4];
+        link_poses[((size_t)b * L) * 16 + e] =
+            (u >= 0 && u < N) ? (float)F[u][e & 15] : __int_as_float(0x7fc00000);
+    }
+    for (int e = lane; e < J * 6; e += 64) {
+        const int j = e / 6, k = e - 6 * j;
+        const int i = jlink[j];
+        float out = __int_as_float(0x7fc00000);
+        if (i >= 0) {
+            if (k < 3)  // a = R_i @ axis_i (the joint's own motion leaves its axis where it is)
+                out = (float)((F[i][4 * k] * axis[3 * i] + F[i][4 * k + 1] * axis[3 * i + 1]) + F[i][4 * k + 2] * axis[3 * i + 2]);
+            else        // p = the moved link's origin: on the axis of a revolute joint (unused for a prismatic one)
+                out = (float)F[i][4 * (k - 3) + 3];
+        }
+        joint_frames[((size_t)b * J) * 6 + e] = out;
+    }
+}
+
+// Single workgroup of 256 threads.  Per tile of EHR_JOINT_TILE pairs: a thread per pair forms the pair's wrench (tau, f) and
+// keeps it with t_l in LDS; then thread (j = t & 31, s = t >> 5) adds joint j's products over pairs s, s + 8, ... of the tile.
+// Every thread has ONE float64 accumulator and adds in a fixed order; the eight partial sums of a joint are combined by one
+// shuffle (lanes j, j + 32 of a wave) and then the four waves in order.
+__global__ void __launch_bounds__(256) joint_backward_adam_kernel(
+    const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac, const float* __restrict__ K, int B, int L, int J,
+    int H, int W, float n, float f, const float* __restrict__ link_poses, const float* __restrict__ joint_frames,
+    const unsigned* __restrict__ upstream, const int* __restrict__ joint_kind, const float* __restrict__ red,
+    const int* __restrict__ free_j, float* __restrict__ offset, float* __restrict__ m, float* __restrict__ v,
+    int* __restrict__ step_j, float lr, float b1, float b2, float eps, float wd, float* __restrict__ grad_out) {
+    __shared__ double A[16];                        // PF @ Tc
+    __shared__ double Wr[EHR_JOINT_TILE][9];        // tau (3), f (3), t_l (3) of the tile's pairs
+    __shared__ double S[4][EHR_JOINT_MAX_JOINTS];
+    const int tid = threadIdx.x;
+    if (tid < 16) {
+        float P[16];
+        projection(K, H, W, n, f, P);
+        for (int r = 0; r < 4; r++) {  // PF = proj @ opencv2blender, as in pose_backward_prefetch
+            P[4 * r + 1] = -P[4 * r + 1];
+            P[4 * r + 2] = -P[4 * r + 2];
+        }
+        const int r = tid >> 2, c = tid & 3;
+        double s = 0.0;
+        for (int k = 0; k < 4; k++) s += (double)P[4 * r + k] * (double)tc_jac[4 * k + c];  // Tc = tc_jac[0:16]: the pose this step rendered
+        A[tid] = s;
+    }
+    const int j = tid & 31, sub = tid >> 5;
+    const bool mine = j < J && free_j[j] != 0;
+    const int jk = j < J ? joint_kind[j] : 0;
+    double acc = 0.0;
+    const int BL = B * L;
+    for (int base = 0; base < BL; base += EHR_JOINT_TILE) {
+        __syncthreads();  // (A is written; the previous tile's wrenches have been read)
+        const int i = base + tid;
+        if (i < BL) {
+            float g[16], lp[12];
+#pragma unroll
+            for (int k = 0; k < 16; k++) g[k] = grad_mvp[(size_t)i * 16 + k];
+#pragma unroll
+            for (int k = 0; k < 12; k++) lp[k] = link_poses[(size_t)i * 16 + k];
+            double G[3][4];  // rows 0..2 of (PF @ Tc)^T @ g: D's last row is zero
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    G[r][c] = ((A[r] * (double)g[c] + A[4 + r] * (double)g[4 + c]) + A[8 + r] * (double)g[8 + c]) +
+                              A[12 + r] * (double)g[12 + c];
+            double Mx[3][3];  // G3 @ R_l^T
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    Mx[r][k] = (G[r][0] * (double)lp[4 * k] + G[r][1] * (double)lp[4 * k + 1]) + G[r][2] * (double)lp[4 * k + 2];
+            Wr[tid][0] = Mx[2][1] - Mx[1][2];
+            Wr[tid][1] = Mx[0][2] - Mx[2][0];
+            Wr[tid][2] = Mx[1][0] - Mx[0][1];
+            Wr[tid][3] = G[0][3];
+            Wr[tid][4] = G[1][3];
+            Wr[tid][5] = G[2][3];
+            Wr[tid][6] = (double)lp[3];
+            Wr[tid][7] = (double)lp[7];
+            Wr[tid][8] = (double)lp[11];
+        }
+        __syncthreads();
+        if (mine) {
+            const int cnt = min(EHR_JOINT_TILE, BL - base);
+            for (int k = sub; k < cnt; k += 8) {
+                const int p = base + k;
+                const int bb = p / L, l = p - bb * L;
+                if (!((upstream[l] >> j) & 1u)) continue;
+                const float* jf = joint_frames + ((size_t)bb * J + j) * 6;
+                const double a0 = jf[0], a1 = jf[1], a2 = jf[2];
+                const double* w = Wr[k];
+                double t0 = w[3], t1 = w[4], t2 = w[5];  // prismatic: a . f
+                if (jk == 1) {                          // revolute: a . (tau + (t_l - p) x f)
+                    const double d0 = w[6] - (double)jf[3], d1 = w[7] - (double)jf[4], d2 = w[8] - (double)jf[5];
+                    t0 = w[0] + (d1 * w[5] - d2 * w[4]);
+                    t1 = w[1] + (d2 * w[3] - d0 * w[5]);
+                    t2 = w[2] + (d0 * w[4] - d1 * w[3]);
+                }
+                if (jk == 1 || jk == 2) acc += (a0 * t0 + a1 * t1) + a2 * t2;
+            }
+        }
+    }
+    acc += wave_xor<32>(acc);
+    if ((tid & 63) < 32) S[tid >> 6][j] = acc;
+    __syncthreads();
+    // Adam, pose_adam_apply's expressions per element; a reported step (any of red[0..7] not finite) touches nothing
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
+    const int t = step_j[0] + 1;
+    if (tid < J) {
+        if (!mine) {
+            if (grad_out) grad_out[tid] = 0.f;
+        } else if (!ok) {
+            if (grad_out) grad_out[tid] = __int_as_float(0x7fc00000);
+        } else {
+            const float gsum = (float)(((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid]);
+            float g = gsum / red[7];
+            if (grad_out) grad_out[tid] = g;
+            const float p = offset[tid];
+            g = g + wd * p;
+            const float mi = b1 * m[tid] + (1.f - b1) * g;
+            const float vi = b2 * v[tid] + (1.f - b2) * g * g;
+            m[tid] = mi;
+            v[tid] = vi;
+            const float bc1 = 1.f - powf(b1, (float)t);
+            const float bc2 = 1.f - powf(b2, (float)t);
+            const float step_size = lr / bc1;
+            const float rsq_bc2 = sqrtf(bc2);
+            const float denom = sqrtf(vi) / rsq_bc2 + eps;
+            offset[tid] = p - step_size * (mi / denom);
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && ok) step_j[0] = t;
+}
+
+}  // namespace ehr
+
+using namespace ehr;
+
+extern "C" {
+
+int ehr_joint_forward(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                      const int32_t* qidx, const int32_t* use, int N, int J, int L, const double* qpos, const float* offset,
+                      int B, float* link_poses, float* joint_frames, void* stream) {
+    if (!parent || !origin || !kind || !axis || !qidx || !use || !qpos || !offset || !link_poses || !joint_frames)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward: NULL tensor");
+    if (N < 1 || N > EHR_JOINT_MAX_LINKS || J < 1 || J > EHR_JOINT_MAX_JOINTS || L < 1 || B < 1)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward: bad sizes (N %d <= 64 links, J %d <= 32 joints, L %d, B %d)", N, J, L, B);
+    joint_forward_kernel<<<B, 64, 0, (hipStream_t)stream>>>(parent, origin, kind, axis, qidx, use, N, J, L, qpos, offset,
+                                                           link_poses, joint_frames);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_joint_backward_adam(const float* grad_mvp, const float* tc_jac, const float* K, int B, int L, int J, int H, int W,
+                            float near_plane, float far_plane, const float* link_poses, const float* joint_frames,
+                            const uint32_t* upstream, const int32_t* joint_kind, const float* red, const int32_t* free_joints,
+                            float* offset, float* adam_m, float* adam_v, int32_t* step_j, float lr, float beta1, float beta2,
+                            float eps, float weight_decay, float* grad_out, void* stream) {
+    if (!grad_mvp || !tc_jac || !K || !link_poses || !joint_frames || !upstream || !joint_kind || !red || !free_joints ||
+        !offset || !adam_m || !adam_v || !step_j)
+        return fail(EHR_ERR_INVALID, "ehr_joint_backward_adam: NULL tensor");
+    if (J < 1 || J > EHR_JOINT_MAX_JOINTS || L < 1 || B < 1 || (long long)B * L > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID, "ehr_joint_backward_adam: bad sizes (J %d <= 32 joints, L %d, B %d)", J, L, B);
+    joint_backward_adam_kernel<<<1, 256, 0, (hipStream_t)stream>>>(
+        grad_mvp, tc_jac, K, B, L, J, H, W, near_plane, far_plane, link_poses, joint_frames, upstream, joint_kind, red,
+        free_joints, offset, adam_m, adam_v, step_j, lr, beta1, beta2, eps, weight_decay, grad_out);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+}  // extern "C"

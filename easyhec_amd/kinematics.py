@@ -139,6 +139,49 @@ class UrdfChain:
             poses[l] = T
         return np.stack([poses[self.link_order[i]] for i in link_indices], axis=1).astype(np.float64)
 
+    def joint_table(self, link_indices):
+        """The tree as flat arrays in articulation order (N = ``len(link_order)``, J = ``dof``, L = ``len(link_indices)``):
+        what the joint-offset kernels (csrc/ehr_joint.hip) and tests/joint_reference.py walk instead of this object.
+
+        ``parent [N] int32`` (-1 for the root; a parent precedes its child), ``origin [N,16] float64`` (row-major joint
+        origin; identity for the root), ``kind [N] int32`` (0 fixed, 1 revolute / continuous, 2 prismatic), ``axis [N,3]
+        float64`` (unit), ``qidx [N] int32`` (column of the active joint that moves the link, or -1), ``use [L] int32``
+        (the rendered links), ``upstream [L] uint32`` (bit j: active joint j lies between the root and rendered link l).
+        With these, ``T_child = T_parent @ origin @ motion(q[qidx])`` is :meth:`compute_forward_kinematics`."""
+        N, J = len(self.link_order), self.dof
+        if N > 64 or J > 32:
+            raise ValueError(f"joint_table: {N} links / {J} active joints exceed the limits of 64 links and 32 joints")
+        index = {l: i for i, l in enumerate(self.link_order)}
+        col = {id(j): i for i, j in enumerate(self.active)}
+        kinds = {"fixed": 0, "revolute": 1, "continuous": 1, "prismatic": 2}
+        parent = np.full(N, -1, dtype=np.int32)
+        origin = np.tile(np.eye(4).reshape(16), (N, 1))
+        kind = np.zeros(N, dtype=np.int32)
+        axis = np.tile(np.array([1.0, 0.0, 0.0]), (N, 1))
+        qidx = np.full(N, -1, dtype=np.int32)
+        for i, l in enumerate(self.link_order[1:], start=1):
+            j = self._joint_of_child[l]
+            if j["type"] not in kinds:
+                raise ValueError(f"joint_table: joint {j['name']!r} has unsupported type {j['type']!r}")
+            parent[i] = index[j["parent"]]
+            assert parent[i] < i
+            origin[i] = j["origin"].reshape(16)
+            kind[i] = kinds[j["type"]]
+            if kind[i]:  # (a fixed joint keeps the placeholder: its axis is never used, and a URDF may give it as 0 0 0)
+                axis[i] = j["axis"] / (np.linalg.norm(j["axis"]) + 1e-30)
+            qidx[i] = col.get(id(j), -1)
+        use = np.asarray(list(link_indices), dtype=np.int32)
+        if use.size and (use.min() < 0 or use.max() >= N):
+            raise ValueError("joint_table: link index out of range")
+        upstream = np.zeros(use.size, dtype=np.uint32)
+        for k, i in enumerate(use):
+            while i >= 0:
+                if qidx[i] >= 0:
+                    upstream[k] |= np.uint32(1) << np.uint32(qidx[i])
+                i = parent[i]
+        return {"parent": parent, "origin": origin, "kind": kind, "axis": axis, "qidx": qidx, "use": use,
+                "upstream": upstream}
+
     def link_poses(self, qpos, link_indices):
         """[len(link_indices),4,4] poses for SAPIEN-style link indices (``use_links`` in the reference configs)."""
         poses = self.compute_forward_kinematics(qpos)

@@ -383,6 +383,46 @@ int ehr_mask_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, cons
                      const float* ref, int Q, int S, int L, int V, int T, int H, int W, int64_t* overlap,
                      int64_t* ref_area, int chunk_views, void* stream);
 
+/* Joint-offset calibration: the joint zero errors of the arm are fitted together with the camera pose.  Two small kernels
+ * AROUND the launch chain of ehr_solver_step, which itself is unchanged: it reads link_poses from device memory on every call
+ * and leaves grad_mvp [B,L,16] and the pose it rendered (tc_jac[0:16]) behind.  A step is
+ *     ehr_joint_forward -> ehr_solver_step -> ehr_joint_backward_adam        on one stream.
+ * Both calls take device pointers only, never allocate or synchronise, and launch on `stream`: between ehr_graph_begin and
+ * ehr_graph_end they are captured together with the chain.
+ * The kinematic chain is a flat table in articulation order (UrdfChain.joint_table; N <= 64 links, J <= 32 active joints):
+ *   parent [N] int32 (-1 = root; a parent precedes its child), origin [N,16] float64 row-major, kind [N] int32 (0 fixed,
+ *   1 revolute / continuous, 2 prismatic), axis [N,3] float64 unit, qidx [N] int32 (active joint that moves the link, or -1),
+ *   use [L] int32 (the rendered links), upstream [L] uint32 (bit j: active joint j lies between the root and rendered link l).
+ * The caller validates the table (it is device memory here); a malformed one gives NaN outputs, never an access outside the arrays.
+ *   ehr_joint_forward : qpos [B,J] float64, offset [J] float32 ->  T_child = T_parent @ origin @ motion(q_j + offset_j), walked
+ *                       in float64 and rounded ONCE: link_poses [B,L,16] float32 (at offset == 0 the float32 cast of the host's
+ *                       float64 forward kinematics up to the double rounding, i.e. within one float32 unit of max(1, |x|)) and
+ *                       joint_frames [B,J,6] float32 = (a, p): the world axis of active joint j in view b and a world point on
+ *                       it.  One wave per view, the link frames in LDS; any B.
+ *   ehr_joint_backward_adam : with G = (PF @ Tc)^T @ grad_mvp[b,l], PF = proj(K) @ opencv2blender and Tc = tc_jac[0:16] (NOT
+ *                       recomputed from dof, which Adam has already moved), and R_l, t_l from link_poses[b,l]:
+ *                           d(sum_b loss_b) / d offset_j = sum_{b,l : bit j of upstream[l]} <G, D_blj>
+ *                           revolute  D = [ [a]x R_l | a x (t_l - p) ; 0 0 ]      prismatic  D = [ 0 | a ; 0 0 ]
+ *                       summed in float64 in a fixed order (bit-reproducible), then ehr_pose_adam's update per element on the
+ *                       mean-loss gradient g_j = sum / red[7] with L2 weight decay, where free_joints[j] != 0 only: a joint that
+ *                       is not free keeps its offset and moments and reports grad_out[j] = 0.  joint_kind [J] int32 is the kind of
+ *                       the link each active joint moves; offset, adam_m, adam_v [J] and step_j [1] are this parameter group's
+ *                       own state (its own step counter); grad_out [J] may be NULL.  red [8] is the solver step's: if any of
+ *                       red[0..7] is not finite (a REPORTED step: same `< 3.0e38f` test as the pose's Adam) the offsets, the
+ *                       moments and step_j stay untouched and the free joints' grad_out is NaN -- the next forward launch then
+ *                       writes identical link_poses, so the chain's own recovery (the same history row again, the
+ *                       general-triangle pass, a new plan) works unchanged.  A single workgroup.
+ * Out of scope: a data-parallel job (the offset gradient would need an exchange of its own) and ehr_solver_step_multi (the
+ * hypotheses share ONE link_poses).  ehr_version() is unchanged: the presence of these symbols is the capability check. */
+int ehr_joint_forward(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                      const int32_t* qidx, const int32_t* use, int N, int J, int L, const double* qpos, const float* offset,
+                      int B, float* link_poses, float* joint_frames, void* stream);
+int ehr_joint_backward_adam(const float* grad_mvp, const float* tc_jac, const float* K, int B, int L, int J, int H, int W,
+                            float near_plane, float far_plane, const float* link_poses, const float* joint_frames,
+                            const uint32_t* upstream, const int32_t* joint_kind, const float* red, const int32_t* free_joints,
+                            float* offset, float* adam_m, float* adam_v, int32_t* step_j, float lr, float beta1, float beta2,
+                            float eps, float weight_decay, float* grad_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
