@@ -79,6 +79,7 @@ SIGNATURES = {
     "ehr_joint_forward": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ehr_joint_backward_adam": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 10 + [c_float] * 5 +
                                 [c_void_p, c_void_p]),
+    "ehr_rig_backward_adam": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 7 + [c_float] * 7 + [c_void_p, c_void_p]),
 }
 
 
@@ -131,6 +132,21 @@ def has_joint_offsets():
         return False
     l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
     return hasattr(l, "ehr_joint_forward") and hasattr(l, "ehr_joint_backward_adam")
+
+
+def has_rig():
+    """True if the library has the camera rig's finish stage (``ehr_rig_backward_adam``); the symbol's presence is the
+    capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_rig_backward_adam")
+
+
+class RigCamera(ctypes.Structure):
+    """``ehr_rig_camera`` of include/ehr.h, field for field."""
+    _fields_ = [(k, c_void_p) for k in ("grad_mvp", "tc_jac", "K", "link_poses", "joint_frames", "red", "dof", "adam_m",
+                                        "adam_v", "step", "loss_out", "grad_out")] + \
+               [("B", c_int), ("H", c_int), ("W", c_int), ("near_plane", c_float), ("far_plane", c_float)]
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

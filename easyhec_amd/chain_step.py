@@ -17,7 +17,55 @@ import torch
 from . import _lib, fused
 
 
-class _ChainStep:
+class _ReportedStepProtocol:
+    """The protocol around a REPORTED step, in one place for every stepper (``_ChainStep``; the camera rig of
+    easyhec_amd/rig_calib.py, which drives several chains): the non-blocking look at the loss and the loop that takes an
+    exact number of effective steps.  A user sets ``dev`` and ``loss`` (all NaN for a reported step) and provides
+    ``steps_done``, ``_recover_and_note()`` and ``_check_status()`` (raises with the status of the context(s))."""
+
+    def _init_protocol(self):
+        # A reported step loses nothing but time -- unless nobody looks.  step() therefore looks itself, without ever
+        # waiting: every `check_every` steps the loss goes to pinned host memory behind an event, the copy that was started
+        # `check_every` steps earlier is inspected, and a NaN there triggers the recovery.
+        self.check_every = 16
+        self._calls = 0
+        self._probe = torch.zeros(self.loss.numel(), dtype=torch.float32)
+        if self.dev.type == "cuda":
+            self._probe = self._probe.pin_memory()
+        self._probe_ev = None
+        self.recoveries = []  # what the recovery did, in order
+
+    def _poll(self):
+        """Non-blocking look at the loss of the step taken `check_every` steps ago (a report is step-wide: every element
+        NaN); starts the next look."""
+        if self._probe_ev is not None:
+            if not self._probe_ev.query():
+                return  # (still in flight: look again next time; never wait here)
+            self._probe_ev = None
+            if bool(torch.isnan(self._probe).all()):
+                self._recover_and_note()
+        self._probe.copy_(self.loss, non_blocking=True)
+        self._probe_ev = torch.cuda.Event()
+        self._probe_ev.record()
+
+    def effective_rounds(self, n, who):
+        """The loop that takes exactly ``n`` EFFECTIVE steps: yields ``(steps still to take, effective steps so far)``; the
+        caller takes that many steps and comes back.  While steps were reported, the chain is recovered and the rest is
+        asked for again -- at most 4 times, then raises with the context's status (``who``: the caller's name, for the
+        message).  ``steps_done`` is read once per round."""
+        start, done, rounds = self.steps_done, 0, 0
+        while done < n:
+            yield n - done, done
+            done = self.steps_done - start
+            if done < n:
+                rounds += 1
+                if rounds > 4:
+                    self._check_status()
+                    raise RuntimeError(f"{who}: {n - done} of {n} steps keep being reported as not taken (NaN loss)")
+                self._recover_and_note()
+
+
+class _ChainStep(_ReportedStepProtocol):
     def _init_chain(self, slack):
         # job slots: `slack` per view tile (default: half as many slots as a view has tiles) instead of one per (view,
         # link, tile) -- 30 MB instead of 0.48 GB of scratch at 8 views 720p x 8 links; the workloads here use a tenth of
@@ -32,16 +80,7 @@ class _ChainStep:
             self.slack = float(os.environ["EHR_VB_SLACK"]) if slack is None else float(slack)
         self._plan_and_bind()
         self._graph = None
-        # A reported step loses nothing but time -- unless nobody looks.  step() therefore looks itself, without ever
-        # waiting: every `check_every` steps the loss goes to pinned host memory behind an event, the copy that was started
-        # `check_every` steps earlier is inspected, and a NaN there triggers recover_from_overflow().
-        self.check_every = 16
-        self._calls = 0
-        self._probe = torch.zeros(self.loss.numel(), dtype=torch.float32)
-        if self.dev.type == "cuda":
-            self._probe = self._probe.pin_memory()
-        self._probe_ev = None
-        self.recoveries = []  # what recover_from_overflow() did, in order
+        self._init_protocol()  # (a NaN seen there triggers recover_from_overflow(); `recoveries` notes what it did)
 
     def _plan_and_bind(self):
         fused._ensure_plan(self.glctx, self.scene, self.B, self.H, self.W, slack=self.slack)
@@ -78,19 +117,6 @@ class _ChainStep:
             if self._calls % self.check_every == 0:
                 self._poll()
         return self.loss
-
-    def _poll(self):
-        """Non-blocking look at the loss of the step taken `check_every` steps ago (a report is step-wide: every element
-        NaN); starts the next look."""
-        if self._probe_ev is not None:
-            if not self._probe_ev.query():
-                return  # (still in flight: look again next time; never wait here)
-            self._probe_ev = None
-            if bool(torch.isnan(self._probe).all()):
-                self._recover_and_note()
-        self._probe.copy_(self.loss, non_blocking=True)
-        self._probe_ev = torch.cuda.Event()
-        self._probe_ev.record()
 
     def _check_capturable(self):
         """Raises if this step's chain cannot be recorded."""
@@ -158,18 +184,5 @@ class _ChainStep:
             self.recoveries.append(what)
         return what
 
-    def effective_rounds(self, n, who):
-        """The loop that takes exactly ``n`` EFFECTIVE steps: yields ``(steps still to take, effective steps so far)``; the
-        caller takes that many steps and comes back.  While steps were reported, the chain is recovered and the rest is
-        asked for again -- at most 4 times, then raises with the context's status (``who``: the caller's name, for the
-        message).  ``steps_done`` is read once per round."""
-        start, done, rounds = self.steps_done, 0, 0
-        while done < n:
-            yield n - done, done
-            done = self.steps_done - start
-            if done < n:
-                rounds += 1
-                if rounds > 4:
-                    fused.check_status(self.glctx)
-                    raise RuntimeError(f"{who}: {n - done} of {n} steps keep being reported as not taken (NaN loss)")
-                self._recover_and_note()
+    def _check_status(self):
+        fused.check_status(self.glctx)

@@ -1,4 +1,4 @@
-// ehr_joint.hip -- joint-offset calibration: the two small kernels that surround the solver step's launch chain when the
+// ehr_joint.hip -- joint-offset calibration: the small kernels that surround the solver step's launch chain when the
 // joint zero errors are fitted together with the camera pose (easyhec_amd/joint_calib.py).
 //
 //   joint_forward      : qpos[b] + offset -> forward kinematics of the flat table (UrdfChain.joint_table), in float64 ->
@@ -10,14 +10,18 @@
 //                        -> the Adam update of pose_adam_apply on the free joints' offsets.
 //                        <G, D> is evaluated as a . (tau + (t_l - p) x f) (revolute) and a . f (prismatic) with
 //                        tau = vee(G3 R_l^T - R_l G3^T), f = G[0:3,3]: per (view, link) pair once, then three products per joint.
+//   rig_backward_adam  : C cameras that watch one arm (easyhec_amd/rig_calib.py): the sum above per camera, added over the
+//                        cameras in order, then every camera's pose Adam and the shared offsets' Adam -- or, if any camera's
+//                        step is reported, nothing at all.  One launch instead of a joint_backward_adam per camera.
 //
-// Neither kernel allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
+// No kernel here allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
 
 #define EHR_JOINT_MAX_LINKS 64
 #define EHR_JOINT_MAX_JOINTS 32
 #define EHR_JOINT_TILE 256  // (view, link) pairs whose wrench one pass of the backward kernel keeps in LDS
+#define EHR_RIG_MAX_CAMERAS 16
 
 namespace ehr {
 
@@ -115,19 +119,21 @@ __global__ void __launch_bounds__(64) joint_forward_kernel(const int* __restrict
     }
 }
 
-// Single workgroup of 256 threads.  Per tile of EHR_JOINT_TILE pairs: a thread per pair forms the pair's wrench (tau, f) and
-// keeps it with t_l in LDS; then thread (j = t & 31, s = t >> 5) adds joint j's products over pairs s, s + 8, ... of the tile.
-// Every thread has ONE float64 accumulator and adds in a fixed order; the eight partial sums of a joint are combined by one
-// shuffle (lanes j, j + 32 of a wave) and then the four waves in order.
-__global__ void __launch_bounds__(256) joint_backward_adam_kernel(
-    const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac, const float* __restrict__ K, int B, int L, int J,
-    int H, int W, float n, float f, const float* __restrict__ link_poses, const float* __restrict__ joint_frames,
-    const unsigned* __restrict__ upstream, const int* __restrict__ joint_kind, const float* __restrict__ red,
-    const int* __restrict__ free_j, float* __restrict__ offset, float* __restrict__ m, float* __restrict__ v,
-    int* __restrict__ step_j, float lr, float b1, float b2, float eps, float wd, float* __restrict__ grad_out) {
-    __shared__ double A[16];                        // PF @ Tc
-    __shared__ double Wr[EHR_JOINT_TILE][9];        // tau (3), f (3), t_l (3) of the tile's pairs
-    __shared__ double S[4][EHR_JOINT_MAX_JOINTS];
+// The sum of one camera's offset gradient, shared by joint_backward_adam_kernel and rig_backward_adam_kernel; call with all
+// 256 threads of the single workgroup.  Per tile of EHR_JOINT_TILE pairs: a thread per pair forms the pair's wrench (tau, f)
+// and keeps it with t_l in LDS; then thread (j = t & 31, s = t >> 5) adds joint j's products over pairs s, s + 8, ... of the
+// tile.  Every thread has ONE float64 accumulator and adds in a fixed order; the eight partial sums of a joint are combined by
+// one shuffle (lanes j, j + 32 of a wave) and left per wave in S, which the caller adds in order: ((S0 + S1) + S2) + S3.
+// A [16], Wr and S are the caller's LDS; ends on a barrier (S is readable), and its first write to S comes after a barrier of
+// its own, so a caller may read S and call again without one in between.
+__device__ __forceinline__ void joint_offset_sums(const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac,
+                                                  const float* __restrict__ K, int B, int L, int J, int H, int W, float n,
+                                                  float f, const float* __restrict__ link_poses,
+                                                  const float* __restrict__ joint_frames,
+                                                  const unsigned* __restrict__ upstream,
+                                                  const int* __restrict__ joint_kind, const int* __restrict__ free_j,
+                                                  bool& mine, double* A, double (*Wr)[9],
+                                                  double (*S)[EHR_JOINT_MAX_JOINTS]) {
     const int tid = threadIdx.x;
     if (tid < 16) {
         float P[16];
@@ -142,7 +148,7 @@ __global__ void __launch_bounds__(256) joint_backward_adam_kernel(
         A[tid] = s;
     }
     const int j = tid & 31, sub = tid >> 5;
-    const bool mine = j < J && free_j[j] != 0;
+    mine = j < J && free_j[j] != 0;  // (out: thread tid < J is joint tid's, and the caller's Adam wants to know)
     const int jk = j < J ? joint_kind[j] : 0;
     double acc = 0.0;
     const int BL = B * L;
@@ -202,34 +208,119 @@ __global__ void __launch_bounds__(256) joint_backward_adam_kernel(
     acc += wave_xor<32>(acc);
     if ((tid & 63) < 32) S[tid >> 6][j] = acc;
     __syncthreads();
-    // Adam, pose_adam_apply's expressions per element; a reported step (any of red[0..7] not finite) touches nothing
+}
+
+// The offsets' Adam for thread tid < J: pose_adam_apply's expressions per element on g = (float)sum() / nfr.  A joint that is
+// not free keeps everything and reports 0; a reported step (!ok) touches nothing and reports NaN for the free joints.
+// sum() returns the joint's float64 sum and is called where the step counts only.
+template <class Sum>
+__device__ __forceinline__ void joint_offset_adam(int tid, bool mine, bool ok, Sum sum, float nfr, int t,
+                                                  float* __restrict__ offset, float* __restrict__ m, float* __restrict__ v,
+                                                  float lr, float b1, float b2, float eps, float wd,
+                                                  float* __restrict__ grad_out) {
+    if (!mine) {
+        if (grad_out) grad_out[tid] = 0.f;
+    } else if (!ok) {
+        if (grad_out) grad_out[tid] = __int_as_float(0x7fc00000);
+    } else {
+        const float gsum = (float)sum();
+        float g = gsum / nfr;
+        if (grad_out) grad_out[tid] = g;
+        const float p = offset[tid];
+        g = g + wd * p;
+        const float mi = b1 * m[tid] + (1.f - b1) * g;
+        const float vi = b2 * v[tid] + (1.f - b2) * g * g;
+        m[tid] = mi;
+        v[tid] = vi;
+        const float bc1 = 1.f - powf(b1, (float)t);
+        const float bc2 = 1.f - powf(b2, (float)t);
+        const float step_size = lr / bc1;
+        const float rsq_bc2 = sqrtf(bc2);
+        const float denom = sqrtf(vi) / rsq_bc2 + eps;
+        offset[tid] = p - step_size * (mi / denom);
+    }
+}
+
+// Single workgroup of 256 threads: one camera's sum (joint_offset_sums), then the offsets' Adam.
+__global__ void __launch_bounds__(256) joint_backward_adam_kernel(
+    const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac, const float* __restrict__ K, int B, int L, int J,
+    int H, int W, float n, float f, const float* __restrict__ link_poses, const float* __restrict__ joint_frames,
+    const unsigned* __restrict__ upstream, const int* __restrict__ joint_kind, const float* __restrict__ red,
+    const int* __restrict__ free_j, float* __restrict__ offset, float* __restrict__ m, float* __restrict__ v,
+    int* __restrict__ step_j, float lr, float b1, float b2, float eps, float wd, float* __restrict__ grad_out) {
+    __shared__ double A[16];                        // PF @ Tc
+    __shared__ double Wr[EHR_JOINT_TILE][9];        // tau (3), f (3), t_l (3) of the tile's pairs
+    __shared__ double S[4][EHR_JOINT_MAX_JOINTS];
+    const int tid = threadIdx.x;
+    bool mine;
+    joint_offset_sums(grad_mvp, tc_jac, K, B, L, J, H, W, n, f, link_poses, joint_frames, upstream, joint_kind, free_j, mine,
+                      A, Wr, S);
+    // a reported step (any of red[0..7] not finite) touches nothing
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
     const int t = step_j[0] + 1;
-    if (tid < J) {
-        if (!mine) {
-            if (grad_out) grad_out[tid] = 0.f;
-        } else if (!ok) {
-            if (grad_out) grad_out[tid] = __int_as_float(0x7fc00000);
-        } else {
-            const float gsum = (float)(((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid]);
-            float g = gsum / red[7];
-            if (grad_out) grad_out[tid] = g;
-            const float p = offset[tid];
-            g = g + wd * p;
-            const float mi = b1 * m[tid] + (1.f - b1) * g;
-            const float vi = b2 * v[tid] + (1.f - b2) * g * g;
-            m[tid] = mi;
-            v[tid] = vi;
-            const float bc1 = 1.f - powf(b1, (float)t);
-            const float bc2 = 1.f - powf(b2, (float)t);
-            const float step_size = lr / bc1;
-            const float rsq_bc2 = sqrtf(bc2);
-            const float denom = sqrtf(vi) / rsq_bc2 + eps;
-            offset[tid] = p - step_size * (mi / denom);
+    if (tid < J)
+        joint_offset_adam(
+            tid, mine, ok, [&]() { return ((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid]; }, red[7], t, offset, m, v, lr, b1,
+            b2, eps, wd, grad_out);
+    __syncthreads();
+    if (tid == 0 && ok) step_j[0] = t;
+}
+
+// The rig's finish stage: C cameras watch one arm and share its joint offsets (easyhec_amd/rig_calib.py).  Single workgroup
+// of 256 threads.  Per camera in order, joint_offset_sums on what that camera's chain left behind; thread tid < J keeps
+// T = S_0 + S_1 + ... in ONE float64 register, n = red_0[7] + red_1[7] + ... in float32.  Then, for the rig as a whole: ok =
+// every red_c[0..7] of every camera is finite (and every camera's B is in range) -> pose_adam_apply per camera on its own
+// red_c and the offsets' Adam on T / n; otherwise nothing moves and every report is NaN.  A camera's struct is read from the
+// device array with uniform loads where it is used: nothing is indexed at run time in a per-thread array.
+__global__ void __launch_bounds__(256) rig_backward_adam_kernel(
+    const ehr_rig_camera* __restrict__ cams, int C, int L, int J, const unsigned* __restrict__ upstream,
+    const int* __restrict__ joint_kind, const int* __restrict__ free_j, float* __restrict__ offset, float* __restrict__ m,
+    float* __restrict__ v, int* __restrict__ step_j, float pose_lr, float offset_lr, float b1, float b2, float eps,
+    float pose_wd, float offset_wd, float* __restrict__ grad_out) {
+    __shared__ double A[16];
+    __shared__ double Wr[EHR_JOINT_TILE][9];
+    __shared__ double S[4][EHR_JOINT_MAX_JOINTS];
+    __shared__ float red_s[8];  // the red that pose_adam_apply judges: camera c's own, or poisoned where the RIG's step is reported
+    const int tid = threadIdx.x;
+    const int j = tid & 31;
+    bool mine = j < J && free_j[j] != 0;
+    bool ok = true;
+    double T = 0.0;
+    float nfr = 0.f;
+    for (int c = 0; c < C; c++) {
+        const ehr_rig_camera* cam = cams + c;
+        const float* red = cam->red;
+#pragma unroll
+        for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
+        const int B = cam->B;
+        // (the array is device memory, so the host cannot judge B: a camera out of range is read nowhere and reports the step)
+        const bool sized = B >= 1 && (long long)B * L <= 0x7fffffffll / 16;
+        ok = ok && sized;
+        if (sized)
+            joint_offset_sums(cam->grad_mvp, cam->tc_jac, cam->K, B, L, J, cam->H, cam->W, cam->near_plane, cam->far_plane,
+                              cam->link_poses, cam->joint_frames, upstream, joint_kind, free_j, mine, A, Wr, S);
+        if (sized && tid < J) {
+            const double s = ((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid];
+            T = c == 0 ? s : T + s;  // (not 0.0 + s: that would turn a sum of -0.0 into +0.0)
         }
+        nfr = c == 0 ? red[7] : nfr + red[7];
     }
+    // every camera's pose: ehr_pose_adam on its own red, or nothing at all
+    for (int c = 0; c < C; c++) {
+        const ehr_rig_camera* cam = cams + c;
+        __syncthreads();  // (the previous camera's red_s has been read)
+        if (tid < 8) red_s[tid] = (ok || tid != 0) ? cam->red[tid] : __int_as_float(0x7fc00000);
+        const AdamState st = pose_adam_fetch(cam->dof, cam->adam_m, cam->adam_v, cam->step);
+        __syncthreads();
+        pose_adam_apply(st, cam->dof, cam->adam_m, cam->adam_v, cam->step, red_s, pose_lr, b1, b2, eps, pose_wd, cam->loss_out,
+                        cam->grad_out);
+    }
+    // the shared offsets: their own counter, offset_lr and offset_wd
+    const int t = step_j[0] + 1;
+    if (tid < J)
+        joint_offset_adam(tid, mine, ok, [&]() { return T; }, nfr, t, offset, m, v, offset_lr, b1, b2, eps, offset_wd, grad_out);
     __syncthreads();
     if (tid == 0 && ok) step_j[0] = t;
 }
@@ -266,6 +357,21 @@ int ehr_joint_backward_adam(const float* grad_mvp, const float* tc_jac, const fl
     joint_backward_adam_kernel<<<1, 256, 0, (hipStream_t)stream>>>(
         grad_mvp, tc_jac, K, B, L, J, H, W, near_plane, far_plane, link_poses, joint_frames, upstream, joint_kind, red,
         free_joints, offset, adam_m, adam_v, step_j, lr, beta1, beta2, eps, weight_decay, grad_out);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_rig_backward_adam(const ehr_rig_camera* cams, int C, int L, int J, const uint32_t* upstream, const int32_t* joint_kind,
+                          const int32_t* free_joints, float* offset, float* adam_m, float* adam_v, int32_t* step_j,
+                          float pose_lr, float offset_lr, float beta1, float beta2, float eps, float pose_wd, float offset_wd,
+                          float* offset_grad_out, void* stream) {
+    if (!cams || !upstream || !joint_kind || !free_joints || !offset || !adam_m || !adam_v || !step_j)
+        return fail(EHR_ERR_INVALID, "ehr_rig_backward_adam: NULL tensor");
+    if (C < 1 || C > EHR_RIG_MAX_CAMERAS || J < 1 || J > EHR_JOINT_MAX_JOINTS || L < 1 || L > 0x7fffffff / 16)
+        return fail(EHR_ERR_INVALID, "ehr_rig_backward_adam: bad sizes (C %d <= 16 cameras, J %d <= 32 joints, L %d)", C, J, L);
+    rig_backward_adam_kernel<<<1, 256, 0, (hipStream_t)stream>>>(cams, C, L, J, upstream, joint_kind, free_joints, offset, adam_m,
+                                                                 adam_v, step_j, pose_lr, offset_lr, beta1, beta2, eps, pose_wd,
+                                                                 offset_wd, offset_grad_out);
     EHR_LAUNCH_CHECK();
     return EHR_OK;
 }

@@ -85,6 +85,10 @@ def _private_weight(batch, dev):
 
 
 class FusedPoseStep(_ChainStep):
+    # private: the chain stops after ``red`` (no Adam, ``loss`` not written) although the solve is not data-parallel -- the
+    # caller finishes the step with a launch of its own (easyhec_amd/rig_calib.py)
+    _stop_after_red = False
+
     def __init__(self, model, batch, lr=0.003, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0005, near=0.001, far=10.0,
                  process_group=None, rccl=None, slack=None, p2p=None):
         self.model = model
@@ -258,7 +262,7 @@ class FusedPoseStep(_ChainStep):
             _lib.ptr(self.hist_row), _f(self.lr), _f(self.betas[0]), _f(self.betas[1]), _f(self.eps), _f(self.wd), _lib.ptr(self.mvp),
             _lib.ptr(self.tc_jac), _lib.ptr(self.mask if want_mask else None), _lib.ptr(self.loss_b),
             _lib.ptr(self.grad_mvp), _lib.ptr(self.red), _lib.ptr(self.loss), _lib.ptr(self.grad),
-            int(self.distributed or self.rccl), stream), "ehr_solver_step")
+            int(self.distributed or self.rccl or self._stop_after_red), stream), "ehr_solver_step")
         if self.p2p:
             # the exchange and Adam in ONE launch: stores into the peers' mailboxes, a wait on the own one, sums in rank order
             _lib.check(lib.ehr_comm_p2p_step(self.glctx.handle, _lib.ptr(self.red), _lib.ptr(dof), _lib.ptr(self.exp_avg),

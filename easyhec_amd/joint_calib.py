@@ -209,14 +209,20 @@ class JointOffsetResult:
     step: object = None         # the JointPoseStep (corrected_link_poses(), state_dict())
 
 
-def solve_joint_offsets(cfg, model, batch, robot, num_steps, qpos=None, capture=True, **kw):
-    """``num_steps`` EFFECTIVE steps of the joint solve with the optimiser settings of ``cfg.solver`` (Adam: lr, weight
-    decay), from a captured graph, with the loop ``RBSolverTrainer.fit`` uses: a reported step is recovered from and taken
-    again.  ``kw``: :class:`JointPoseStep`'s keywords."""
+def _check_solver_settings(cfg, kw):
+    """The solver-settings check of the one-call solves (this one and ``rig_calib.solve_rig``); fills in ``cfg.solver``'s lr
+    and weight decay where ``kw`` has none."""
     if cfg.solver.do_grad_clip or cfg.solver.optimizer != "Adam":
         raise ValueError("the launch chain implements the reference's default solver only (Adam, no gradient clipping)")
     kw.setdefault("lr", cfg.solver.max_lr)
     kw.setdefault("weight_decay", cfg.solver.weight_decay)
+
+
+def solve_joint_offsets(cfg, model, batch, robot, num_steps, qpos=None, capture=True, **kw):
+    """``num_steps`` EFFECTIVE steps of the joint solve with the optimiser settings of ``cfg.solver`` (Adam: lr, weight
+    decay), from a captured graph, with the loop ``RBSolverTrainer.fit`` uses: a reported step is recovered from and taken
+    again.  ``kw``: :class:`JointPoseStep`'s keywords."""
+    _check_solver_settings(cfg, kw)
     js = JointPoseStep(model, batch, robot, qpos, **kw)
     if capture:
         js.capture()

@@ -423,6 +423,39 @@ int ehr_joint_backward_adam(const float* grad_mvp, const float* tc_jac, const fl
                             float* offset, float* adam_m, float* adam_v, int32_t* step_j, float lr, float beta1, float beta2,
                             float eps, float weight_decay, float* grad_out, void* stream);
 
+/* Camera-rig calibration: C fixed cameras watch ONE arm, and every camera constrains the same joint offsets.  Each camera runs
+ * its own  ehr_joint_forward (with the SHARED offset pointer, into its own link_poses / joint_frames) -> ehr_solver_step(
+ * defer_adam = 1)  on its own context, views, K and image size; then ONE launch of a single 256-thread workgroup finishes the
+ * step for the whole rig.  `cams` is a DEVICE array of C <= 16 structs of device pointers (what camera c's chain left behind,
+ * and its pose's Adam group); L and J are the rig's (one robot).  No atomics, no allocation, no synchronisation; capturable.
+ *   per camera, in order : S_c[j] = the float64 sum ehr_joint_backward_adam forms for that camera alone (same expressions,
+ *                          tiles starting at that camera's pair 0, same order, same combination of the four waves);
+ *   the rig              : T[j] = S_0[j] + S_1[j] + ... in float64, n = red_0[7] + red_1[7] + ... in float32 (camera order),
+ *                          g_j = (float)T[j] / n: the gradient of the MEAN per-view loss over all views of all cameras.
+ *                          With C == 1 every value is ehr_joint_backward_adam's, bit for bit.
+ *   all or nothing       : ok = every red_c[0..7] of every camera passes ehr_pose_adam's `< 3.0e38f` test (and every B_c is in
+ *                          range: B_c >= 1, B_c * L <= INT_MAX / 16 -- the array is device memory, so this is judged on the
+ *                          device, and such a camera is read nowhere).  If ok, camera c's dof / adam_m / adam_v / step get
+ *                          ehr_pose_adam's update on its own red_c (pose_lr, pose_wd; loss_out[0] = red_c[6] / red_c[7],
+ *                          grad_out [6] optional) bit for bit, and the free joints get ehr_joint_backward_adam's update on g_j
+ *                          with the offsets' own counter step_j, offset_lr and offset_wd; a joint that is not free keeps
+ *                          everything and reports offset_grad_out[j] = 0.  If not ok, NOTHING moves -- no camera's pose group,
+ *                          not the offsets' -- every camera's loss_out (and grad_out) is NaN and the free joints'
+ *                          offset_grad_out is NaN: a report is rig-wide, as it is step-wide in ehr_solver_step_multi, and every
+ *                          camera's chain re-uses its history row on the next call by its own rule.
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+typedef struct {            /* one camera of the rig; all pointers are device pointers */
+    const float *grad_mvp, *tc_jac, *K, *link_poses, *joint_frames, *red;   /* what that camera's chain left behind */
+    float *dof, *adam_m, *adam_v; int32_t *step;  float *loss_out, *grad_out; /* its pose's Adam group */
+    int B, H, W;  float near_plane, far_plane;
+} ehr_rig_camera;
+
+int ehr_rig_backward_adam(const ehr_rig_camera* cams /* DEVICE array [C] */, int C, int L, int J,
+        const uint32_t* upstream, const int32_t* joint_kind, const int32_t* free_joints,
+        float* offset, float* adam_m, float* adam_v, int32_t* step_j,
+        float pose_lr, float offset_lr, float beta1, float beta2, float eps, float pose_wd, float offset_wd,
+        float* offset_grad_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
