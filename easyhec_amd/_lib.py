@@ -80,6 +80,8 @@ SIGNATURES = {
     "ehr_joint_backward_adam": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 10 + [c_float] * 5 +
                                 [c_void_p, c_void_p]),
     "ehr_rig_backward_adam": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 7 + [c_float] * 7 + [c_void_p, c_void_p]),
+    "ehr_intrinsics_backward_adam": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4 +
+                                     [c_float] * 5 + [c_void_p] * 3),
 }
 
 
@@ -140,6 +142,14 @@ def has_rig():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_rig_backward_adam")
+
+
+def has_intrinsics():
+    """True if the library has the intrinsics refinement's kernel (``ehr_intrinsics_backward_adam``); the symbol's presence
+    is the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_intrinsics_backward_adam")
 
 
 class RigCamera(ctypes.Structure):

@@ -1,0 +1,192 @@
+// ehr_intrinsics.hip -- intrinsics refinement: the one small kernel that follows the solver step's launch chain when the
+// focal lengths and the principal point are fitted together with the camera pose (easyhec_amd/intrinsics_calib.py).
+//
+//   theta [4] float32, dimensionless:   fu = K0[0] exp(theta0)   fv = K0[4] exp(theta1)   cu = K0[2] + W theta2   cv = K0[5] + H theta3
+//   intrinsics_backward_adam: grad_mvp [B,L,16] (written by the chain) -> d(sum_b loss_b) / d theta.  MVP_bl = P(K) @ A_bl with
+//                        A_bl = F @ Tc @ link_poses[b,l], F = diag(1,-1,-1,1), Tc = tc_jac[0:16] (the pose that was rendered),
+//                        and projection() is linear in fu, fv, cu, cv: P[0] = 2 fu / W, P[5] = 2 fv / H, P[2] = 1 - 2 cu / W,
+//                        P[6] = 2 cv / H - 1.  With Q[r,k] = sum_{b,l} sum_c grad_mvp[b,l][r,c] A_bl[k,c]:
+//                            s0 = fu (2/W) Q[0,0]    s1 = fv (2/H) Q[1,1]    s2 = -2 Q[0,2]    s3 = 2 Q[1,2]
+//                        -> the Adam update of pose_adam_apply on the free elements -> the K the next step's vertex head reads.
+//
+// The kernel does not allocate, synchronise or use an atomic: results are bit-reproducible from run to run.
+#include "ehr_host.h"
+#include "ehr_pose_core.h"
+
+namespace ehr {
+
+// One entry of K from K0 and its parameter, evaluated in float64 and rounded once.  i: 0 fu, 1 fv, 2 cu, 3 cv.  A parameter
+// that is exactly zero gives K0's bits (selected, not left to exp(0.0) == 1.0).
+__device__ __forceinline__ float intrinsics_entry(const float* __restrict__ K0, float th, int i, int H, int W) {
+    const float k0 = K0[i == 0 ? 0 : (i == 1 ? 4 : (i == 2 ? 2 : 5))];
+    double x;
+    if (i < 2)
+        x = (double)k0 * exp((double)th);
+    else
+        x = (double)k0 + (double)(i == 2 ? W : H) * (double)th;
+    return th == 0.f ? k0 : (float)x;
+}
+
+// LDS of intrinsics_adam: the group's state in the six-element layout pose_adam_apply works on.
+struct IntrinsicsStage {
+    double d[4];   // s0..s3
+    float red[8];  // what pose_adam_apply judges and divides: the four sums, 0, 0, the chain's verdict, red[7]
+    float p[8], m[8], v[8], g[8];
+    int step;
+};
+
+// Q[0,0], Q[1,1], Q[0,2], Q[1,2] of one camera; call with all 256 threads of the single workgroup.  Thread t adds pairs t,
+// t + 256, ... in order into four float64 accumulators of its own (products and sums float64 from float32 inputs); every wave
+// combines with wave_sum_f64 and leaves its four sums in S[wave][0..3], which the caller adds in order: ((S0 + S1) + S2) + S3.
+// Ends on a barrier (S is readable); its write to S comes after a barrier of its own, so a caller may read S and call again.
+__device__ __forceinline__ void intrinsics_sums(const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac,
+                                                const float* __restrict__ link_poses, int B, int L, double (*S)[4]) {
+    const int tid = threadIdx.x;
+    double T[3][4];  // rows 0..2 of Tc = tc_jac[0:16]: the pose this step rendered
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) T[k][j] = (double)tc_jac[4 * k + j];
+    double q00 = 0.0, q11 = 0.0, q02 = 0.0, q12 = 0.0;
+    const int BL = B * L;
+    for (int i = tid; i < BL; i += 256) {
+        float g[8], lp[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) lp[k] = link_poses[(size_t)i * 16 + k];
+#pragma unroll
+        for (int k = 0; k < 8; k++) g[k] = grad_mvp[(size_t)i * 16 + k];
+        double A[3][4];  // rows 0..2 of F @ Tc @ lp
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const double a = ((T[k][0] * (double)lp[c] + T[k][1] * (double)lp[4 + c]) + T[k][2] * (double)lp[8 + c]) +
+                                 T[k][3] * (double)lp[12 + c];
+                A[k][c] = k == 0 ? a : -a;
+            }
+        q00 += ((double)g[0] * A[0][0] + (double)g[1] * A[0][1]) + ((double)g[2] * A[0][2] + (double)g[3] * A[0][3]);
+        q11 += ((double)g[4] * A[1][0] + (double)g[5] * A[1][1]) + ((double)g[6] * A[1][2] + (double)g[7] * A[1][3]);
+        q02 += ((double)g[0] * A[2][0] + (double)g[1] * A[2][1]) + ((double)g[2] * A[2][2] + (double)g[3] * A[2][3]);
+        q12 += ((double)g[4] * A[2][0] + (double)g[5] * A[2][1]) + ((double)g[6] * A[2][2] + (double)g[7] * A[2][3]);
+    }
+    q00 = wave_sum_f64(q00);
+    q11 = wave_sum_f64(q11);
+    q02 = wave_sum_f64(q02);
+    q12 = wave_sum_f64(q12);
+    __syncthreads();  // (a previous call's S has been read)
+    if ((tid & 63) == 0) {
+        S[tid >> 6][0] = q00;
+        S[tid >> 6][1] = q11;
+        S[tid >> 6][2] = q02;
+        S[tid >> 6][3] = q12;
+    }
+    __syncthreads();
+}
+
+// The group's Adam and the new K; call with all 256 threads.  Element i < 4 is thread i's.  The update itself is
+// pose_adam_apply's, called on a six-element staging copy of the group in LDS (elements 4 and 5 are zero padding): its
+// verdict covers red[0..7] of the chain (carried in slot 6 of the staged red) and the four sums.  Only the free elements are
+// copied back; a reported step copies nothing back and leaves K alone.
+__device__ __forceinline__ void intrinsics_adam(double (*S)[4], const float* __restrict__ red, const float* __restrict__ K0,
+                                                const int* __restrict__ free4, int tie_focal, int H, int W,
+                                                float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
+                                                int* __restrict__ step_k, float lr, float b1, float b2, float eps, float wd,
+                                                float* __restrict__ K, float* __restrict__ grad_out, IntrinsicsStage& st) {
+    const int tid = threadIdx.x;
+    const bool mine = tid < 4 && free4[tid] != 0;
+    AdamState as;
+    as.p = as.m = as.v = 0.f;
+    as.step_size = as.rsq_bc2 = 0.f;
+    as.has_bias = false;
+    as.t = step_k[0] + 1;
+    if (tid < 4) {
+        as.p = theta[tid];
+        as.m = m[tid];
+        as.v = v[tid];
+        const double q = ((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid];
+        double d;
+        if (tid < 2)  // fu, fv as rendered: from theta before this update
+            d = (double)intrinsics_entry(K0, as.p, tid, H, W) * (2.0 / (double)(tid == 0 ? W : H)) * q;
+        else
+            d = (tid == 2 ? -2.0 : 2.0) * q;
+        st.d[tid] = d;
+    }
+    if (tid == 0) st.step = as.t - 1;
+    __syncthreads();
+    if (tid < 8) {
+        float r = 0.f;
+        if (tid < 4) {
+            const double d = (tie_focal != 0 && tid < 2) ? st.d[0] + st.d[1] : st.d[tid];
+            r = mine ? (float)d : 0.f;
+        } else if (tid == 6) {  // the chain's own red: a reported step touches nothing
+            bool ok = true;
+#pragma unroll
+            for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
+            r = ok ? 0.f : __int_as_float(0x7fc00000);
+        } else if (tid == 7) {
+            r = red[7];
+        }
+        st.red[tid] = r;
+    }
+    __syncthreads();
+    pose_adam_apply(as, st.p, st.m, st.v, &st.step, st.red, lr, b1, b2, eps, wd, nullptr, st.g);
+    __syncthreads();
+    const bool ok = st.step == as.t;
+    if (tid < 4) {
+        if (!mine) {
+            if (grad_out) grad_out[tid] = 0.f;
+        } else {
+            if (grad_out) grad_out[tid] = st.g[tid];  // (NaN where the step is reported)
+            if (ok) {
+                theta[tid] = st.p[tid];
+                m[tid] = st.m[tid];
+                v[tid] = st.v[tid];
+            }
+        }
+    }
+    if (tid < 9 && ok) {
+        const int i = tid == 0 ? 0 : (tid == 4 ? 1 : (tid == 2 ? 2 : (tid == 5 ? 3 : -1)));
+        float out = K0[tid];
+        if (i >= 0) {
+            const float th = free4[i] != 0 ? st.p[i] : theta[i];  // (a free element's new value is in LDS; the others do not move)
+            out = intrinsics_entry(K0, th, i, H, W);
+        }
+        K[tid] = out;
+    }
+    if (tid == 0 && ok) step_k[0] = as.t;
+}
+
+// Single workgroup of 256 threads: the sums, then the group's Adam and the K of the next step.
+__global__ void __launch_bounds__(256) intrinsics_backward_adam_kernel(
+    const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac, const float* __restrict__ link_poses, int B, int L,
+    int H, int W, const float* __restrict__ red, const float* __restrict__ K0, const int* __restrict__ free4, int tie_focal,
+    float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v, int* __restrict__ step_k, float lr, float b1,
+    float b2, float eps, float wd, float* __restrict__ K, float* __restrict__ grad_out) {
+    __shared__ double S[4][4];
+    __shared__ IntrinsicsStage st;
+    intrinsics_sums(grad_mvp, tc_jac, link_poses, B, L, S);
+    intrinsics_adam(S, red, K0, free4, tie_focal, H, W, theta, m, v, step_k, lr, b1, b2, eps, wd, K, grad_out, st);
+}
+
+}  // namespace ehr
+
+using namespace ehr;
+
+extern "C" {
+
+int ehr_intrinsics_backward_adam(const float* grad_mvp, const float* tc_jac, const float* link_poses, int B, int L, int H,
+                                 int W, const float* red, const float* K0, const int32_t* free4, int tie_focal, float* theta,
+                                 float* adam_m, float* adam_v, int32_t* step_k, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float* K, float* grad_out, void* stream) {
+    if (!grad_mvp || !tc_jac || !link_poses || !red || !K0 || !free4 || !theta || !adam_m || !adam_v || !step_k || !K)
+        return fail(EHR_ERR_INVALID, "ehr_intrinsics_backward_adam: NULL tensor");
+    if (L < 1 || B < 1 || (long long)B * L > 0x7fffffffll / 16 || H < 1 || W < 1)
+        return fail(EHR_ERR_INVALID, "ehr_intrinsics_backward_adam: bad sizes (L %d, B %d, H %d, W %d)", L, B, H, W);
+    intrinsics_backward_adam_kernel<<<1, 256, 0, (hipStream_t)stream>>>(grad_mvp, tc_jac, link_poses, B, L, H, W, red, K0,
+                                                                        free4, tie_focal, theta, adam_m, adam_v, step_k, lr,
+                                                                        beta1, beta2, eps, weight_decay, K, grad_out);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+}  // extern "C"

@@ -456,6 +456,40 @@ int ehr_rig_backward_adam(const ehr_rig_camera* cams /* DEVICE array [C] */, int
         float pose_lr, float offset_lr, float beta1, float beta2, float eps, float pose_wd, float offset_wd,
         float* offset_grad_out, void* stream);
 
+/* Intrinsics refinement: the focal lengths and the principal point are fitted together with the camera pose.  ONE small kernel
+ * AFTER the launch chain of ehr_solver_step, which itself is unchanged: it reads K (nine floats) from device memory on every
+ * call and leaves grad_mvp [B,L,16] and the pose it rendered (tc_jac[0:16]) behind.  A step is
+ *     ehr_solver_step -> ehr_intrinsics_backward_adam        on one stream
+ * (with joint offsets: ehr_joint_forward -> ehr_solver_step -> ehr_joint_backward_adam -> ehr_intrinsics_backward_adam; the
+ * joint kernel reads K as rendered, so the launch that rewrites K runs last).  Device pointers only; never allocates or
+ * synchronises; launches on `stream`: between ehr_graph_begin and ehr_graph_end it is captured together with the chain.
+ *   parameters : K0 [9] float32 = the intrinsics as given (never written), theta [4] float32, dimensionless:
+ *                    fu = K0[0] exp(theta0)    fv = K0[4] exp(theta1)    cu = K0[2] + W theta2    cv = K0[5] + H theta3
+ *   writing K  : K[0], K[4], K[2], K[5] are evaluated in float64 and rounded once; the other five entries are K0's; an entry
+ *                whose theta is exactly 0 is written with K0's bits (selected, not left to exp(0) == 1).
+ *   gradient   : A_bl = F @ Tc @ link_poses[b,l] with F = diag(1,-1,-1,1) and Tc = tc_jac[0:16] (NOT recomputed from dof, which
+ *                Adam has already moved), Q[r,k] = sum_{b,l} sum_c grad_mvp[b,l][r,c] A_bl[k,c], and for d(sum_b loss_b)/d theta
+ *                    s0 = fu (2/W) Q[0,0]    s1 = fv (2/H) Q[1,1]    s2 = -2 Q[0,2]    s3 = 2 Q[1,2]
+ *                with fu, fv as rendered (from theta BEFORE this update).  Products and sums are float64 from float32 inputs in
+ *                a fixed order, no atomics: thread t of the single 256-thread workgroup adds pairs t, t + 256, ... in order,
+ *                each wave combines by a shuffle butterfly, the four waves add in order.  Bit-reproducible.
+ *   free, tie  : free4 [4] int32; an element that is not free keeps theta and its moments and reports grad_out == +0.  With
+ *                tie_focal != 0 both focal elements take s0 + s1, the derivative with respect to ONE common log-scale: from
+ *                equal starts (theta, moments) they stay equal bit for bit.
+ *   Adam       : ehr_pose_adam's update per element on g_i = (float)s_i / red[7] with L2 weight decay; theta, adam_m, adam_v
+ *                [4] and step_k [1] are this parameter group's own state (its own counter, lr and weight decay); grad_out [4]
+ *                may be NULL.  red [8] is the solver step's: if any of red[0..7] fails the pose Adam's `< 3.0e38f` test (a
+ *                REPORTED step), or a free element's float32 sum does, nothing of the group moves, K is left as it is and the
+ *                free elements' grad_out is NaN -- the chain then renders the same K again and its own recovery (the same
+ *                history row again, the general-triangle pass, a new plan) works unchanged.
+ * Out of scope: per-camera intrinsics inside ehr_rig_backward_adam, a data-parallel job (the gradient would need an exchange of
+ * its own), ehr_solver_step_multi (the hypotheses share ONE K), lens distortion, skew, per-view intrinsics.
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+int ehr_intrinsics_backward_adam(const float* grad_mvp, const float* tc_jac, const float* link_poses, int B, int L,
+                                 int H, int W, const float* red, const float* K0, const int32_t* free4, int tie_focal,
+                                 float* theta, float* adam_m, float* adam_v, int32_t* step_k, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, float* K, float* grad_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
