@@ -17,6 +17,14 @@ import torch
 from . import _lib, fused
 
 
+def check_solver_settings(cfg, what="the launch chain"):
+    """The one check of ``cfg.solver`` for everything that steps a launch chain (``what``: the caller's name for it in the
+    message); returns the constructors' ``lr`` / ``weight_decay`` keywords from it."""
+    if cfg.solver.do_grad_clip or cfg.solver.optimizer != "Adam":
+        raise ValueError(f"{what} implements the reference's default solver only (Adam, no gradient clipping)")
+    return {"lr": cfg.solver.max_lr, "weight_decay": cfg.solver.weight_decay}
+
+
 class _ReportedStepProtocol:
     """The protocol around a REPORTED step, in one place for every stepper (``_ChainStep``; the camera rig of
     easyhec_amd/rig_calib.py, which drives several chains): the non-blocking look at the loss and the loop that takes an
@@ -63,6 +71,19 @@ class _ReportedStepProtocol:
                     self._check_status()
                     raise RuntimeError(f"{who}: {n - done} of {n} steps keep being reported as not taken (NaN loss)")
                 self._recover_and_note()
+
+    def take_effective_steps(self, n, who):
+        """Takes exactly ``n`` EFFECTIVE steps with :meth:`effective_rounds` and returns ``[>= n, loss.numel()]`` (CPU): the
+        ``loss`` of every step that was not reported, in order.  One device log per round, filled by copies on the stream;
+        the first wait is the copy to the host at the end."""
+        logs = []
+        for remaining, _ in self.effective_rounds(n, who):
+            log = torch.empty((remaining, self.loss.numel()), device=self.dev)
+            for it in range(remaining):
+                log[it].copy_(self.step())
+            logs.append(log)
+        hist = torch.cat(logs).cpu() if logs else torch.zeros((0, self.loss.numel()))
+        return hist[~torch.isnan(hist).all(dim=1)]  # (reported steps: NaN in every element, taken by nobody)
 
 
 class _ChainStep(_ReportedStepProtocol):

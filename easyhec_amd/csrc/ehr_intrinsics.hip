@@ -7,11 +7,12 @@
 //                        and projection() is linear in fu, fv, cu, cv: P[0] = 2 fu / W, P[5] = 2 fv / H, P[2] = 1 - 2 cu / W,
 //                        P[6] = 2 cv / H - 1.  With Q[r,k] = sum_{b,l} sum_c grad_mvp[b,l][r,c] A_bl[k,c]:
 //                            s0 = fu (2/W) Q[0,0]    s1 = fv (2/H) Q[1,1]    s2 = -2 Q[0,2]    s3 = 2 Q[1,2]
-//                        -> the Adam update of pose_adam_apply on the free elements -> the K the next step's vertex head reads.
+//                        -> the Adam update (group_adam) on the free elements -> the K the next step's vertex head reads.
 //
 // The kernel does not allocate, synchronise or use an atomic: results are bit-reproducible from run to run.
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
+#include "ehr_group_adam.h"
 
 namespace ehr {
 
@@ -26,14 +27,6 @@ __device__ __forceinline__ float intrinsics_entry(const float* __restrict__ K0, 
         x = (double)k0 + (double)(i == 2 ? W : H) * (double)th;
     return th == 0.f ? k0 : (float)x;
 }
-
-// LDS of intrinsics_adam: the group's state in the six-element layout pose_adam_apply works on.
-struct IntrinsicsStage {
-    double d[4];   // s0..s3
-    float red[8];  // what pose_adam_apply judges and divides: the four sums, 0, 0, the chain's verdict, red[7]
-    float p[8], m[8], v[8], g[8];
-    int step;
-};
 
 // Q[0,0], Q[1,1], Q[0,2], Q[1,2] of one camera; call with all 256 threads of the single workgroup.  Thread t adds pairs t,
 // t + 256, ... in order into four float64 accumulators of its own (products and sums float64 from float32 inputs); every wave
@@ -83,77 +76,43 @@ __device__ __forceinline__ void intrinsics_sums(const float* __restrict__ grad_m
     __syncthreads();
 }
 
-// The group's Adam and the new K; call with all 256 threads.  Element i < 4 is thread i's.  The update itself is
-// pose_adam_apply's, called on a six-element staging copy of the group in LDS (elements 4 and 5 are zero padding): its
-// verdict covers red[0..7] of the chain (carried in slot 6 of the staged red) and the four sums.  Only the free elements are
-// copied back; a reported step copies nothing back and leaves K alone.
+// The group's Adam and the new K; call with all 256 threads, behind intrinsics_sums' barrier.  The work is wave 0's alone, so
+// it needs no barrier and no LDS of its own: element i < 4 is lane i's (its sum s_i in float64; fu, fv as rendered, i.e. from
+// theta before this update; group_adam), which also writes its entry of K; lanes 4..8 write the entries that are K0's.  The
+// verdict is the chain's own (red[0..7] finite) and every FREE element's float32 sum finite.  A reported step leaves K alone.
 __device__ __forceinline__ void intrinsics_adam(double (*S)[4], const float* __restrict__ red, const float* __restrict__ K0,
                                                 const int* __restrict__ free4, int tie_focal, int H, int W,
                                                 float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v,
                                                 int* __restrict__ step_k, float lr, float b1, float b2, float eps, float wd,
-                                                float* __restrict__ K, float* __restrict__ grad_out, IntrinsicsStage& st) {
-    const int tid = threadIdx.x;
+                                                float* __restrict__ K, float* __restrict__ grad_out) {
+    const int tid = threadIdx.x & 63;  // the lane: wave 0 goes on alone
+    if (threadIdx.x >= 64) return;
     const bool mine = tid < 4 && free4[tid] != 0;
-    AdamState as;
-    as.p = as.m = as.v = 0.f;
-    as.step_size = as.rsq_bc2 = 0.f;
-    as.has_bias = false;
-    as.t = step_k[0] + 1;
+    double d = 0.0;
     if (tid < 4) {
-        as.p = theta[tid];
-        as.m = m[tid];
-        as.v = v[tid];
         const double q = ((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid];
-        double d;
-        if (tid < 2)  // fu, fv as rendered: from theta before this update
-            d = (double)intrinsics_entry(K0, as.p, tid, H, W) * (2.0 / (double)(tid == 0 ? W : H)) * q;
+        if (tid < 2)
+            d = (double)intrinsics_entry(K0, theta[tid], tid, H, W) * (2.0 / (double)(tid == 0 ? W : H)) * q;
         else
             d = (tid == 2 ? -2.0 : 2.0) * q;
-        st.d[tid] = d;
     }
-    if (tid == 0) st.step = as.t - 1;
-    __syncthreads();
-    if (tid < 8) {
-        float r = 0.f;
-        if (tid < 4) {
-            const double d = (tie_focal != 0 && tid < 2) ? st.d[0] + st.d[1] : st.d[tid];
-            r = mine ? (float)d : 0.f;
-        } else if (tid == 6) {  // the chain's own red: a reported step touches nothing
-            bool ok = true;
+    const double other = wave_xor<1>(d);  // (lanes 0 and 1: each other's sum)
+    if (tie_focal != 0 && tid < 2) d = tid == 0 ? d + other : other + d;  // s0 + s1 for both
+    bool ok = true;
 #pragma unroll
-            for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
-            r = ok ? 0.f : __int_as_float(0x7fc00000);
-        } else if (tid == 7) {
-            r = red[7];
-        }
-        st.red[tid] = r;
-    }
-    __syncthreads();
-    pose_adam_apply(as, st.p, st.m, st.v, &st.step, st.red, lr, b1, b2, eps, wd, nullptr, st.g);
-    __syncthreads();
-    const bool ok = st.step == as.t;
-    if (tid < 4) {
-        if (!mine) {
-            if (grad_out) grad_out[tid] = 0.f;
-        } else {
-            if (grad_out) grad_out[tid] = st.g[tid];  // (NaN where the step is reported)
-            if (ok) {
-                theta[tid] = st.p[tid];
-                m[tid] = st.m[tid];
-                v[tid] = st.v[tid];
-            }
-        }
-    }
+    for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
+    ok = ok && __ballot(mine && !(fabsf((float)d) < 3.0e38f)) == 0;
+    const int t = step_k[0] + 1;
+    if (tid < 4) group_adam(tid, mine, ok, [&]() { return d; }, red[7], t, theta, m, v, lr, b1, b2, eps, wd, grad_out);
     if (tid < 9 && ok) {
-        const int i = tid == 0 ? 0 : (tid == 4 ? 1 : (tid == 2 ? 2 : (tid == 5 ? 3 : -1)));
-        float out = K0[tid];
-        if (i >= 0) {
-            const float th = free4[i] != 0 ? st.p[i] : theta[i];  // (a free element's new value is in LDS; the others do not move)
-            out = intrinsics_entry(K0, th, i, H, W);
-        }
-        K[tid] = out;
+        const int i = tid == 0 ? 0 : (tid == 1 ? 4 : (tid == 2 ? 2 : (tid == 3 ? 5 : -1)));  // lane i < 4: its entry of K
+        const int rest = tid == 4 ? 1 : (tid == 5 ? 3 : tid);  // lanes 4..8: entries 1, 3, 6, 7, 8
+        if (i >= 0)
+            K[i] = intrinsics_entry(K0, theta[tid], tid, H, W);
+        else
+            K[rest] = K0[rest];
     }
-    if (tid == 0 && ok) step_k[0] = as.t;
+    if (tid == 0 && ok) step_k[0] = t;
 }
 
 // Single workgroup of 256 threads: the sums, then the group's Adam and the K of the next step.
@@ -163,9 +122,8 @@ __global__ void __launch_bounds__(256) intrinsics_backward_adam_kernel(
     float* __restrict__ theta, float* __restrict__ m, float* __restrict__ v, int* __restrict__ step_k, float lr, float b1,
     float b2, float eps, float wd, float* __restrict__ K, float* __restrict__ grad_out) {
     __shared__ double S[4][4];
-    __shared__ IntrinsicsStage st;
     intrinsics_sums(grad_mvp, tc_jac, link_poses, B, L, S);
-    intrinsics_adam(S, red, K0, free4, tie_focal, H, W, theta, m, v, step_k, lr, b1, b2, eps, wd, K, grad_out, st);
+    intrinsics_adam(S, red, K0, free4, tie_focal, H, W, theta, m, v, step_k, lr, b1, b2, eps, wd, K, grad_out);
 }
 
 }  // namespace ehr

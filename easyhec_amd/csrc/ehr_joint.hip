@@ -17,6 +17,7 @@
 // No kernel here allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
+#include "ehr_group_adam.h"
 
 #define EHR_JOINT_MAX_LINKS 64
 #define EHR_JOINT_MAX_JOINTS 32
@@ -210,37 +211,6 @@ __device__ __forceinline__ void joint_offset_sums(const float* __restrict__ grad
     __syncthreads();
 }
 
-// The offsets' Adam for thread tid < J: pose_adam_apply's expressions per element on g = (float)sum() / nfr.  A joint that is
-// not free keeps everything and reports 0; a reported step (!ok) touches nothing and reports NaN for the free joints.
-// sum() returns the joint's float64 sum and is called where the step counts only.
-template <class Sum>
-__device__ __forceinline__ void joint_offset_adam(int tid, bool mine, bool ok, Sum sum, float nfr, int t,
-                                                  float* __restrict__ offset, float* __restrict__ m, float* __restrict__ v,
-                                                  float lr, float b1, float b2, float eps, float wd,
-                                                  float* __restrict__ grad_out) {
-    if (!mine) {
-        if (grad_out) grad_out[tid] = 0.f;
-    } else if (!ok) {
-        if (grad_out) grad_out[tid] = __int_as_float(0x7fc00000);
-    } else {
-        const float gsum = (float)sum();
-        float g = gsum / nfr;
-        if (grad_out) grad_out[tid] = g;
-        const float p = offset[tid];
-        g = g + wd * p;
-        const float mi = b1 * m[tid] + (1.f - b1) * g;
-        const float vi = b2 * v[tid] + (1.f - b2) * g * g;
-        m[tid] = mi;
-        v[tid] = vi;
-        const float bc1 = 1.f - powf(b1, (float)t);
-        const float bc2 = 1.f - powf(b2, (float)t);
-        const float step_size = lr / bc1;
-        const float rsq_bc2 = sqrtf(bc2);
-        const float denom = sqrtf(vi) / rsq_bc2 + eps;
-        offset[tid] = p - step_size * (mi / denom);
-    }
-}
-
 // Single workgroup of 256 threads: one camera's sum (joint_offset_sums), then the offsets' Adam.
 __global__ void __launch_bounds__(256) joint_backward_adam_kernel(
     const float* __restrict__ grad_mvp, const float* __restrict__ tc_jac, const float* __restrict__ K, int B, int L, int J,
@@ -261,7 +231,7 @@ __global__ void __launch_bounds__(256) joint_backward_adam_kernel(
     for (int k = 0; k < 8; k++) ok = ok && (fabsf(red[k]) < 3.0e38f);
     const int t = step_j[0] + 1;
     if (tid < J)
-        joint_offset_adam(
+        group_adam(
             tid, mine, ok, [&]() { return ((S[0][tid] + S[1][tid]) + S[2][tid]) + S[3][tid]; }, red[7], t, offset, m, v, lr, b1,
             b2, eps, wd, grad_out);
     __syncthreads();
@@ -320,7 +290,7 @@ __global__ void __launch_bounds__(256) rig_backward_adam_kernel(
     // the shared offsets: their own counter, offset_lr and offset_wd
     const int t = step_j[0] + 1;
     if (tid < J)
-        joint_offset_adam(tid, mine, ok, [&]() { return T; }, nfr, t, offset, m, v, offset_lr, b1, b2, eps, offset_wd, grad_out);
+        group_adam(tid, mine, ok, [&]() { return T; }, nfr, t, offset, m, v, offset_lr, b1, b2, eps, offset_wd, grad_out);
     __syncthreads();
     if (tid == 0 && ok) step_j[0] = t;
 }

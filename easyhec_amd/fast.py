@@ -20,8 +20,11 @@ import torch.distributed as dist
 
 from . import _lib
 from .chain_step import _ChainStep
+from .param_group import AdamGroup
 
 __all__ = ["FusedPoseStep", "choose_exchange"]
+
+POSE_LR, POSE_WEIGHT_DECAY = 0.003, 0.0005  # Adam's defaults for the pose, and for every group that is not given its own
 
 
 def _f(x):
@@ -84,13 +87,30 @@ def _private_weight(batch, dev):
     return None if w is None else w.to(dev, torch.float32).contiguous().clone()
 
 
-class FusedPoseStep(_ChainStep):
-    # private: the chain stops after ``red`` (no Adam, ``loss`` not written) although the solve is not data-parallel -- the
-    # caller finishes the step with a launch of its own (easyhec_amd/rig_calib.py)
-    _stop_after_red = False
+def refuse_unsupported(kw, available, starts, data_parallel, missing):
+    """The refusals every solve built on ``FusedPoseStep`` makes before it constructs one, each raised with the caller's
+    own reason: ``starts=`` among the keywords ``kw`` (a call ported from ``MultiStartPoseStep`` gets the reason, not a
+    TypeError about a keyword), a data-parallel job, and a library without the solve's kernels (``available()`` false)."""
+    if "starts" in kw:
+        raise ValueError(starts)
+    pg = kw.get("process_group")
+    if kw.get("rccl") or kw.get("p2p") or (dist.is_available() and dist.is_initialized() and dist.get_world_size(pg) > 1):
+        raise ValueError(data_parallel)
+    if not available():
+        raise RuntimeError(missing)
 
-    def __init__(self, model, batch, lr=0.003, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0005, near=0.001, far=10.0,
-                 process_group=None, rccl=None, slack=None, p2p=None):
+
+class FusedPoseStep(_ChainStep):
+    def __init__(self, model, batch, lr=POSE_LR, betas=(0.9, 0.999), eps=1e-8, weight_decay=POSE_WEIGHT_DECAY, near=0.001,
+                 far=10.0, process_group=None, rccl=None, slack=None, p2p=None, *, loss=None, defer_adam=False):
+        """loss: the [1] device tensor the step's loss goes to (default: one of its own; a camera of a rig gets its element
+        of the rig's).  defer_adam: the chain stops after ``red`` (no Adam, ``loss`` not written) although the solve is not
+        data-parallel -- the caller finishes the step with a launch of its own (easyhec_amd/rig_calib.py).
+
+        A calibration solve is this class built with more launches around the chain, each a part the step holds:
+        ``_before`` (``launch(step, stream)``) runs ahead of the chain, ``_after`` behind it, in order; a part of ``_after``
+        also adds its parameter group to the state dict (``add_state`` / ``check_state`` / ``load_state``) and says whether
+        its launch ``rewrites_K``."""
         self.model = model
         self.renderer = model._ensure_renderer()
         self.scene = model._ensure_scene()
@@ -110,7 +130,8 @@ class FusedPoseStep(_ChainStep):
         assert self.weight is None or self.weight.shape == self.ref.shape
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.near, self.far = near, far
-        self.pg = process_group
+        self.pg, self.defer_adam = process_group, bool(defer_adam)
+        self._before, self._after = (), ()
         self.distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(self.pg) > 1
         ex = choose_exchange(rccl, p2p, os.environ.get("EHR_COMM", ""), os.environ.get("EHR_TRY_RCCL"), self.distributed,
                              dist.get_backend(self.pg) if self.distributed else None)
@@ -156,9 +177,8 @@ class FusedPoseStep(_ChainStep):
         # one -- like the reference's load_model path.  The row of ``history_ops`` the next step records its pose in is a
         # counter of its own (the reference's first all-zero row, rb_solver.py:50-51): it starts at the model's history
         # cursor, so a solver built on a loaded checkpoint appends whatever the optimiser's step count is.
-        self.exp_avg = torch.zeros(6, device=dev)
-        self.exp_avg_sq = torch.zeros(6, device=dev)
-        self.step_t = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.pose_group = g = AdamGroup(6, dev, lr, weight_decay)   # (the parameter is the model's ``dof``)
+        self.exp_avg, self.exp_avg_sq, self.step_t, self.grad = g.exp_avg, g.exp_avg_sq, g.step_t, g.grad
         self.hist_row = torch.full((1,), int(model.history_cursor()), dtype=torch.int32, device=dev)
         # work buffers, allocated once
         self.mvp = torch.empty((self.B, self.L, 4, 4), device=dev)
@@ -166,8 +186,7 @@ class FusedPoseStep(_ChainStep):
         self.tc_jac = torch.empty((7, 16), device=dev)
         self.loss_b = torch.empty((self.B,), device=dev)
         self.red = torch.empty((8,), device=dev)
-        self.loss = torch.zeros((1,), device=dev)
-        self.grad = torch.zeros((6,), device=dev)
+        self.loss = torch.zeros((1,), device=dev) if loss is None else loss
         self.mask = torch.empty((self.B, self.H, self.W), device=dev)
         self._init_chain(slack)
 
@@ -251,6 +270,8 @@ class FusedPoseStep(_ChainStep):
         m, sc = self.model, self.scene
         dof = m.dof.data
         hist = m.history_ops
+        for part in self._before:
+            part.launch(self, stream)
         # one C call = 3 launches: [pose fwd + vertices + raster records] -> jobs, resolved by the waves that drew them
         # [-> general-triangle jobs, resolved likewise, once a step has needed them] -> composite [+ in its last workgroup:
         # accumulators + pose bwd (+ Adam)]
@@ -262,7 +283,7 @@ class FusedPoseStep(_ChainStep):
             _lib.ptr(self.hist_row), _f(self.lr), _f(self.betas[0]), _f(self.betas[1]), _f(self.eps), _f(self.wd), _lib.ptr(self.mvp),
             _lib.ptr(self.tc_jac), _lib.ptr(self.mask if want_mask else None), _lib.ptr(self.loss_b),
             _lib.ptr(self.grad_mvp), _lib.ptr(self.red), _lib.ptr(self.loss), _lib.ptr(self.grad),
-            int(self.distributed or self.rccl or self._stop_after_red), stream), "ehr_solver_step")
+            int(self.distributed or self.rccl or self.defer_adam), stream), "ehr_solver_step")
         if self.p2p:
             # the exchange and Adam in ONE launch: stores into the peers' mailboxes, a wait on the own one, sums in rank order
             _lib.check(lib.ehr_comm_p2p_step(self.glctx.handle, _lib.ptr(self.red), _lib.ptr(dof), _lib.ptr(self.exp_avg),
@@ -279,6 +300,12 @@ class FusedPoseStep(_ChainStep):
                                          _lib.ptr(self.step_t), _lib.ptr(self.red), _f(self.lr), _f(self.betas[0]),
                                          _f(self.betas[1]), _f(self.eps), _f(self.wd), _lib.ptr(self.loss),
                                          _lib.ptr(self.grad), stream), "ehr_pose_adam")
+        # the parts' finish launches.  The ORDER is a contract, stated and checked here once: every finish launch reads what
+        # the chain left as it was rendered, K included, so the one that rewrites K for the next step runs last.
+        if any(part.rewrites_K for part in self._after[:-1]):
+            raise RuntimeError("a finish launch that rewrites K must be the last one: the others read K as rendered")
+        for part in self._after:
+            part.launch(self, stream)
 
     def _host_copies_stale(self):
         self.model._hist_n = None  # the chain writes history_ops rows itself: the host cursor is stale from here on
@@ -294,21 +321,28 @@ class FusedPoseStep(_ChainStep):
     def steps_done(self):
         return int(self.step_t.item())
 
+    def _group0(self):
+        """The pose's ``param_groups`` entry, which every other group's is built from."""
+        return {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
+                "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                "decoupled_weight_decay": False, "params": [0]}
+
     def state_dict(self):
-        """torch.optim.Adam-shaped state for checkpoints (trainer/rbsolver.py:95-114)."""
-        return {"state": {0: {"step": self.step_t.float().cpu().reshape(()), "exp_avg": self.exp_avg.cpu().clone(),
-                              "exp_avg_sq": self.exp_avg_sq.cpu().clone()}},
-                "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd,
-                                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
-                                  "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                                  "params": [0]}]}
+        """torch.optim.Adam-shaped state for checkpoints (trainer/rbsolver.py:95-114): group 0 is the pose; every part
+        with a parameter group of its own adds it, with the parameters that no model holds."""
+        sd = {"state": {0: self.pose_group.state_entry()}, "param_groups": [self._group0()]}
+        for part in self._after:
+            part.add_state(self, sd)
+        return sd
 
     def load_state_dict(self, sd):
-        """Inverse of :meth:`state_dict`; also accepts a ``torch.optim.Adam.state_dict()`` of the same parameter."""
+        """Inverse of :meth:`state_dict`; also accepts a ``torch.optim.Adam.state_dict()`` of the same parameter.  A part
+        whose group the state does not hold keeps its own; one whose group was saved for another problem (another free set,
+        other settings) raises before anything is loaded."""
+        for part in self._after:
+            part.check_state(self, sd)
         st = sd.get("state", {})
-        if len(st) == 0:
-            return  # a fresh optimiser
-        st = st[sorted(st.keys())[0]]
-        self.exp_avg.copy_(torch.as_tensor(st["exp_avg"], dtype=torch.float32).reshape(6))
-        self.exp_avg_sq.copy_(torch.as_tensor(st["exp_avg_sq"], dtype=torch.float32).reshape(6))
-        self.step_t.fill_(int(round(float(torch.as_tensor(st["step"]).reshape(-1)[0]))))
+        if len(st):  # (none: a fresh optimiser)
+            self.pose_group.load_state(st[sorted(st.keys())[0]])
+        for part in self._after:
+            part.load_state(self, sd)

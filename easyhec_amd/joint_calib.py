@@ -20,10 +20,11 @@ from dataclasses import dataclass, field
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import _lib
-from .fast import FusedPoseStep, _f
+from .chain_step import check_solver_settings
+from .fast import POSE_LR, POSE_WEIGHT_DECAY, FusedPoseStep, _f, refuse_unsupported
+from .param_group import AdamGroup
 
 __all__ = ["JointPoseStep", "JointOffsetResult", "solve_joint_offsets", "joint_kinds", "default_free_joints"]
 
@@ -60,6 +61,78 @@ def _check_table(t, J):
             raise ValueError(f"joint offsets: table entry {k!r} has the wrong length")
 
 
+class _JointForward:
+    """The launch before the chain: qpos + offsets -> the step's ``link_poses`` and ``joint_frames``.  Holds what describes
+    the arm on the device (the joint table, the recorded joint vectors, the free mask) and the offsets' group, which a rig's
+    cameras share."""
+
+    def __init__(self, table, J, qp, free_joints, offsets, dev):
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=dt)).to(dev)
+        self.N, self.J, self.offsets, self.free_joints = int(table["parent"].shape[0]), J, offsets, free_joints
+        self.t = [up(table[k], dt) for k, dt in (("parent", np.int32), ("origin", np.float64), ("kind", np.int32),
+                                                 ("axis", np.float64), ("qidx", np.int32), ("use", np.int32))]
+        self.upstream = up(np.asarray(table["upstream"]).astype(np.uint32).view(np.int32), np.int32)
+        self.jkind = up(joint_kinds(table), np.int32)
+        mask = np.zeros(J, dtype=np.int32)
+        mask[free_joints] = 1
+        self.free = up(mask, np.int32)
+        self.qpos = up(qp, np.float64)
+
+    def launch(self, step, stream):
+        _lib.check(_lib.lib().ehr_joint_forward(
+            *[_lib.ptr(t) for t in self.t], self.N, self.J, step.L, _lib.ptr(self.qpos), _lib.ptr(self.offsets.param), step.B,
+            _lib.ptr(step.link_poses), _lib.ptr(step.joint_frames), stream), "ehr_joint_forward")
+
+
+class _JointFinish:
+    """The launch after the chain: grad_mvp -> d loss / d offsets -> Adam on the free joints; and the offsets' part of the
+    state dict: parameter group 1 and the offsets themselves, which no model holds."""
+    rewrites_K = False
+
+    def __init__(self, forward):
+        self.fw = forward
+
+    def launch(self, step, stream):
+        fw, g, (b1, b2) = self.fw, self.fw.offsets, step.betas
+        _lib.check(_lib.lib().ehr_joint_backward_adam(
+            _lib.ptr(step.grad_mvp), _lib.ptr(step.tc_jac), _lib.ptr(step.K), step.B, step.L, fw.J, step.H, step.W,
+            _f(step.near), _f(step.far), _lib.ptr(step.link_poses), _lib.ptr(step.joint_frames), _lib.ptr(fw.upstream),
+            _lib.ptr(fw.jkind), _lib.ptr(step.red), _lib.ptr(fw.free), _lib.ptr(g.param), _lib.ptr(g.exp_avg),
+            _lib.ptr(g.exp_avg_sq), _lib.ptr(g.step_t), _f(g.lr), _f(b1), _f(b2), _f(step.eps), _f(g.wd), _lib.ptr(g.grad),
+            stream), "ehr_joint_backward_adam")
+
+    def add_state(self, step, sd):
+        g = self.fw.offsets
+        sd["state"][1] = g.state_entry()
+        sd["param_groups"].append(g.param_group(sd["param_groups"][0], 1))
+        sd["joint_offsets"] = {"offsets": g.param.cpu().clone(), "free": list(self.fw.free_joints)}
+
+    def check_state(self, step, sd):
+        check_free_joints(sd.get("joint_offsets"), self.fw.free_joints, "step")
+        if len(sd.get("param_groups", [])) > 1:
+            self.fw.offsets.check_saved(sd["param_groups"][1], "the offsets' group", "step")
+
+    def load_state(self, step, sd):
+        """A pose-only state dict (``FusedPoseStep``'s) leaves the offsets' group as it is."""
+        self.fw.offsets.load_state(sd.get("state", {}).get(1), (sd.get("joint_offsets") or {}).get("offsets"))
+
+
+def check_free_joints(jo, free_joints, owner):
+    # the moments of a joint that was not free are zero and its offset was never fitted: a different mask would mix them
+    if jo is not None and sorted(int(j) for j in jo["free"]) != free_joints:
+        raise ValueError(f"load_state_dict: the state was saved with free joints {sorted(jo['free'])}, this {owner} has "
+                         f"{free_joints}")
+
+
+def offsets_group(robot, dev, init_offset, offset_lr, offset_weight_decay, kw):
+    """The offsets' Adam group, a fresh one: ``offset_lr`` / ``offset_weight_decay`` default to the pose's, which are among
+    ``FusedPoseStep``'s keywords ``kw`` or its defaults."""
+    J = int(robot.chain.dof)
+    return AdamGroup(J, dev, kw.get("lr", POSE_LR) if offset_lr is None else float(offset_lr),
+                     kw.get("weight_decay", POSE_WEIGHT_DECAY) if offset_weight_decay is None else float(offset_weight_decay),
+                     np.zeros(J, dtype=np.float32) if init_offset is None else np.asarray(init_offset, dtype=np.float32).reshape(J))
+
+
 class JointPoseStep(FusedPoseStep):
     def __init__(self, model, batch, robot, qpos=None, *, free=None, offset_lr=None, offset_weight_decay=None,
                  init_offset=None, **kw):
@@ -68,15 +141,17 @@ class JointPoseStep(FusedPoseStep):
         free: active-joint indices whose offsets are fitted (default :func:`default_free_joints`); offset_lr /
         offset_weight_decay: the offsets' Adam group (defaults: the pose's; the weight decay is the prior towards zero
         offsets); init_offset [J]: where the offsets start (default 0).  Everything else is ``FusedPoseStep``'s."""
-        if "starts" in kw:
-            # (nothing combines the two: MultiStartPoseStep has no hook for these kernels.  A call ported from
-            #  MultiStartPoseStep(model, batch, starts) gets the reason instead of a TypeError about a keyword.)
-            raise ValueError("joint offsets are not available for the multi-start step: its hypotheses share one link_poses")
-        pg = kw.get("process_group")
-        if kw.get("rccl") or kw.get("p2p") or (dist.is_available() and dist.is_initialized() and dist.get_world_size(pg) > 1):
-            raise ValueError("joint offsets are not available for a data-parallel job: the offset gradient is not exchanged")
-        if not _lib.has_joint_offsets():
-            raise RuntimeError("this libehr_hip.so has no joint-offset kernels (ehr_joint_forward): rebuild it")
+        refuse_unsupported(
+            kw, _lib.has_joint_offsets,
+            "joint offsets are not available for the multi-start step: its hypotheses share one link_poses",
+            "joint offsets are not available for a data-parallel job: the offset gradient is not exchanged",
+            "this libehr_hip.so has no joint-offset kernels (ehr_joint_forward): rebuild it")
+        g = offsets_group(robot, model.dof.device, init_offset, offset_lr, offset_weight_decay, kw)
+        self._init_joint(model, batch, robot, qpos, free, g, True, kw)
+
+    def _init_joint(self, model, batch, robot, qpos, free, offsets, finish, kw):
+        """offsets: the offsets' group -- this step's own, or the one a rig's cameras share; finish: whether the
+        step finishes with ``ehr_joint_backward_adam`` (a rig's camera does not: the rig's one finish launch follows)."""
         if qpos is None:
             if "qpos" not in batch:
                 raise ValueError("JointPoseStep needs the recorded joint vectors: pass qpos= or batch['qpos']")
@@ -88,7 +163,6 @@ class JointPoseStep(FusedPoseStep):
         q = np.atleast_2d(q)
         qp = np.zeros((q.shape[0], J))
         qp[:, :min(J, q.shape[1])] = q[:, :J]
-        off0 = np.zeros(J, dtype=np.float32) if init_offset is None else np.asarray(init_offset, dtype=np.float32).reshape(J)
         batch = dict(batch)
         # batch["link_poses"] is optional here and never rendered from: the forward kernel writes this object's own buffer
         # from qpos + offsets.  One that is given must be the kinematics of the recorded qpos (what the dataset computes) --
@@ -101,103 +175,33 @@ class JointPoseStep(FusedPoseStep):
                                  "joint vectors and the link poses must describe the same views")
         else:
             batch["link_poses"] = torch.from_numpy(fk0).float()
-        super().__init__(model, batch, **kw)
+        FusedPoseStep.__init__(self, model, batch, **kw)
         dev = self.dev
         if qp.shape[0] != self.B or len(table["use"]) != self.L:
             raise ValueError(f"JointPoseStep: qpos {qp.shape} / {len(table['use'])} rendered links do not match the batch's "
                              f"{self.B} views of {self.L} links")
-        self.robot, self.table, self.J, self.N = robot, table, J, int(table["parent"].shape[0])
+        self.robot, self.table, self.J = robot, table, J
         free = default_free_joints(table) if free is None else [int(j) for j in free]
         if any(j < 0 or j >= J for j in free):
             raise ValueError(f"free joints {free}: active joints are 0..{J - 1}")
         self.free_joints = sorted(set(free))
-        mask = np.zeros(J, dtype=np.int32)
-        mask[self.free_joints] = 1
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=dt)).to(dev)
-        self._t = {k: up(table[k], dt) for k, dt in (("parent", np.int32), ("origin", np.float64), ("kind", np.int32),
-                                                    ("axis", np.float64), ("qidx", np.int32), ("use", np.int32))}
-        self._upstream = up(np.asarray(table["upstream"]).astype(np.uint32).view(np.int32), np.int32)
-        self._jkind = up(joint_kinds(table), np.int32)
-        self._free = up(mask, np.int32)
-        self.qpos = up(qp, np.float64)
-        self.offset_lr = self.lr if offset_lr is None else float(offset_lr)
-        self.offset_wd = self.wd if offset_weight_decay is None else float(offset_weight_decay)
-        # the second Adam parameter group: a fresh one unless load_state_dict restores it
-        self.offsets = up(off0, np.float32)
-        self.offset_exp_avg = torch.zeros(J, device=dev)
-        self.offset_exp_avg_sq = torch.zeros(J, device=dev)
-        self.offset_step_t = torch.zeros((1,), dtype=torch.int32, device=dev)
-        self.offset_grad = torch.zeros(J, device=dev)
+        self.offsets_group = g = offsets
+        self.offset_lr, self.offset_wd = g.lr, g.wd
+        self.offsets, self.offset_grad = g.param, g.grad
+        self.offset_exp_avg, self.offset_exp_avg_sq, self.offset_step_t = g.exp_avg, g.exp_avg_sq, g.step_t
+        self.kinematics = fw = _JointForward(table, J, qp, self.free_joints, g, dev)
+        self._before, self._after = (fw,), ((_JointFinish(fw),) if finish else ())
         # the buffer the forward kernel writes and the chain reads: this object's own, never the caller's tensor
         self.link_poses = torch.empty((self.B, self.L, 4, 4), device=dev)
         self.joint_frames = torch.empty((self.B, J, 6), device=dev)
-        with torch.cuda.device(dev):
-            self._launch_forward(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        self.corrected_link_poses()  # (the first forward launch: ``link_poses`` hold the kinematics before any step)
 
-    # -- launches ---------------------------------------------------------------------------------------------------
-    def _launch_forward(self, stream):
-        t = self._t
-        _lib.check(_lib.lib().ehr_joint_forward(
-            _lib.ptr(t["parent"]), _lib.ptr(t["origin"]), _lib.ptr(t["kind"]), _lib.ptr(t["axis"]), _lib.ptr(t["qidx"]),
-            _lib.ptr(t["use"]), self.N, self.J, self.L, _lib.ptr(self.qpos), _lib.ptr(self.offsets), self.B,
-            _lib.ptr(self.link_poses), _lib.ptr(self.joint_frames), stream), "ehr_joint_forward")
-
-    def _enqueue(self, want_mask, stream=None):
-        if stream is None:
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self._launch_forward(stream)
-        super()._enqueue(want_mask, stream=stream)
-        b1, b2 = self.betas
-        _lib.check(_lib.lib().ehr_joint_backward_adam(
-            _lib.ptr(self.grad_mvp), _lib.ptr(self.tc_jac), _lib.ptr(self.K), self.B, self.L, self.J, self.H, self.W,
-            _f(self.near), _f(self.far), _lib.ptr(self.link_poses), _lib.ptr(self.joint_frames), _lib.ptr(self._upstream),
-            _lib.ptr(self._jkind), _lib.ptr(self.red), _lib.ptr(self._free), _lib.ptr(self.offsets),
-            _lib.ptr(self.offset_exp_avg), _lib.ptr(self.offset_exp_avg_sq), _lib.ptr(self.offset_step_t),
-            _f(self.offset_lr), _f(b1), _f(b2), _f(self.eps), _f(self.offset_wd), _lib.ptr(self.offset_grad), stream),
-            "ehr_joint_backward_adam")
-
-    # -- results ----------------------------------------------------------------------------------------------------
     def corrected_link_poses(self):
         """[B,L,4,4] float32 (device, a copy): the link poses at the CURRENT offsets, for what comes after the solve (the
         space explorer, tools/validate.py)."""
         with torch.cuda.device(self.dev):
-            self._launch_forward(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            self.kinematics.launch(self, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         return self.link_poses.clone()
-
-    def state_dict(self):
-        """``FusedPoseStep.state_dict`` with a second parameter group (index 1: the offsets' Adam state) and the offsets
-        themselves, which no model holds."""
-        sd = super().state_dict()
-        sd["state"][1] = {"step": self.offset_step_t.float().cpu().reshape(()), "exp_avg": self.offset_exp_avg.cpu().clone(),
-                          "exp_avg_sq": self.offset_exp_avg_sq.cpu().clone()}
-        g = dict(sd["param_groups"][0])
-        g.update(lr=self.offset_lr, weight_decay=self.offset_wd, params=[1])
-        sd["param_groups"].append(g)
-        sd["joint_offsets"] = {"offsets": self.offsets.cpu().clone(), "free": list(self.free_joints)}
-        return sd
-
-    def load_state_dict(self, sd):
-        """Inverse of :meth:`state_dict`; a pose-only state dict (``FusedPoseStep``'s) restores the pose's group and leaves
-        the offsets' as it is."""
-        jo = sd.get("joint_offsets")
-        if jo is not None and sorted(int(j) for j in jo["free"]) != self.free_joints:
-            # the moments of a joint that was not free are zero and its offset was never fitted: a different mask would mix them
-            raise ValueError(f"load_state_dict: the state was saved with free joints {sorted(jo['free'])}, this step has "
-                             f"{self.free_joints}")
-        groups = sd.get("param_groups", [])
-        if len(groups) > 1:
-            g = groups[1]
-            if float(g.get("lr", self.offset_lr)) != self.offset_lr or float(g.get("weight_decay", self.offset_wd)) != self.offset_wd:
-                raise ValueError(f"load_state_dict: the offsets' group was saved with lr {g.get('lr')} / weight decay "
-                                 f"{g.get('weight_decay')}, this step has {self.offset_lr} / {self.offset_wd}")
-        super().load_state_dict(sd)
-        st = sd.get("state", {}).get(1)
-        if st is not None:
-            self.offset_exp_avg.copy_(torch.as_tensor(st["exp_avg"], dtype=torch.float32).reshape(self.J))
-            self.offset_exp_avg_sq.copy_(torch.as_tensor(st["exp_avg_sq"], dtype=torch.float32).reshape(self.J))
-            self.offset_step_t.fill_(int(round(float(torch.as_tensor(st["step"]).reshape(-1)[0]))))
-        if jo is not None:
-            self.offsets.copy_(torch.as_tensor(jo["offsets"], dtype=torch.float32).reshape(self.J))
 
 
 @dataclass
@@ -209,29 +213,13 @@ class JointOffsetResult:
     step: object = None         # the JointPoseStep (corrected_link_poses(), state_dict())
 
 
-def _check_solver_settings(cfg, kw):
-    """The solver-settings check of the one-call solves (this one and ``rig_calib.solve_rig``); fills in ``cfg.solver``'s lr
-    and weight decay where ``kw`` has none."""
-    if cfg.solver.do_grad_clip or cfg.solver.optimizer != "Adam":
-        raise ValueError("the launch chain implements the reference's default solver only (Adam, no gradient clipping)")
-    kw.setdefault("lr", cfg.solver.max_lr)
-    kw.setdefault("weight_decay", cfg.solver.weight_decay)
-
-
 def solve_joint_offsets(cfg, model, batch, robot, num_steps, qpos=None, capture=True, **kw):
     """``num_steps`` EFFECTIVE steps of the joint solve with the optimiser settings of ``cfg.solver`` (Adam: lr, weight
     decay), from a captured graph, with the loop ``RBSolverTrainer.fit`` uses: a reported step is recovered from and taken
     again.  ``kw``: :class:`JointPoseStep`'s keywords."""
-    _check_solver_settings(cfg, kw)
-    js = JointPoseStep(model, batch, robot, qpos, **kw)
+    js = JointPoseStep(model, batch, robot, qpos, **{**check_solver_settings(cfg), **kw})
     if capture:
         js.capture()
-    kept = []
-    for remaining, _ in js.effective_rounds(num_steps, "solve_joint_offsets"):
-        for _ in range(remaining):  # (a reported step's loss is NaN and is dropped below: num_steps finite ones remain)
-            kept.append(js.step().clone())
-    torch.cuda.synchronize(js.dev)
-    losses = torch.cat(kept).cpu() if kept else torch.zeros(0)
-    losses = losses[~torch.isnan(losses)][:num_steps]
+    losses = js.take_effective_steps(num_steps, "solve_joint_offsets")[:num_steps, 0]
     js.release_graph()
     return JointOffsetResult(js.offsets.cpu().clone(), losses, model.dof.detach().cpu().clone(), list(js.recoveries), js)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .chain_step import _ChainStep
+from .chain_step import _ChainStep, check_solver_settings
 from .fast import _f, _private_weight
 from .se3 import se3_log_map
 from .synthetic import perturb_pose
@@ -167,18 +167,9 @@ def solve_multistart(cfg, model, batch, starts, num_steps, tail=20, slack=None):
     ``RBSolverTrainer.fit`` uses (a reported step is recovered from and run again), ranks the hypotheses by the mean of their
     last ``tail`` losses and writes the winner's pose into ``model.dof`` and its rows into ``model.history_ops`` -- so
     SpaceExplorer and checkpoints see an ordinary solve."""
-    if cfg.solver.do_grad_clip or cfg.solver.optimizer != "Adam":
-        raise ValueError("the launch chain implements the reference's default solver only (Adam, no gradient clipping)")
-    ms = MultiStartPoseStep(model, batch, starts, lr=cfg.solver.max_lr, weight_decay=cfg.solver.weight_decay, slack=slack)
+    ms = MultiStartPoseStep(model, batch, starts, slack=slack, **check_solver_settings(cfg))
     ms.capture()
-    logs = []
-    for remaining, _ in ms.effective_rounds(num_steps, "solve_multistart"):
-        log = torch.empty((remaining, ms.P), device=ms.dev)
-        for it in range(remaining):
-            log[it].copy_(ms.step())
-        logs.append(log)
-    hist = torch.cat(logs).cpu()
-    hist = hist[~torch.isnan(hist).all(dim=1)]  # (reported steps: NaN for every hypothesis, taken by none)
+    hist = ms.take_effective_steps(num_steps, "solve_multistart")
     means = hist[-tail:].double().mean(dim=0) if hist.shape[0] > 0 else torch.full((ms.P,), float("nan"), dtype=torch.float64)
     ranking = rank_losses(means.numpy())
     w = ranking[0]

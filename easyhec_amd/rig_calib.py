@@ -22,12 +22,11 @@ import ctypes
 from dataclasses import dataclass, field
 
 import torch
-import torch.distributed as dist
 
 from . import _lib, fused
-from .chain_step import _ReportedStepProtocol
-from .fast import FusedPoseStep, _f
-from .joint_calib import JointPoseStep, _check_solver_settings
+from .chain_step import _ReportedStepProtocol, check_solver_settings
+from .fast import _f, refuse_unsupported
+from .joint_calib import JointPoseStep, check_free_joints, offsets_group
 
 __all__ = ["RigJointStep", "RigResult", "solve_rig"]
 
@@ -36,14 +35,11 @@ MAX_CAMERAS = 16  # EHR_RIG_MAX_CAMERAS
 
 class _RigCameraStep(JointPoseStep):
     """One camera of the rig: ``JointPoseStep``'s construction (the table and the qpos / link_poses checks, the forward
-    kernel's buffers) with a chain that stops after ``red`` and no finish launch of its own."""
-    _stop_after_red = True
+    launch) around the rig's ONE offsets' group, with the camera's element of the rig's ``loss``, a chain that stops after
+    ``red`` and no finish launch of its own."""
 
-    def _enqueue(self, want_mask, stream=None):
-        if stream is None:
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self._launch_forward(stream)
-        FusedPoseStep._enqueue(self, want_mask, stream=stream)
+    def __init__(self, model, batch, robot, qpos, free, offsets, loss, **kw):
+        self._init_joint(model, batch, robot, qpos, free, offsets, False, dict(kw, loss=loss, defer_adam=True))
 
 
 def _per_camera(v, C, name):
@@ -64,15 +60,13 @@ class RigJointStep(_ReportedStepProtocol):
         cameras; ``slack``, ``near`` and ``far`` may be a list with one entry per camera."""
         models, batches = list(models), list(batches)
         C = len(models)
-        if "starts" in kw:
-            raise ValueError("a camera rig is not available for the multi-start step: its hypotheses share one link_poses, "
-                             "and the search over a rig is out of scope")
-        pg = kw.get("process_group")
-        if kw.get("rccl") or kw.get("p2p") or (dist.is_available() and dist.is_initialized() and dist.get_world_size(pg) > 1):
-            raise ValueError("a camera rig is not available for a data-parallel job: the cameras' sums are joined on one "
-                             "device, and the offset gradient is not exchanged")
-        if not _lib.has_rig():
-            raise RuntimeError("this libehr_hip.so has no rig kernel (ehr_rig_backward_adam): rebuild it")
+        refuse_unsupported(
+            kw, _lib.has_rig,
+            "a camera rig is not available for the multi-start step: its hypotheses share one link_poses, and the search "
+            "over a rig is out of scope",
+            "a camera rig is not available for a data-parallel job: the cameras' sums are joined on one device, and the "
+            "offset gradient is not exchanged",
+            "this libehr_hip.so has no rig kernel (ehr_rig_backward_adam): rebuild it")
         if not 1 <= C <= MAX_CAMERAS or len(batches) != C:
             raise ValueError(f"RigJointStep: {C} models / {len(batches)} batches; a rig has 1..{MAX_CAMERAS} cameras and one "
                              "batch per camera")
@@ -85,30 +79,20 @@ class RigJointStep(_ReportedStepProtocol):
         if len(qpos) != C:
             raise ValueError(f"RigJointStep: qpos= has {len(qpos)} entries for {C} cameras")
         per = {k: _per_camera(kw.pop(k), C, k) for k in ("slack", "near", "far") if k in kw}
-        self.cameras = []
-        for c in range(C):
-            kc = dict(kw, **{k: v[c] for k, v in per.items()})
-            self.cameras.append(_RigCameraStep(models[c], batches[c], robot, qpos[c], free=free, offset_lr=offset_lr,
-                                               offset_weight_decay=offset_weight_decay, init_offset=init_offset, **kc))
+        self.C, self.dev, self.robot = C, models[0].dof.device, robot
+        # the ONE offsets' group, which every camera's forward launch reads and the rig's finish launch updates, and the
+        # ``loss [C]`` the finish launch writes camera by camera: both handed to the cameras' constructors
+        self.offsets_group = g = offsets_group(robot, self.dev, init_offset, offset_lr, offset_weight_decay, kw)
+        self.offsets, self.offset_grad, self.offset_lr, self.offset_wd = g.param, g.grad, g.lr, g.wd
+        self.offset_exp_avg, self.offset_exp_avg_sq, self.offset_step_t = g.exp_avg, g.exp_avg_sq, g.step_t
+        self.loss = torch.zeros((C,), device=self.dev)
+        self.cameras = [_RigCameraStep(models[c], batches[c], robot, qpos[c], free, g, self.loss[c:c + 1],
+                                       **dict(kw, **{k: v[c] for k, v in per.items()})) for c in range(C)]
         first = self.cameras[0]
         if any(cam.L != first.L for cam in self.cameras):
             raise ValueError(f"RigJointStep: the cameras render {[cam.L for cam in self.cameras]} links: one robot, one link count")
-        self.C, self.L, self.J, self.dev, self.robot = C, first.L, first.J, first.dev, robot
-        self.free_joints = list(first.free_joints)
+        self.L, self.J, self.free_joints, self.kinematics = first.L, first.J, list(first.free_joints), first.kinematics
         self.lr, self.wd, self.betas, self.eps = first.lr, first.wd, first.betas, first.eps
-        self.offset_lr, self.offset_wd = first.offset_lr, first.offset_wd
-        # the ONE offsets' group: the first camera's tensors, which every camera's forward launch reads.  Every camera has
-        # allocated a group (and a ``loss``) of its own in its constructor; they are replaced HERE, before the first step.
-        # That relies on JointPoseStep / FusedPoseStep looking these attributes up at every launch (``_launch_forward``,
-        # ``_enqueue``) and never keeping a tensor or a pointer of them from construction: keep it so, or pass them in.
-        self.offsets, self.offset_exp_avg, self.offset_exp_avg_sq = first.offsets, first.offset_exp_avg, first.offset_exp_avg_sq
-        self.offset_step_t, self.offset_grad = first.offset_step_t, first.offset_grad
-        self.loss = torch.zeros((C,), device=self.dev)
-        for c, cam in enumerate(self.cameras):
-            cam.offsets, cam.offset_exp_avg, cam.offset_exp_avg_sq = self.offsets, self.offset_exp_avg, self.offset_exp_avg_sq
-            cam.offset_step_t, cam.offset_grad = self.offset_step_t, self.offset_grad
-            cam.loss = self.loss[c:c + 1]
-        self._upstream, self._jkind, self._free = first._upstream, first._jkind, first._free
         self._cams_dev, self._cams_key = None, None
         # the protocol around a reported step is _ChainStep's own (chain_step._ReportedStepProtocol): a non-blocking look at
         # ``loss [C]`` every `check_every` steps; ``recoveries`` holds "camera c: what its context recovered from", in order
@@ -139,12 +123,11 @@ class RigJointStep(_ReportedStepProtocol):
                 if getattr(cam.glctx, "_bound_weight", None) is not cam.weight:
                     cam._plan_and_bind()  # somebody else used the context with other weights since: bind this camera's again
                 cam._enqueue(False, stream=stream)
-            b1, b2 = self.betas
+            (b1, b2), fw, g = self.betas, self.kinematics, self.offsets_group
             _lib.check(_lib.lib().ehr_rig_backward_adam(
-                _lib.ptr(cams), self.C, self.L, self.J, _lib.ptr(self._upstream), _lib.ptr(self._jkind), _lib.ptr(self._free),
-                _lib.ptr(self.offsets), _lib.ptr(self.offset_exp_avg), _lib.ptr(self.offset_exp_avg_sq),
-                _lib.ptr(self.offset_step_t), _f(self.lr), _f(self.offset_lr), _f(b1), _f(b2), _f(self.eps), _f(self.wd),
-                _f(self.offset_wd), _lib.ptr(self.offset_grad), stream), "ehr_rig_backward_adam")
+                _lib.ptr(cams), self.C, self.L, self.J, _lib.ptr(fw.upstream), _lib.ptr(fw.jkind), _lib.ptr(fw.free),
+                _lib.ptr(g.param), _lib.ptr(g.exp_avg), _lib.ptr(g.exp_avg_sq), _lib.ptr(g.step_t), _f(self.lr), _f(g.lr),
+                _f(b1), _f(b2), _f(self.eps), _f(self.wd), _f(g.wd), _lib.ptr(g.grad), stream), "ehr_rig_backward_adam")
             self._calls += 1
             if self._calls % self.check_every == 0:
                 self._poll()
@@ -182,15 +165,10 @@ class RigJointStep(_ReportedStepProtocol):
     def state_dict(self):
         """torch.optim.Adam-shaped: parameter groups 0..C-1 are the cameras' poses, group C the offsets; plus the offsets
         themselves, which no model holds."""
-        state, groups = {}, []
-        for c, cam in enumerate(self.cameras):
-            sd = FusedPoseStep.state_dict(cam)
-            state[c] = sd["state"][0]
-            groups.append(dict(sd["param_groups"][0], params=[c]))
-        state[self.C] = {"step": self.offset_step_t.float().cpu().reshape(()), "exp_avg": self.offset_exp_avg.cpu().clone(),
-                         "exp_avg_sq": self.offset_exp_avg_sq.cpu().clone()}
-        groups.append(dict(groups[0], lr=self.offset_lr, weight_decay=self.offset_wd, params=[self.C]))
-        return {"state": state, "param_groups": groups,
+        every = [cam.pose_group for cam in self.cameras] + [self.offsets_group]
+        group0 = self.cameras[0]._group0()
+        return {"state": {i: g.state_entry() for i, g in enumerate(every)},
+                "param_groups": [g.param_group(group0, i) for i, g in enumerate(every)],
                 "joint_offsets": {"offsets": self.offsets.cpu().clone(), "free": list(self.free_joints), "cameras": self.C}}
 
     def load_state_dict(self, sd):
@@ -199,21 +177,12 @@ class RigJointStep(_ReportedStepProtocol):
         jo, groups = sd.get("joint_offsets"), sd.get("param_groups", [])
         if jo is None or int(jo.get("cameras", -1)) != self.C or len(groups) != self.C + 1:
             raise ValueError(f"load_state_dict: the state is not a rig's of {self.C} cameras (it has {len(groups)} parameter groups)")
-        if sorted(int(j) for j in jo["free"]) != self.free_joints:
-            raise ValueError(f"load_state_dict: the state was saved with free joints {sorted(jo['free'])}, this rig has "
-                             f"{self.free_joints}")
-        for c, g in enumerate(groups):
-            lr, wd = (self.lr, self.wd) if c < self.C else (self.offset_lr, self.offset_wd)
-            if float(g.get("lr", lr)) != lr or float(g.get("weight_decay", wd)) != wd:
-                raise ValueError(f"load_state_dict: group {c} was saved with lr {g.get('lr')} / weight decay "
-                                 f"{g.get('weight_decay')}, this rig has {lr} / {wd}")
-        for c, cam in enumerate(self.cameras):
-            FusedPoseStep.load_state_dict(cam, {"state": {0: sd["state"][c]}})
-        st = sd["state"][self.C]
-        self.offset_exp_avg.copy_(torch.as_tensor(st["exp_avg"], dtype=torch.float32).reshape(self.J))
-        self.offset_exp_avg_sq.copy_(torch.as_tensor(st["exp_avg_sq"], dtype=torch.float32).reshape(self.J))
-        self.offset_step_t.fill_(int(round(float(torch.as_tensor(st["step"]).reshape(-1)[0]))))
-        self.offsets.copy_(torch.as_tensor(jo["offsets"], dtype=torch.float32).reshape(self.J))
+        check_free_joints(jo, self.free_joints, "rig")
+        every = [cam.pose_group for cam in self.cameras] + [self.offsets_group]
+        for i, g in enumerate(every):
+            g.check_saved(groups[i], f"group {i}", "rig")
+        for i, g in enumerate(every):
+            g.load_state(sd["state"][i], jo["offsets"] if g is self.offsets_group else None)
 
 
 @dataclass
@@ -228,14 +197,7 @@ class RigResult:
 def solve_rig(cfg, models, batches, robot, num_steps, qpos=None, **kw):
     """``num_steps`` EFFECTIVE steps of the rig solve with the optimiser settings of ``cfg.solver`` (Adam: lr, weight
     decay): a reported step is recovered from and taken again.  ``kw``: :class:`RigJointStep`'s keywords."""
-    _check_solver_settings(cfg, kw)
-    rig = RigJointStep(models, batches, robot, qpos, **kw)
-    kept = []
-    for remaining, _ in rig.effective_rounds(num_steps, "solve_rig"):
-        for _ in range(remaining):  # (a reported step's losses are NaN and are dropped below: num_steps finite rows remain)
-            kept.append(rig.step().clone())
-    torch.cuda.synchronize(rig.dev)
-    losses = torch.stack(kept).cpu() if kept else torch.zeros((0, rig.C))
-    losses = losses[~torch.isnan(losses).all(dim=1)][:num_steps]
+    rig = RigJointStep(models, batches, robot, qpos, **{**check_solver_settings(cfg), **kw})
+    losses = rig.take_effective_steps(num_steps, "solve_rig")[:num_steps]
     dofs = torch.stack([cam.model.dof.detach().cpu().clone() for cam in rig.cameras])
     return RigResult(rig.offsets.cpu().clone(), losses, dofs, list(rig.recoveries), rig)

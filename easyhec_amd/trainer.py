@@ -64,11 +64,10 @@ class RBSolverTrainer:
         if graph and not fast:
             self._capture_autograd_step()
         if fast:
+            from .chain_step import check_solver_settings
             from .fast import FusedPoseStep
-            if cfg.solver.do_grad_clip or cfg.solver.optimizer != "Adam":
-                raise ValueError("fast path implements the reference's default solver only (Adam, no gradient clipping)")
-            self.fast = FusedPoseStep(model, self.batch, lr=cfg.solver.max_lr, weight_decay=cfg.solver.weight_decay,
-                                      process_group=process_group, rccl=rccl)
+            self.fast = FusedPoseStep(model, self.batch, process_group=process_group, rccl=rccl,
+                                      **check_solver_settings(cfg, "fast path"))
             if graph and (not self.distributed or self.fast.rccl):
                 self.fast.capture()
         if "Tc_c2b" in self.batch and "gt_dof6" not in self.batch:

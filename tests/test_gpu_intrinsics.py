@@ -702,7 +702,7 @@ def test_composition_with_joint_offsets(xarm7):
     c0 = JointIntrinsicsPoseStep(m0, batch, xarm7, qp, free=[], free_intrinsics=())
     js = JointPoseStep(mj, batch, xarm7, qp)
     c1 = JointIntrinsicsPoseStep(m1, batch, xarm7, qp, free_intrinsics=())
-    assert c0._intr_group == 2 and set(c1.state_dict()["state"]) == {0, 1, 2}
+    assert c0.state_dict()["intrinsics"]["group"] == 2 and set(c1.state_dict()["state"]) == {0, 1, 2}
     for it in range(30):
         fs.step(), c0.step(), js.step(), c1.step()
         torch.cuda.synchronize()
@@ -731,8 +731,8 @@ def test_composition_with_joint_offsets(xarm7):
         b1, b2 = c2.betas
         _lib.check(_lib.lib().ehr_joint_backward_adam(
             _lib.ptr(c2.grad_mvp), _lib.ptr(c2.tc_jac), _lib.ptr(K), c2.B, c2.L, c2.J, c2.H, c2.W, _f(c2.near), _f(c2.far),
-            _lib.ptr(c2.link_poses), _lib.ptr(c2.joint_frames), _lib.ptr(c2._upstream), _lib.ptr(c2._jkind), _lib.ptr(c2.red),
-            _lib.ptr(c2._free), _lib.ptr(off), _lib.ptr(m), _lib.ptr(v), _lib.ptr(t), _f(c2.offset_lr), _f(b1), _f(b2),
+            _lib.ptr(c2.link_poses), _lib.ptr(c2.joint_frames), _lib.ptr(c2.kinematics.upstream), _lib.ptr(c2.kinematics.jkind), _lib.ptr(c2.red),
+            _lib.ptr(c2.kinematics.free), _lib.ptr(off), _lib.ptr(m), _lib.ptr(v), _lib.ptr(t), _f(c2.offset_lr), _f(b1), _f(b2),
             _f(c2.eps), _f(c2.offset_wd), _lib.ptr(grad), _stream()), "ehr_joint_backward_adam")
         torch.cuda.synchronize()
         return grad, off
