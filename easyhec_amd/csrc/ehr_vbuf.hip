@@ -65,7 +65,8 @@ constexpr int VB_HEAVY_T_DEFAULT = 3000;  // cost (4-pixel units walked + 256 pe
                                           // ones for 25
 constexpr int VB_HEAVY_CAP = 4096;    // heavy jobs remembered per step
 constexpr int VB_MED_CAP = 2048;      // long single-wave jobs remembered per step (they are started first)
-constexpr int VB_MED_T_DEFAULT = 1500;    // cost from which a single-wave job counts as long
+constexpr int VB_MED_T_DEFAULT = 1250;    // cost from which a single-wave job counts as long (1500 until the box trim took a
+                                          // third off the long jobs' costs; 1000 starts too many together: profiles/box_trim.md)
 // Issue priority (s_setprio) of the waves on the jobs the kernel ends on: a long job started first runs beside three
 // siblings per SIMD for most of its life (41 us instead of 30); with priority 48.5 instead of 50.0 us at 8 views.
 constexpr int VB_PRIO_LONG = 3;
@@ -707,6 +708,25 @@ __device__ __forceinline__ int vb_scan_max(int v) {  // inclusive maximum of val
 __device__ __forceinline__ int vb_div_small(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
 // the next set bit of m above position j (there is one)
 __device__ __forceinline__ int vb_next_set(u64 m, int j) { return j + __ffsll((unsigned long long)(m >> (j + 1))); }
+// The steps j of [0, n) at which all three m[k] + j s[k] can be >= 0, as a range [lo, hi] (lo > hi: none).  m[k] is the
+// edge's largest value across the box's other axis, so a step outside the range holds no covered pixel.  The values are
+// integers: m + j s >= 0 is m + 0.5 + j s > 0, a bound -(m + 0.5) / s that is never an integer and never 0 / 0 (s = 0: the
+// quotient is an infinity of the right sign).  The float quotient is within 1e-5 of the true one wherever it lies inside
+// the box (|j| <= 34), and is pushed outwards by 1/256 before it is rounded: the range is never too small, and one step
+// too large only where a bound comes that close to an integer.
+__device__ __forceinline__ void vb_trim_range(const int m[3], const int s[3], int n, int& lo, int& hi) {
+    float fl = 0.f, fh = (float)(n - 1);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float t = -((float)m[k] + 0.5f) * __builtin_amdgcn_rcpf((float)s[k]);
+        if (s[k] >= 0)
+            fl = fmaxf(fl, t);  // rising along the axis: a lower bound
+        else
+            fh = fminf(fh, t);
+    }
+    lo = (int)ceilf(fminf(fl, 64.f) - 0x1p-8f);
+    hi = (int)floorf(fmaxf(fh, -1.f) + 0x1p-8f);
+}
 
 struct VbRegion {
     int x0, y0, x1, y1;  // pixels of the region inside the image (inclusive); region origin = (rx0, ry0) below
@@ -991,7 +1011,9 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
     if (sv) {
         if (r1.w == 1) {
             wide = true;
-        } else {
+        } else if (LAZY) {
+            // (the lazy instantiation has no register to spare while the records are live: it stages the clamped box as it
+            // is and trims it from the staged values, below)
             const int ix0 = bx.x & 0xffffu, iy0 = bx.x >> 16, ix1 = bx.y & 0xffffu, iy1 = bx.y >> 16;
             const int cx0 = max(ix0, rg.x0), cy0 = max(iy0, rg.y0);
             const int bw = min(ix1, rg.x1) - cx0 + 1, bh = min(iy1, rg.y1) - cy0 + 1;  // > 0: the boxes overlap
@@ -1006,9 +1028,48 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
             }
             R.box[lane] = (unsigned)(cx0 - rx0) | ((unsigned)(cy0 - ry0) << 8) | ((unsigned)bw << 16) | ((unsigned)bh << 24);
             R.ent[lane] = (srel << 14) | ((r1.w == 2) ? (1u << 13) : 0u);
+        } else {
+            R.ent[lane] = (srel << 14) | ((r1.w == 2) ? (1u << 13) : 0u);
+            const int ix0 = bx.x & 0xffffu, iy0 = bx.x >> 16, ix1 = bx.y & 0xffffu, iy1 = bx.y >> 16;
+            int cx0 = max(ix0, rg.x0), cy0 = max(iy0, rg.y0);
+            int bw = min(ix1, rg.x1) - cx0 + 1, bh = min(iy1, rg.y1) - cy0 + 1;  // > 0: the boxes overlap
+            const unsigned w[3] = {(unsigned)r0.w, (unsigned)r1.x, (unsigned)r1.y};
+            const int ev[3] = {r0.x, r0.y, r0.z};
+            const int ox = cx0 - ix0, oy = cy0 - iy0;
+            int e[3], sx[3], sy[3], m[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                sx[k] = -16 * (int)(short)(w[k] >> 16);
+                sy[k] = 16 * (int)(short)(w[k] & 0xffffu);
+                e[k] = ev[k] + __mul24(sx[k], ox) + __mul24(sy[k], oy);  // (24-bit operands: full-rate multiplies)
+                R.dxy[lane][k] = w[k];
+            }
+            // Box trim: the clamped box is often a corner of the triangle's own box which the triangle barely reaches, or
+            // misses (a quarter of the triangles that get here cover no pixel of the region, two thirds of the units hold no
+            // covered pixel).  Cut it down to the rows, then to the columns of those rows, on which all three edges can
+            // still be >= 0 (m[k]: edge k's largest value across the other axis), and move the edge values to its new
+            // first pixel.  The walkers test the same integers on fewer pixels, none of them covered: same bits.
+            int t0, t1;
+#pragma unroll
+            for (int k = 0; k < 3; k++) m[k] = e[k] + max(0, __mul24(sx[k], bw - 1));
+            vb_trim_range(m, sy, bh, t0, t1);
+            cy0 += t0;
+            bh = t1 - t0 + 1;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                e[k] += __mul24(sy[k], t0);
+                m[k] = e[k] + max(0, __mul24(sy[k], bh - 1));
+            }
+            vb_trim_range(m, sx, bw, t0, t1);
+            cx0 += t0;
+            bw = t1 - t0 + 1;
+            const bool empty = bh <= 0 || bw <= 0;  // the triangle misses the region: as good as hidden
+#pragma unroll
+            for (int k = 0; k < 3; k++) R.e[lane][k] = e[k] + __mul24(sx[k], t0);
+            R.box[lane] = (unsigned)(cx0 - rx0) | ((unsigned)(cy0 - ry0) << 8) | ((unsigned)bw << 16) | ((unsigned)bh << 24);
             const u64 bm = ((1ull << bw) - 1ull) << (cx0 - rx0);
-            bool hidden = has_in;
-            if (has_in) {
+            bool hidden = has_in || empty;
+            if (has_in && !empty) {
                 // rows y0 .. y0 + bh - 1 = the 2^k rows from y0 and the 2^k rows up to the last, k = floor(log2(bh))
                 const int y0r = cy0 - ry0, k = 31 - __clz(bh);
                 const u64* const tab = (k == 0) ? S.intr : S.intr_and[k - 1];
@@ -1025,6 +1086,52 @@ __device__ __forceinline__ int vb_raster_round(bool sv, size_t slot, unsigned sr
         }
     }
     if ((!WIDE || COVER) && __ballot(wide)) return -1;  // the lean instantiation hands the whole job to vb_job_slow
+    if (LAZY && sv && !wide) {
+        // the box trim of the eager form above, on the staged values: the records' registers are dead here (this way round
+        // the lazy instantiation spills 21 VGPRs, the other way round 33; the eager one 6 against 8)
+        const unsigned b4 = R.box[lane];
+        int x0r = b4 & 255, y0r = (b4 >> 8) & 255, bw = (b4 >> 16) & 255, bh = b4 >> 24;
+        int e[3], sx[3], sy[3], m[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const unsigned w = R.dxy[lane][k];
+            sx[k] = -16 * (int)(short)(w >> 16);
+            sy[k] = 16 * (int)(short)(w & 0xffffu);
+            e[k] = R.e[lane][k];
+            m[k] = e[k] + max(0, __mul24(sx[k], bw - 1));
+        }
+        int t0, t1;
+        vb_trim_range(m, sy, bh, t0, t1);
+        y0r += t0;
+        bh = t1 - t0 + 1;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            e[k] += __mul24(sy[k], t0);
+            m[k] = e[k] + max(0, __mul24(sy[k], bh - 1));
+        }
+        vb_trim_range(m, sx, bw, t0, t1);
+        x0r += t0;
+        bw = t1 - t0 + 1;
+#pragma unroll
+        for (int k = 0; k < 3; k++) R.e[lane][k] = e[k] + __mul24(sx[k], t0);
+        R.box[lane] = (unsigned)x0r | ((unsigned)y0r << 8) | ((unsigned)bw << 16) | ((unsigned)bh << 24);
+        bool hidden = bh <= 0 || bw <= 0;  // the triangle misses the region: as good as hidden
+        if (has_in && !hidden) {
+            // rows y0 .. y0 + bh - 1 = the 2^k rows from y0 and the 2^k rows up to the last, k = floor(log2(bh))
+            const u64 bm = ((1ull << bw) - 1ull) << x0r;
+            const int k = 31 - __clz(bh);
+            const u64* const tab = (k == 0) ? S.intr : S.intr_and[k - 1];
+            const u64 all = tab[y0r] & tab[y0r + bh - (1 << k)];
+            hidden = (all & bm) == bm;
+        }
+        // a box of VB_SPAN_GW or more units per row goes to the span walker: work = its rows
+        if (!hidden) {
+            if (((bw + 3) >> 2) >= VB_SPAN_GW && !(COVER && (R.ent[lane] & (1u << 13))))  // (coverage-only form: flagged boxes stay with the units)
+                srows = bh;
+            else
+                units = ((bw + 3) >> 2) * bh;
+        }
+    }
     // one scan for both walkers: units in the low half (<= 64 x 90), span rows in the high half (<= 64 x 10)
     const int packed = units | (srows << 16);
     const int incl = vb_scan_add(packed);
