@@ -46,6 +46,7 @@ SIGNATURES = {
     "ehr_render_mask_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    "ehr_mask_information": (c_int, [c_void_p] * 8 + [c_int, c_void_p] + [c_int] * 6 + [c_void_p] * 6),
     "ehr_fused_status": (c_int, [c_void_p]),
     "ehr_fused_bind_ref": (c_int, [c_void_p, c_void_p, c_void_p]),
     "ehr_pose_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p,
@@ -150,6 +151,14 @@ def has_intrinsics():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_intrinsics_backward_adam")
+
+
+def has_information():
+    """True if the library has the information matrix of the mask loss (``ehr_mask_information``); the symbol's presence is
+    the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_information")
 
 
 class RigCamera(ctypes.Structure):

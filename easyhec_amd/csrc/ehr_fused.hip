@@ -70,6 +70,19 @@ int ehr_render_mask_loss(ehr_ctx* ctx, const float* verts, const int32_t* tris, 
                        loss, grad_mvp, nullptr, nullptr, stream);
 }
 
+int ehr_mask_information(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
+                         const int32_t* vert_link, const int32_t* opp, const float* mvp, const float* dmvp, int N,
+                         const float* ref, int B, int L, int V, int T, int H, int W, double* info, double* grad,
+                         long long* count, float* loss, float* grad_mvp, void* stream) {
+    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_mask_information: ctx is NULL");
+    if (!verts || !tris || !tri_link || !vert_link || !opp || !mvp || !dmvp || !ref || !info || !grad || !count)
+        return fail(EHR_ERR_INVALID, "ehr_mask_information: NULL tensor");
+    if (ctx->pB != B || ctx->pL != L || ctx->pV != V || ctx->pT != T || ctx->pH != H || ctx->pW != W)
+        return fail(EHR_ERR_INVALID, "ehr_mask_information: shape differs from the planned one; call ehr_fused_plan first");
+    return vbuf_information(ctx, verts, tris, vert_link, opp, mvp, dmvp, N, ref, B, L, V, T, H, W, info, grad, count, loss,
+                            grad_mvp, (hipStream_t)stream);
+}
+
 // What ehr_solver_step and ehr_solver_step_multi share: the checks on their common arguments, and the head and tail of the
 // solver-step form.  `who` is the entry point's name (for messages); they differ in the context's head-state buffer, in how
 // many views one pose owns and in whether Adam is left to the caller.

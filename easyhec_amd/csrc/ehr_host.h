@@ -70,10 +70,23 @@ int vbuf_score(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int3
 int vbuf_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
                  const float* ref, int Q, int S, int L, int V, int T, int H, int W, long long* overlap, long long* ref_area,
                  hipStream_t stream, int* handled);
+// What ehr_mask_information adds to a chain: per chunk of views, behind the composite launch, the launches that turn the
+// chunk's job slots into info / grad / count of its views (vb_info_launch).  NULL: the chain's launches are what they were.
+struct InfoCall {
+    const float* dmvp;  // [N][B][L][16]
+    int N;
+    double* info;       // [B][N][N]
+    double* grad;       // [B][N]
+    long long* count;   // [B]
+};
 int vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
                const int32_t* opp, float* mvp, const float* ref, int B, int L, int V, int T, int H, int W, float* mask,
                float* loss, float* grad_mvp, const StepHead* head, const StepTail* tail, hipStream_t stream,
-               int multi_views = 0);  // > 0: the multi-start step, B = P x multi_views virtual views (ehr_solver_step_multi)
+               int multi_views = 0,  // > 0: the multi-start step, B = P x multi_views virtual views (ehr_solver_step_multi)
+               const InfoCall* info = nullptr);
+int vbuf_information(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const int32_t* opp,
+                     const float* mvp, const float* dmvp, int N, const float* ref, int B, int L, int V, int T, int H, int W,
+                     double* info, double* grad, long long* count, float* loss, float* grad_mvp, hipStream_t stream);
 
 }  // namespace ehr
 
@@ -133,6 +146,8 @@ struct ehr_ctx {
     int vb_weight_views = 0;           // read by every fused call on this plan; view b reads image b % vb_weight_views
     ehr::Scratch vb_hstate;  // i32 [16], survives re-plans: [0] Adam's step counter + 1 as the previous solver step's head saw
                              // it, [1] whether that head advanced the history cursor, [2] where it left it (a REPORTED step's row is reused)
+    ehr::Scratch vb_info;    // ehr_mask_information's own: tile records | group sums | record flags | the saved heavy-job hint |
+                             // stand-ins for loss and grad_mvp (VbInfoScratch).  No captured graph points into it.
     ehr::Scratch vb_hstate_m;  // i32 [pB][VB_HSTATE_INTS]: the same per hypothesis of a multi-start step (ehr_solver_step_multi; kept
                                // across re-plans that do not grow it)
     // space-explorer scoring (ehr_mask_variance) keeps its own scratch so that it never disturbs a solver plan

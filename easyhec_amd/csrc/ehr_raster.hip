@@ -562,6 +562,7 @@ int ehr_ctx_destroy(ehr_ctx* c) {
     c->vb_refsum.release();
     c->vb_hstate.release();
     c->vb_hstate_m.release();
+    c->vb_info.release();
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (int k = 0; k < 2; k++)

@@ -3311,9 +3311,421 @@ int ehr::vbuf_meta_read(ehr_ctx* ctx, int* meta4) {
     return EHR_OK;
 }
 
+// ---- information matrix of the mask loss (ehr_mask_information) ------------------------------
+// After a chunk's composite launch every job slot still holds what the backward pass was built from.  vb_info_kernel
+// reads them once more and forms, per tile that holds a job, the Gauss-Newton sums over the tile's pixels for N caller
+// given tangents dmvp[k] = d MVP / d theta_k:
+//     J_p[k] = gate_p sum_l sum_pairs <d si_l,p / d MVP[b,l], dmvp[k,b,l]>      float32, links in link order, pairs in list order
+//     record = upper triangle of sum_p w_p J_p J_p^T | sum_p (2 w_p e_p) J_p | pixels with w_p > 0 and J_p != 0     float64
+// One wave per tile, no atomics on values: pairs that land on the same pixel are added one after the other in list
+// order (their rank among the batch's lanes), a lane owns whole entries of the record and walks the tile's active pixels
+// in pixel order.  Two small kernels then add the records of a view in tile order, 64 tiles to a group, in float64.
+// A record entry is a sum of squares of per-radian sensitivities (thousands squared, over thousands of pixels): float64,
+// not the 2^32 fixed point of the loss.
+constexpr int VB_INFO_MAX_N = 32;
+constexpr int VB_INFO_GROUP = 64;  // tile records added per workgroup of the first reduction level
+__host__ __device__ constexpr int vb_info_tri(int N) { return N * (N + 1) / 2; }
+__host__ __device__ constexpr int vb_info_rec(int N) { return vb_info_tri(N) + N + 1; }  // doubles per record
+constexpr int VB_INFO_LANE_ENTRIES = (vb_info_tri(VB_INFO_MAX_N) + VB_INFO_MAX_N + 63) / 64;  // entries a lane owns, at most (9)
+constexpr int vb_info_wave_floats(int N) { return 256 * (N + 3); }  // LDS of a wave: J [256][N] | w | 2 w e | active list
+// record entry e -> (ka, kb): info entry (ka <= kb), or gradient entry ka with kb = -1
+__host__ __device__ __forceinline__ void vb_info_entry(int e, int N, int& ka, int& kb) {
+    int k = 0;
+    while (k < N && e >= N - k) {
+        e -= N - k;
+        k++;
+    }
+    if (k < N) {
+        ka = k;
+        kb = k + e;
+    } else {
+        ka = e;
+        kb = -1;
+    }
+}
+
+struct VbInfoArgs {
+    VbSlots sl;           // (read only)
+    const VbItem* spill;
+    int spill_cap;
+    const float* verts;
+    int V;
+    const float* mvp;     // [B][L][16] of the chunk
+    const float* dmvp;    // [N][B_all][L][16] of the call
+    const float* ref;     // [B][H][W] of the chunk
+    VbWeight wt;          // (w == NULL: every weight is 1)
+    int N, B, b0, B_all;  // tangents; views of the chunk, its first view, views of the call
+    BinGeom g;
+    double* rec;          // [B][nt][vb_info_rec(N)] tile records
+    int* valid;           // [B][nt] a record was written (zero before the launch)
+    int* meta;
+};
+
+__global__ void __launch_bounds__(256)
+vb_info_kernel(VbInfoArgs A) {
+    extern __shared__ int s_dyn[];  // [U + 1] first job of every (view, link) | [U] its tile range | per wave vb_info_wave_floats(N)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)(blockDim.x >> 6);
+    const BinGeom g = A.g;
+    const int W = g.W, H = g.H, L = g.L, B = A.B, U = B * L, N = A.N, V = A.V;
+    const int jcap = A.sl.jcap, spill_cap = A.spill_cap;
+    int* const s_jbase = s_dyn;
+    unsigned* const s_utile = reinterpret_cast<unsigned*>(s_dyn + U + 1);
+    float* const J = reinterpret_cast<float*>(s_dyn + 2 * U + 1) + (size_t)wave * vb_info_wave_floats(N);
+    float* const wq = J + 256 * N;   // gate ? w : 0
+    float* const gq = wq + 256;      // 2 w e
+    int* const list = reinterpret_cast<int*>(gq + 256);
+    for (int i = tid; i <= U; i += (int)blockDim.x) s_jbase[i] = A.sl.jbase[i];
+    for (int i = tid; i < U; i += (int)blockDim.x) s_utile[i] = A.sl.jutile[i];
+    __syncthreads();
+    const int nitems = min(s_jbase[U], jcap);
+    const int r = lane >> 3, c4 = (lane & 7) * 4;
+    const float invL = __builtin_amdgcn_rcpf((float)L);
+    const int nent = vb_info_tri(N) + N, R = vb_info_rec(N);
+    int ea[VB_INFO_LANE_ENTRIES], eb[VB_INFO_LANE_ENTRIES];
+#pragma unroll
+    for (int j = 0; j < VB_INFO_LANE_ENTRIES; j++) {
+        ea[j] = -1;
+        eb[j] = -1;
+        if (lane + 64 * j < nent) vb_info_entry(lane + 64 * j, N, ea[j], eb[j]);
+    }
+    for (int item = (int)blockIdx.x * nw + wave; item < nitems; item += (int)gridDim.x * nw) {
+        // the job's (view, link) and tile, and whether it stands for its tile (vb_composite_items' sparse enumeration)
+        int lo = 0, hi = U - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_jbase[mid] <= item)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        const int b = vb_div_small(lo, invL);
+        int tx, ty;
+        {
+            const unsigned ut = s_utile[lo];
+            const int nx = (int)(ut >> 22), k = item - s_jbase[lo];
+            const int kr = nx > 0 ? k / nx : 0;
+            ty = (int)((ut >> 10) & 4095u) + kr;
+            tx = (int)(ut & 1023u) + k - kr * nx;
+        }
+        unsigned tmask;
+        int myn = -1, myslot = 0;
+        bool beyond = false;
+        {
+            bool mine = false;
+            if (lane < L) {
+                const int u = b * L + lane;
+                const unsigned ut = s_utile[u];
+                const int j0 = s_jbase[u], n = s_jbase[u + 1] - j0;
+                const int tx0 = ut & 1023u, ty0 = (ut >> 10) & 4095u, nx = ut >> 22;
+                if (n > 0 && tx >= tx0 && tx < tx0 + nx && ty >= ty0 && (ty - ty0) * nx < n) {
+                    mine = true;
+                    myslot = j0 + (ty - ty0) * nx + (tx - tx0);
+                    if (myslot < jcap)
+                        myn = A.sl.jn[myslot];
+                    else
+                        beyond = true;
+                }
+            }
+            const u64 have = __ballot(mine);
+            if (have == 0 || (int)__ffsll((unsigned long long)have) - 1 != lo - b * L) continue;  // an earlier link owns the tile
+            tmask = (unsigned)__ballot(myn >= 0);
+        }
+        if (__ballot(beyond) && lane == 0) atomicOr(&A.meta[EHR_META_OVERFLOW], 1);  // a slot beyond jcap: reported
+        const unsigned bmask = (unsigned)__ballot(myn > 0);
+        if (bmask == 0 || tx >= g.ntx || ty >= g.nty) continue;  // no blended pair: every J of the tile is zero
+        const int tile = ty * g.ntx + tx;
+        const int rx0 = tx * EHR_TILE_W - 1, ry0 = ty * EHR_TILE_H - 1;
+        // ---- 1. the links' sum in link order, gate, e, w (the composite stage's float32 expressions)
+        {
+            const int ix = tx * EHR_TILE_W + c4, iy = ty * EHR_TILE_H + r;
+            const bool row_in = iy < H;
+            const int row = H - 1 - (row_in ? iy : 0);  // image convention: row 0 = top
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+            unsigned todo = tmask;
+            while (todo) {
+                const int l = __ffs(todo) - 1;
+                todo &= todo - 1;
+                const size_t slot = (size_t)vb_readlane(myslot, l);
+                const float4 v4 = *reinterpret_cast<const float4*>(A.sl.jval + slot * 256 + r * EHR_TILE_W + c4);
+                acc[0] += v4.x;
+                acc[1] += v4.y;
+                acc[2] += v4.z;
+                acc[3] += v4.w;
+            }
+            VB_WAVE_SYNC();  // the previous tile's reads of this wave's LDS are complete
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float wg = 0.f, ge = 0.f;
+                if (row_in && ix + j < W) {
+                    const float rf = A.ref[((size_t)b * H + row) * W + ix + j];
+                    const float wv = A.wt.w ? A.wt.w[((size_t)((A.wt.view0 + b) % A.wt.nviews) * H + row) * W + ix + j] : 1.f;
+                    const float m = acc[j] > 1.f ? 1.f : acc[j];
+                    const float e = m - rf;
+                    const float we = wv * e;
+                    ge = 2.f * we;
+                    wg = (acc[j] <= 1.f) ? wv : 0.f;
+                }
+                wq[r * EHR_TILE_W + c4 + j] = wg;
+                gq[r * EHR_TILE_W + c4 + j] = ge;
+            }
+            for (int i = lane; i < 256 * N; i += 64) J[i] = 0.f;
+            VB_WAVE_SYNC();
+        }
+        // ---- 2. every blended pair of every link -> J of the pixel it blends into
+        unsigned links = bmask;
+        while (links) {
+            const int l = __ffs(links) - 1;
+            links &= links - 1;
+            const size_t slot = (size_t)vb_readlane(myslot, l);
+            int n = vb_readlane(myn, l);
+            int sbase = 0;
+            if (n > VB_JOB_ITEMS) {  // the rest of the list lives in the spill pool; never read outside it
+                sbase = A.sl.jspill[slot];
+                if (sbase < 0 || sbase >= spill_cap) {
+                    n = VB_JOB_ITEMS;
+                    if (lane == 0) atomicOr(&A.meta[EHR_META_OVERFLOW], 1);
+                } else if (n > VB_JOB_ITEMS + (spill_cap - sbase)) {
+                    n = VB_JOB_ITEMS + (spill_cap - sbase);
+                    if (lane == 0) atomicOr(&A.meta[EHR_META_OVERFLOW], 1);
+                }
+            }
+            const float* const M = A.mvp + ((size_t)b * L + l) * 16;
+            const float* const D0 = A.dmvp + (((size_t)(A.b0 + b)) * L + l) * 16;
+            const size_t dstride = (size_t)A.B_all * L * 16;
+            for (int base = 0; base < n; base += 64) {
+                const int i = base + lane;
+                bool on = i < n;
+                int tp = -1;
+                float g1[3] = {0.f, 0.f, 0.f}, g2[3] = {0.f, 0.f, 0.f};
+                float h1[3] = {0.f, 0.f, 0.f}, h2[3] = {0.f, 0.f, 0.f};
+                if (on) {
+                    const VbItem itm = *((i < VB_JOB_ITEMS) ? &A.sl.jitems[slot * VB_JOB_ITEMS + i] : &A.spill[sbase + (i - VB_JOB_ITEMS)]);
+                    const int q = itm.packed & 1023, d = (itm.packed >> 10) & 1;
+                    const int tri1 = (itm.packed >> 13) & 1;
+                    const float dc = ((itm.packed >> 14) & 1) ? 1.f : -1.f;
+                    const int nq = q + (d ? VB_RW : 1);
+                    const int oq = (itm.alpha > 0.f) ? q : nq;
+                    const int oy = vb_div_rw(oq), ox = oq - oy * VB_RW;
+                    on = ox >= 1 && ox <= EHR_TILE_W && oy >= 1 && oy <= EHR_TILE_H && (unsigned)itm.v1 < (unsigned)V &&
+                         (unsigned)itm.v2 < (unsigned)V;
+                    if (on) {
+                        tp = (oy - 1) * EHR_TILE_W + (ox - 1);
+                        on = wq[tp] != 0.f;  // gated, outside the image or without weight: contributes nothing
+                    }
+                    if (on) {
+                        const int qy = vb_div_rw(q), qx = q - qy * VB_RW;
+                        int px = rx0 + qx, py = ry0 + qy;
+                        if (tri1) {
+                            px += 1 - d;
+                            py += d;
+                        }
+                        const float* a1 = A.verts + 3 * (size_t)itm.v1;
+                        const float* a2 = A.verts + 3 * (size_t)itm.v2;
+                        h1[0] = a1[0]; h1[1] = a1[1]; h1[2] = a1[2];
+                        h2[0] = a2[0]; h2[1] = a2[1]; h2[2] = a2[2];
+                        aa_pos_grad(transform_vertex(M, h1[0], h1[1], h1[2]), transform_vertex(M, h2[0], h2[1], h2[2]), px, py, d,
+                                    itm.alpha, dc, W, H, g1, g2);
+                    } else {
+                        tp = -1;
+                    }
+                }
+                // rank of this pair among the batch's pairs of the same pixel: they are added one after the other
+                int rank = 0;
+                for (int j = 0; j < 64; j++) {
+                    const int tj = vb_readlane(tp, j);
+                    rank += (j < lane && tj == tp) ? 1 : 0;
+                }
+                if (!on) rank = -1;
+                const int nrank = vb_scan_max(rank + 1);
+                const int rounds = vb_readlane(nrank, 63);
+                for (int k = 0; k < N; k++) {
+                    const float* const D = D0 + (size_t)k * dstride;
+                    // d clip / d theta_k of the two vertices, then the pair's contribution: rows x, y, w
+                    const float4 t1 = transform_vertex(D, h1[0], h1[1], h1[2]);
+                    const float4 t2 = transform_vertex(D, h2[0], h2[1], h2[2]);
+                    const float c = (g1[0] * t1.x + g1[1] * t1.y + g1[2] * t1.w) + (g2[0] * t2.x + g2[1] * t2.y + g2[2] * t2.w);
+                    for (int rr = 0; rr < rounds; rr++) {
+                        if (rank == rr) J[tp * N + k] += c;
+                        VB_WAVE_SYNC();
+                    }
+                }
+            }
+        }
+        VB_WAVE_SYNC();
+        // ---- 3. the tile's active pixels in pixel order, then its record
+        int npix = 0, cnt = 0;
+        for (int c = 0; c < 4; c++) {
+            const int p = c * 64 + lane;
+            bool any = false;
+            for (int k = 0; k < N; k++) any = any || (J[p * N + k] != 0.f);
+            const u64 m = __ballot(any);
+            if (any) list[npix + vb_mbcnt(m)] = p;
+            npix += __popcll(m);
+            cnt += __popcll(__ballot(any && wq[p] > 0.f));
+        }
+        if (npix == 0) continue;
+        VB_WAVE_SYNC();
+        double sum[VB_INFO_LANE_ENTRIES];
+#pragma unroll
+        for (int j = 0; j < VB_INFO_LANE_ENTRIES; j++) sum[j] = 0.0;
+        for (int i = 0; i < npix; i++) {
+            const int p = list[i];
+            const double w = (double)wq[p], ge = (double)gq[p];
+            const float* const Jp = J + p * N;
+#pragma unroll
+            for (int j = 0; j < VB_INFO_LANE_ENTRIES; j++) {
+                if (ea[j] < 0) continue;
+                const double a = (double)Jp[ea[j]];
+                if (eb[j] >= 0)
+                    sum[j] += w * (a * (double)Jp[eb[j]]);
+                else
+                    sum[j] += ge * a;
+            }
+        }
+        double* const rec = A.rec + ((size_t)b * g.nt + tile) * R;
+#pragma unroll
+        for (int j = 0; j < VB_INFO_LANE_ENTRIES; j++)
+            if (ea[j] >= 0) rec[lane + 64 * j] = sum[j];
+        if (lane == 0) {
+            rec[R - 1] = (double)cnt;
+            A.valid[(size_t)b * g.nt + tile] = 1;
+        }
+    }
+}
+
+// out[b][grp][e] = sum in order of in[b][t][e] over the group's valid records t (valid == NULL: all of them)
+__global__ void __launch_bounds__(256)
+vb_info_group_kernel(const double* __restrict__ in, const int* __restrict__ valid, int n, int R, double* __restrict__ out) {
+    const int b = blockIdx.y, grp = blockIdx.x, ngrp = gridDim.x;
+    const int t0 = grp * VB_INFO_GROUP, t1 = min(n, t0 + VB_INFO_GROUP);
+    for (int e = threadIdx.x; e < R; e += 256) {
+        double s = 0.0;
+        for (int t = t0; t < t1; t++)
+            if (!valid || valid[(size_t)b * n + t]) s += in[((size_t)b * n + t) * R + e];
+        out[((size_t)b * ngrp + grp) * R + e] = s;
+    }
+}
+
+// grp [B][ngrp][R] -> info [B][N][N] (both triangles), grad [B][N], count [B] of the chunk's views; a non-finite sum is reported
+__global__ void __launch_bounds__(256)
+vb_info_finish_kernel(const double* __restrict__ grp, int ngrp, int N, double* __restrict__ info, double* __restrict__ grad,
+                      long long* __restrict__ count, int* __restrict__ meta) {
+    const int b = blockIdx.x, R = vb_info_rec(N);
+    for (int e = threadIdx.x; e < R; e += 256) {
+        double s = 0.0;
+        for (int k = 0; k < ngrp; k++) s += grp[((size_t)b * ngrp + k) * R + e];
+        if (!(fabs(s) <= 1.7e308)) atomicOr(&meta[EHR_META_OVERFLOW], 1);  // (also a NaN)
+        if (e == R - 1) {
+            count[b] = (long long)s;
+        } else {
+            int ka, kb;
+            vb_info_entry(e, N, ka, kb);
+            if (kb < 0) {
+                grad[(size_t)b * N + ka] = s;
+            } else {
+                info[((size_t)b * N + ka) * N + kb] = s;
+                info[((size_t)b * N + kb) * N + ka] = s;
+            }
+        }
+    }
+}
+
+// A reported call (the chain's own overflow, or one of the above): every output is NaN, count -1
+__global__ void __launch_bounds__(256)
+vb_info_report_kernel(const int* __restrict__ meta, int B, int N, double* __restrict__ info, double* __restrict__ grad,
+                      long long* __restrict__ count, float* __restrict__ loss) {
+    if (__hip_atomic_load(&meta[EHR_META_OVERFLOW], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+    const double nanv = __longlong_as_double(0x7ff8000000000000ll);
+    const int b = blockIdx.x;
+    for (int e = threadIdx.x; e < N * N; e += 256) info[(size_t)b * N * N + e] = nanv;
+    for (int e = threadIdx.x; e < N; e += 256) grad[(size_t)b * N + e] = nanv;
+    if (threadIdx.x == 0) {
+        count[b] = -1;
+        if (loss) loss[b] = __int_as_float(0x7fc00000);
+    }
+}
+
+// scratch of ehr_mask_information (ehr_ctx::vb_info), for chunks of Bc views
+struct VbInfoScratch {
+    double* rec;    // [Bc][nt][R]
+    double* grp;    // [Bc][ngrp][R]
+    int* valid;     // [Bc][nt]
+    int* hint;      // a copy of the heavy-job hint (ehr_ctx::vb_heavy), put back after the call
+    float* loss;    // [B] where the caller wants no loss
+    float* grad;    // [B][L][16] where the caller wants no grad_mvp
+};
+static VbInfoScratch vb_info_scratch(void* base, size_t Bc, size_t nt, size_t R, size_t hint_bytes, size_t B, size_t L, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbInfoScratch s;
+    const size_t ngrp = (nt + VB_INFO_GROUP - 1) / VB_INFO_GROUP;
+    s.rec = c.take<double>(Bc * nt * R);
+    s.grp = c.take<double>(Bc * ngrp * R);
+    s.valid = c.take<int>(Bc * nt);
+    s.hint = c.take<int>(hint_bytes / sizeof(int), 16);
+    s.loss = c.take<float>(B, 16);
+    s.grad = c.take<float>(B * L * 16, 16);
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return s;
+}
+
+// The chunk's launches of ehr_mask_information, behind its composite launch
+static int vb_info_launch(ehr_ctx* ctx, const InfoCall& ic, const VbSlots& sl, const VbItem* spill, const float* verts, int V,
+                          const float* mvp_k, const float* ref_k, const VbWeight& wt, int Bk, int b0, int B, const BinGeom& g,
+                          int* meta, hipStream_t stream) {
+    const int N = ic.N, R = vb_info_rec(N);
+    const int Bc = std::max(1, std::min(ctx->vb_chunk, B));
+    const VbInfoScratch s = vb_info_scratch(ctx->vb_info.ptr, Bc, g.nt, R, ctx->vb_heavy.cap, B, g.L);
+    int rc;
+    if ((rc = zero_words(s.valid, (size_t)Bk * g.nt, stream))) return rc;
+    VbInfoArgs a;
+    a.sl = sl; a.spill = spill; a.spill_cap = ctx->vb_spill_cap; a.verts = verts; a.V = V; a.mvp = mvp_k; a.dmvp = ic.dmvp;
+    a.ref = ref_k; a.wt = wt; a.N = N; a.B = Bk; a.b0 = b0; a.B_all = B; a.g = g; a.rec = s.rec; a.valid = s.valid; a.meta = meta;
+    // waves per workgroup: as many of 4, 2, 1 as the default 64 KB of dynamic LDS hold
+    const size_t tables = (2 * (size_t)Bk * g.L + 1) * sizeof(int), per_wave = (size_t)vb_info_wave_floats(N) * sizeof(float);
+    int nw = 4;
+    while (nw > 1 && tables + nw * per_wave > 65536) nw >>= 1;
+    const int nwg = std::max(1, ctx->num_cus * 16 / nw);
+    vb_info_kernel<<<nwg, 64 * nw, tables + nw * per_wave, stream>>>(a);
+    EHR_LAUNCH_CHECK();
+    const int ngrp = (g.nt + VB_INFO_GROUP - 1) / VB_INFO_GROUP;
+    vb_info_group_kernel<<<dim3(ngrp, Bk), 256, 0, stream>>>(s.rec, s.valid, g.nt, R, s.grp);
+    EHR_LAUNCH_CHECK();
+    vb_info_finish_kernel<<<Bk, 256, 0, stream>>>(s.grp, ngrp, N, ic.info + (size_t)b0 * N * N, ic.grad + (size_t)b0 * N,
+                                                  ic.count + b0, meta);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr::vbuf_information(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const int32_t* opp,
+                          const float* mvp, const float* dmvp, int N, const float* ref, int B, int L, int V, int T, int H, int W,
+                          double* info, double* grad, long long* count, float* loss, float* grad_mvp, hipStream_t stream) {
+    if (N < 1 || N > VB_INFO_MAX_N)
+        return fail(EHR_ERR_INVALID, "ehr_mask_information: N = %d tangents (1 <= N <= %d)", N, VB_INFO_MAX_N);
+    if (ctx->capturing) return fail(EHR_ERR_INVALID, "ehr_mask_information: not inside a graph capture");
+    const BinGeom g = make_geom(H, W, L);
+    const int Bc = std::max(1, std::min(ctx->vb_chunk, B));
+    size_t bytes;
+    vb_info_scratch(nullptr, Bc, g.nt, vb_info_rec(N), ctx->vb_heavy.cap, B, L, &bytes);
+    int rc;
+    if ((rc = ctx->vb_info.reserve(bytes))) return rc;
+    const VbInfoScratch s = vb_info_scratch(ctx->vb_info.ptr, Bc, g.nt, vb_info_rec(N), ctx->vb_heavy.cap, B, L);
+    // the heavy-job hint is the solve's: the chain below advances it, so it is put back as it was
+    if ((rc = copy_words(s.hint, ctx->vb_heavy.ptr, ctx->vb_heavy.cap / sizeof(int), stream))) return rc;
+    InfoCall ic;
+    ic.dmvp = dmvp; ic.N = N; ic.info = info; ic.grad = grad; ic.count = count;
+    float* const loss_k = loss ? loss : s.loss;
+    rc = vbuf_chain(ctx, verts, tris, vert_link, opp, const_cast<float*>(mvp), ref, B, L, V, T, H, W, nullptr, loss_k,
+                    grad_mvp ? grad_mvp : s.grad, nullptr, nullptr, stream, 0, &ic);
+    if (rc) return rc;
+    if ((rc = copy_words(ctx->vb_heavy.ptr, s.hint, ctx->vb_heavy.cap / sizeof(int), stream))) return rc;
+    vb_info_report_kernel<<<B, 256, 0, stream>>>(vb_acc_meta((long long*)ctx->vb_acc.ptr, B, L), B, N, info, grad, count, loss);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
 int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const int32_t* opp, float* mvp, const float* ref, int B, int L, int V,
                     int T, int H, int W, float* mask, float* loss, float* grad_mvp, const StepHead* head,
-                    const StepTail* tail, hipStream_t stream, int multi_views) {
+                    const StepTail* tail, hipStream_t stream, int multi_views, const InfoCall* info) {
     const bool multi = multi_views > 0;  // B = P x multi_views virtual views; ref and head->link_poses hold multi_views real ones
     if (tris != ctx->vb_plan_tris || opp != ctx->vb_plan_opp || verts != ctx->vb_plan_verts)
         return fail(EHR_ERR_INVALID, "fused op: the scene arrays differ from the planned ones; call ehr_fused_plan again");
@@ -3463,6 +3875,10 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
 #undef VB_COMPOSITE
 #undef VB_COMPOSITE_W
         EHR_LAUNCH_CHECK();
+        if (info) {  // ehr_mask_information: the chunk's slots are read once more before the next chunk overwrites them
+            const int rc = vb_info_launch(ctx, *info, sl, spill, verts, V, mvp_k, ref_k, wt, Bk, b0, B, g, meta, stream);
+            if (rc) return rc;
+        }
     }
     if (ev) EHR_HIP(hipEventRecord(ev[5], stream));
     if (multi) {  // the finish stage, one workgroup per hypothesis (ms[5] of the timing ABI)

@@ -191,6 +191,27 @@ int ehr_fused_bind_ref_shared(ehr_ctx* ctx, const float* ref, int Bv, void* stre
  * ehr_version() is unchanged: the presence of this symbol is the capability check. */
 int ehr_fused_bind_weight(ehr_ctx* ctx, const float* weight, int Bv, void* stream);
 
+/* Gauss-Newton information matrix of the fused mask loss for N caller-given tangents dmvp[k] = d MVP / d theta_k
+ * ([N,B,L,16] float32; 1 <= N <= 32, anything else is refused).  On the planned context, with the bound weights and a
+ * bound reference honoured like ehr_render_mask_loss does.  Per pixel p of view b, with s_p the float32 link sum, m_p the
+ * composited mask, e_p = m_p - ref_p, w_p the bound weight (or 1) and gate_p = (s_p <= 1):
+ *     J_p[k]  = gate_p * sum_l <d si_l,p / d MVP[b,l], dmvp[k,b,l]>     (the composite stage's blended-pair terms, float32)
+ *     info[b] = sum_p w_p J_p J_p^T            [B,N,N] float64, exactly symmetric
+ *     grad[b] = sum_p 2 w_p e_p J_p            [B,N]   float64: the loss gradient along the tangents
+ *     count[b] = pixels with w_p > 0 and some J_p[k] != 0                [B] int64
+ * Per view; sums over views, cameras or hypotheses are the caller's, in float64.  loss [B] and grad_mvp [B,L,16] (both may
+ * be NULL) are what ehr_render_mask_loss gives, bit for bit: the call runs that chain and, per chunk of views, one more
+ * kernel over the chunk's job slots plus a fixed-order float64 reduction.  No atomics on values: two calls, or two
+ * contexts, give identical bits.  A reported call (the chain's overflow, a spill index outside the pool, a slot beyond
+ * the plan's, a non-finite sum) leaves info, grad and loss NaN and count -1, and raises ehr_fused_status.  The context's
+ * heavy-job hint, bound reference and weights and a solve's optimiser state are as they were afterwards; a natively
+ * captured chain stays valid.  Not to be called inside a graph capture (its scratch is sized on the first call).
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+int ehr_mask_information(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* tri_link,
+                         const int32_t* vert_link, const int32_t* opp, const float* mvp, const float* dmvp, int N,
+                         const float* ref, int B, int L, int V, int T, int H, int W, double* info, double* grad,
+                         long long* count, float* loss, float* grad_mvp, void* stream);
+
 /* Measurement hook (bench.py's roofline leg): when enabled, every ehr_render_mask_loss / ehr_solver_step call records
  * hipEvents around its kernels on the launch stream.  ehr_fused_timing_read synchronises, writes the ACCUMULATED
  * milliseconds per stage since the last read and the number of calls covered, then resets.  Stages of the default
