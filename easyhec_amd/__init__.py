@@ -8,3 +8,11 @@
 The compute path is libehr_hip.so (hand-written HIP for gfx950, C ABI in include/ehr.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the Levenberg-Marquardt solve (easyhec_amd/lm.py), looked up on first use: importing the package stays free of torch
+    if name in ("LevenbergMarquardt", "solve_lm", "LmResult"):
+        from . import lm
+        return getattr(lm, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

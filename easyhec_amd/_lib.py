@@ -83,6 +83,9 @@ SIGNATURES = {
     "ehr_rig_backward_adam": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 7 + [c_float] * 7 + [c_void_p, c_void_p]),
     "ehr_intrinsics_backward_adam": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4 +
                                      [c_float] * 5 + [c_void_p] * 3),
+    "ehr_lm_linearize": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3),
+    "ehr_lm_update": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 +
+                      [c_void_p] * 2 + [c_int] * 2 + [ctypes.c_double] * 2 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p]),
 }
 
 
@@ -159,6 +162,21 @@ def has_information():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_information")
+
+
+def has_lm():
+    """True if the library has the Levenberg-Marquardt kernels (``ehr_lm_linearize`` / ``ehr_lm_update``); the symbols'
+    presence is the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
+    return hasattr(l, "ehr_lm_linearize") and hasattr(l, "ehr_lm_update")
+
+
+# the state block of ehr_lm_update (include/ehr.h: EHR_LM_*), in float64 words
+LM_STATE = {"lambda": 0, "nu": 1, "F_acc": 2, "pred": 3, "rho": 4, "F_trial": 5, "iterations": 6, "accepted": 7, "rejected": 8,
+            "reported": 9, "done": 10, "why": 11, "last": 12, "count": 13, "retries": 14}
+LM_THETA, LM_DELTA, LM_G, LM_H, LM_STATE_DOUBLES, LM_MAX_PARAMS = 16, 48, 80, 112, 1136, 32
 
 
 class RigCamera(ctypes.Structure):

@@ -1,0 +1,543 @@
+// ehr_lm.hip -- Levenberg-Marquardt on the information matrix of the mask loss (easyhec_amd/lm.py): the
+// two small kernels that surround ehr_mask_information in one iteration
+//
+//     [ehr_joint_forward]  ->  ehr_lm_linearize  ->  ehr_mask_information  ->  ehr_lm_update        on one stream.
+//
+//   lm_linearize : dof, K as rendered, link_poses [, joint_frames] -> mvp [B,L,16] (ehr_pose_forward's, bit for bit: the same
+//                  device functions of ehr_pose_core.h) and the tangents dmvp [N,B,L,16] = d MVP[b,l] / d theta_k, evaluated in
+//                  float64 at the float32 parameters and rounded once.  One thread per (k, b, l) matrix.
+//   lm_update    : the call's info / grad / loss / count -> accept or reject the trial, the damping's schedule, the damped
+//                  normal equations (H_acc + lambda D) delta = -g_acc / 2 by a Cholesky factorisation of the scaled system, the
+//                  predicted reduction, the stopping rule, and the next trial's parameters (or the accepted ones).  One
+//                  workgroup of one wave, float64 throughout, every sum in a fixed order.
+//
+// No kernel here allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
+#include "ehr_host.h"
+#include "ehr_pose_core.h"
+
+#define EHR_LM_MAX_RETRIES 8  // non-positive pivots in a row (lambda raised each time) before the solve gives up
+
+namespace ehr {
+
+// ---- float64 forward mode with ONE partial: the exponential map of ehr_pose_core.h (se3_exp_dual) restated in float64 ----------
+struct DD {
+    double v, d;
+};
+__device__ __forceinline__ DD dd(double v, double d = 0.0) {
+    DD r;
+    r.v = v;
+    r.d = d;
+    return r;
+}
+__device__ __forceinline__ DD operator+(const DD& a, const DD& b) { return dd(a.v + b.v, a.d + b.d); }
+__device__ __forceinline__ DD operator-(const DD& a, const DD& b) { return dd(a.v - b.v, a.d - b.d); }
+__device__ __forceinline__ DD operator*(const DD& a, const DD& b) { return dd(a.v * b.v, a.d * b.v + a.v * b.d); }
+__device__ __forceinline__ DD operator/(const DD& a, const DD& b) {
+    const double inv = 1.0 / b.v, q = a.v * inv;
+    return dd(q, (a.d - q * b.d) * inv);
+}
+__device__ __forceinline__ DD ddsqrt(const DD& a) {
+    const double s = sqrt(a.v);
+    return dd(s, a.d * (0.5 / s));
+}
+__device__ __forceinline__ DD ddsin(const DD& a) { return dd(sin(a.v), a.d * cos(a.v)); }
+__device__ __forceinline__ DD ddcos(const DD& a) { return dd(cos(a.v), -a.d * sin(a.v)); }
+
+// Tc = se3_exp_map(dof) (row-major, [[R, t], [0, 1]]) and d Tc / d dof[which] (which < 0: values only), in float64 at the
+// float32 dof; the squared angle is clamped at 1e-4 and the gradient passes only where it is not (torch.clamp).
+__device__ void se3_exp_f64(const float* dof, int which, double* T, double* dT) {
+    DD x[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) x[i] = dd((double)dof[i], i == which ? 1.0 : 0.0);
+    const DD w0 = x[3], w1 = x[4], w2 = x[5];
+    DD nrms = w0 * w0 + w1 * w1 + w2 * w2;
+    if (!(nrms.v >= 1e-4)) nrms = dd(1e-4);
+    const DD th = ddsqrt(nrms), one = dd(1.0), zero = dd(0.0);
+    const DD inv = one / th;
+    const DD fac1 = inv * ddsin(th);
+    const DD fac2 = inv * inv * (one - ddcos(th));
+    const DD fv1 = (one - ddcos(th)) / (th * th);
+    const DD fv2 = (th - ddsin(th)) / (th * th * th);
+    const DD Kx[9] = {zero, zero - w2, w1, w2, zero, zero - w0, zero - w1, w0, zero};
+    DD K2[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) K2[3 * r + c] = Kx[3 * r] * Kx[c] + Kx[3 * r + 1] * Kx[3 + c] + Kx[3 * r + 2] * Kx[6 + c];
+    for (int r = 0; r < 3; r++) {
+        DD t = zero;
+        for (int c = 0; c < 3; c++) {
+            const DD I = dd(r == c ? 1.0 : 0.0);
+            const DD R = fac1 * Kx[3 * r + c] + fac2 * K2[3 * r + c] + I;
+            T[4 * r + c] = R.v;
+            dT[4 * r + c] = R.d;
+            const DD V = I + Kx[3 * r + c] * fv1 + K2[3 * r + c] * fv2;
+            t = t + V * x[c];
+        }
+        T[4 * r + 3] = t.v;
+        dT[4 * r + 3] = t.d;
+    }
+    for (int c = 0; c < 4; c++) {
+        T[12 + c] = c == 3 ? 1.0 : 0.0;
+        dT[12 + c] = 0.0;
+    }
+}
+
+__device__ __forceinline__ void mat4_mul_f64(const double* A, const double* B, double* C) {
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++)
+            C[4 * r + c] = ((A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c]) + A[4 * r + 2] * B[8 + c]) + A[4 * r + 3] * B[12 + c];
+}
+
+// Which intrinsics element(s) the q-th free intrinsics parameter moves: the order is "f" (tied: elements 0 and 1 together) or
+// "fx", "fy", then "cx", "cy" (easyhec_amd/intrinsics_calib.py).  Returns the first element, or -1 past the end.
+__device__ __forceinline__ int lm_intrinsics_element(int q, int free4_mask, int tie_focal) {
+    if (tie_focal) {
+        if (q == 0) return 0;
+        q -= 1;
+    } else {
+        for (int i = 0; i < 2; i++)
+            if ((free4_mask >> i) & 1) {
+                if (q == 0) return i;
+                q -= 1;
+            }
+    }
+    for (int i = 2; i < 4; i++)
+        if ((free4_mask >> i) & 1) {
+            if (q == 0) return i;
+            q -= 1;
+        }
+    return -1;
+}
+
+__global__ void __launch_bounds__(256) lm_linearize_kernel(const float* __restrict__ dof, const float* __restrict__ K,
+                                                           const float* __restrict__ link_poses, int B, int L, int H, int W,
+                                                           float n, float f, const float* __restrict__ joint_frames,
+                                                           const unsigned* __restrict__ upstream,
+                                                           const int* __restrict__ joint_kind, const int* __restrict__ free_list,
+                                                           int F, int J, int free4_mask, int tie_focal, int N,
+                                                           float* __restrict__ mvp, float* __restrict__ dmvp) {
+    const int BL = B * L;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)(N + 1) * BL) return;
+    const int k = (int)(idx / BL) - 1, i = (int)(idx % BL);
+    const float* lpf = link_poses + (size_t)i * 16;
+    if (k < 0) {  // the matrix itself: pose_forward_kernel's expressions
+        Dual<1> T[16];
+        se3_exp_dual<1>(dof, 1e-4f, T);
+        float Tc[16], P[16], C[16];
+        for (int e = 0; e < 16; e++) Tc[e] = T[e].v;
+        projection(K, H, W, n, f, P);
+        mvp_from_pose(Tc, P, lpf, C);
+        for (int e = 0; e < 16; e++) mvp[(size_t)i * 16 + e] = C[e];
+        return;
+    }
+    double Tc[16], dTc[16], lp[16], M[16], A[16], out[16];
+    se3_exp_f64(dof, k < 6 ? k : -1, Tc, dTc);
+    for (int e = 0; e < 16; e++) lp[e] = (double)lpf[e];
+    const double fu = (double)K[0], fv = (double)K[4], cu = (double)K[2], cv = (double)K[5];
+    const double nn = (double)n, ff = (double)f;
+    double PF[16];  // proj(K) @ diag(1,-1,-1,1), in float64 from the float32 K
+    for (int e = 0; e < 16; e++) PF[e] = 0.0;
+    PF[0] = 2.0 * fu / (double)W;
+    PF[2] = -(-2.0 * cu / (double)W + 1.0);
+    PF[5] = -(2.0 * fv / (double)H);
+    PF[6] = -(2.0 * cv / (double)H - 1.0);
+    PF[10] = (ff + nn) / (ff - nn);
+    PF[11] = -2.0 * ff * nn / (ff - nn);
+    PF[14] = 1.0;
+    for (int e = 0; e < 16; e++) out[e] = 0.0;
+    if (k < 6) {  // PF @ dTc/ddof_k @ lp
+        mat4_mul_f64(dTc, lp, M);
+        mat4_mul_f64(PF, M, out);
+    } else if (k < 6 + F) {  // PF @ Tc @ D_blj
+        const int j = free_list[k - 6];
+        const int b = i / L, l = i - b * L;
+        const int kind = (j >= 0 && j < J) ? joint_kind[j] : 0;
+        if (j >= 0 && j < J && ((upstream[l] >> j) & 1u) && (kind == 1 || kind == 2)) {
+            const float* jf = joint_frames + ((size_t)b * J + j) * 6;
+            const double a[3] = {(double)jf[0], (double)jf[1], (double)jf[2]};
+            double D[16];
+            for (int e = 0; e < 16; e++) D[e] = 0.0;
+            if (kind == 1) {  // [a]x R_l | a x (t_l - p)
+                const double d[3] = {lp[3] - (double)jf[3], lp[7] - (double)jf[4], lp[11] - (double)jf[5]};
+                for (int c = 0; c < 3; c++) {
+                    D[c] = a[1] * lp[8 + c] - a[2] * lp[4 + c];
+                    D[4 + c] = a[2] * lp[c] - a[0] * lp[8 + c];
+                    D[8 + c] = a[0] * lp[4 + c] - a[1] * lp[c];
+                }
+                D[3] = a[1] * d[2] - a[2] * d[1];
+                D[7] = a[2] * d[0] - a[0] * d[2];
+                D[11] = a[0] * d[1] - a[1] * d[0];
+            } else {          // 0 | a
+                D[3] = a[0];
+                D[7] = a[1];
+                D[11] = a[2];
+            }
+            mat4_mul_f64(Tc, D, M);
+            mat4_mul_f64(PF, M, out);
+        }
+    } else {  // d proj / d theta @ diag(1,-1,-1,1) @ Tc @ lp: the derivatives that ehr_intrinsics_backward_adam's s0..s3 imply
+        const int el = lm_intrinsics_element(k - 6 - F, free4_mask, tie_focal);
+        mat4_mul_f64(Tc, lp, A);
+        for (int c = 0; c < 4; c++) {
+            A[4 + c] = -A[4 + c];
+            A[8 + c] = -A[8 + c];
+        }
+        for (int c = 0; c < 4; c++) {
+            if (el == 0) out[c] = (2.0 * fu / (double)W) * A[c];
+            if (el == 1 || (el == 0 && tie_focal)) out[4 + c] = (2.0 * fv / (double)H) * A[4 + c];
+            if (el == 2) out[c] = -2.0 * A[8 + c];
+            if (el == 3) out[4 + c] = 2.0 * A[8 + c];
+        }
+    }
+    float* o = dmvp + ((size_t)k * BL + i) * 16;
+    for (int e = 0; e < 16; e++) o[e] = (float)out[e];
+}
+
+// ---- the update ---------------------------------------------------------------------------------------------------------------
+// ehr_intrinsics.hip's intrinsics_entry (the "writing K" rule of ehr_intrinsics_backward_adam), restated: one entry of K from K0
+// and its parameter in float64, rounded once; a parameter that is exactly zero gives K0's bits.
+__device__ __forceinline__ float lm_intrinsics_entry(const float* __restrict__ K0, float th, int i, int H, int W) {
+    const float k0 = K0[i == 0 ? 0 : (i == 1 ? 4 : (i == 2 ? 2 : 5))];
+    double x;
+    if (i < 2)
+        x = (double)k0 * exp((double)th);
+    else
+        x = (double)k0 + (double)(i == 2 ? W : H) * (double)th;
+    return th == 0.f ? k0 : (float)x;
+}
+
+struct LmParams {  // where the N parameters live: dof, then the free joints' offsets, then the free intrinsics
+    float* dof;
+    float* offset;
+    const int* free_list;
+    int F, J;
+    float* theta;
+    int free4_mask, tie_focal;
+    const float* K0;
+    float* K;
+    int H, W;
+};
+__device__ __forceinline__ float lm_param_read(const LmParams& p, int k) {
+    if (k < 6) return p.dof[k];
+    if (k < 6 + p.F) {
+        const int j = p.free_list[k - 6];  // (device memory: an index outside the offsets is read nowhere)
+        return (j >= 0 && j < p.J) ? p.offset[j] : 0.f;
+    }
+    return p.theta[lm_intrinsics_element(k - 6 - p.F, p.free4_mask, p.tie_focal)];
+}
+__device__ __forceinline__ void lm_param_write(const LmParams& p, int k, float x) {
+    if (k < 6) {
+        p.dof[k] = x;
+    } else if (k < 6 + p.F) {
+        const int j = p.free_list[k - 6];
+        if (j >= 0 && j < p.J) p.offset[j] = x;
+    } else {
+        const int el = lm_intrinsics_element(k - 6 - p.F, p.free4_mask, p.tie_focal);
+        p.theta[el] = x;
+        if (p.tie_focal && el == 0) p.theta[1] = x;  // both focal entries move together
+    }
+}
+// K from theta: call with >= 9 threads behind a barrier that follows the writes to theta
+__device__ __forceinline__ void lm_write_K(const LmParams& p, int tid) {
+    if (p.free4_mask == 0 || tid >= 9) return;
+    const int i = tid == 0 ? 0 : (tid == 1 ? 4 : (tid == 2 ? 2 : (tid == 3 ? 5 : -1)));
+    const int rest = tid == 4 ? 1 : (tid == 5 ? 3 : tid);
+    if (i >= 0)
+        p.K[i] = lm_intrinsics_entry(p.K0, p.theta[tid], tid, p.H, p.W);
+    else
+        p.K[rest] = p.K0[rest];
+}
+
+__device__ __forceinline__ bool lm_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// the spacing of float32 at |x| (numpy.spacing of the float32), from the exponent bits: exact, no denormal arithmetic
+__device__ __forceinline__ double lm_spacing_f32(float x) {
+    const int e = (__float_as_int(x) >> 23) & 0xff;
+    return ldexp(1.0, (e == 0 ? 1 : e) - 150);
+}
+
+__global__ void __launch_bounds__(64) lm_update_kernel(const double* __restrict__ info, const double* __restrict__ grad,
+                                                       const long long* __restrict__ count, const float* __restrict__ loss,
+                                                       int B, int N, LmParams p, double ftol, double lambda_max, int finalize,
+                                                       double* __restrict__ st, double* __restrict__ log, int log_rows) {
+    __shared__ double Hm[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];  // the call's sum, then H_acc
+    __shared__ double A[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];   // the scaled, damped system and its factor
+    __shared__ double gv[EHR_LM_MAX_PARAMS], sv[EHR_LM_MAX_PARAMS], yv[EHR_LM_MAX_PARAMS], rv[EHR_LM_MAX_PARAMS],
+        hy[EHR_LM_MAX_PARAMS], dl[EHR_LM_MAX_PARAMS];
+    __shared__ double sh_F, sh_cnt, sh_lambda, sh_nu;
+    __shared__ int sh_accept, sh_fail, sh_small;
+    const int tid = threadIdx.x;
+    double* const th_acc = st + EHR_LM_THETA;
+    double* const H_acc = st + EHR_LM_H;
+    double* const g_acc = st + EHR_LM_G;
+    const bool have = st[EHR_LM_ACCEPTED] > 0.0;  // a point has been accepted
+    if (finalize != 0 || st[EHR_LM_DONE] != 0.0) {  // only restore the accepted parameters
+        if (have && tid < N) lm_param_write(p, tid, (float)th_acc[tid]);
+        __syncthreads();
+        if (have) lm_write_K(p, tid);
+        return;
+    }
+    // 1. the call's sums, in view order
+    int bad = 0;
+    for (int e = tid; e < N * N; e += 64) {
+        const int r = e / N, c = e - r * N;
+        double s = 0.0;
+        for (int b = 0; b < B; b++) s += info[((size_t)b * N + r) * N + c];
+        Hm[r][c] = s;
+        bad |= !lm_finite(s);
+    }
+    if (tid < N) {
+        double s = 0.0;
+        for (int b = 0; b < B; b++) s += grad[(size_t)b * N + tid];
+        gv[tid] = s;
+        bad |= !lm_finite(s);
+    }
+    if (tid == 0) {
+        double s = 0.0, c = 0.0;
+        for (int b = 0; b < B; b++) {
+            s += (double)loss[b];
+            bad |= count[b] < 0;
+            c += (double)count[b];
+        }
+        bad |= !lm_finite(s);
+        sh_F = s;
+        sh_cnt = c;
+    }
+    const int it = (int)st[EHR_LM_ITERATIONS];
+    double* const row = (log && it < log_rows) ? log + (size_t)it * 4 : nullptr;  // (thread 0's)
+    bad = __syncthreads_or(bad);
+    // 2. a reported call: the trial is discarded, nothing else moves
+    if (bad) {
+        if (have && tid < N) lm_param_write(p, tid, (float)th_acc[tid]);
+        if (tid == 0) {
+            st[EHR_LM_REPORTED] += 1.0;
+            st[EHR_LM_ITERATIONS] = (double)(it + 1);
+            st[EHR_LM_LAST] = -1.0;
+            if (row) {
+                row[0] = __longlong_as_double(0x7ff8000000000000ll);
+                row[1] = -1.0;
+                row[2] = st[EHR_LM_LAMBDA];
+                row[3] = __longlong_as_double(0x7ff8000000000000ll);
+            }
+        }
+        __syncthreads();
+        if (have) lm_write_K(p, tid);
+        return;
+    }
+    // 3. accept or reject
+    if (tid == 0) {
+        const double F = sh_F, F_acc = st[EHR_LM_F];
+        double lambda = st[EHR_LM_LAMBDA], nu = st[EHR_LM_NU], rho = 0.0;
+        const int accept = !have || F < F_acc;
+        if (accept) {
+            if (have) {
+                rho = (F_acc - F) / st[EHR_LM_PRED];
+                const double t = 2.0 * rho - 1.0;
+                lambda *= fmax(1.0 / 3.0, 1.0 - t * t * t);
+            }
+            nu = 2.0;
+            st[EHR_LM_F] = F;
+            st[EHR_LM_COUNT] = sh_cnt;
+            st[EHR_LM_RHO] = rho;
+            st[EHR_LM_ACCEPTED] += 1.0;
+        } else {
+            lambda *= nu;
+            nu *= 2.0;
+            st[EHR_LM_REJECTED] += 1.0;
+        }
+        st[EHR_LM_ITERATIONS] = (double)(it + 1);
+        st[EHR_LM_LAST] = accept ? 1.0 : 0.0;
+        st[EHR_LM_F_TRIAL] = F;
+        sh_accept = accept;
+        sh_lambda = lambda;
+        sh_nu = nu;
+        if (row) {
+            row[0] = F;
+            row[1] = accept ? 1.0 : 0.0;
+            row[3] = accept ? rho : __longlong_as_double(0x7ff8000000000000ll);
+        }
+    }
+    __syncthreads();
+    if (sh_accept) {
+        for (int e = tid; e < N * N; e += 64) {
+            const int r = e / N, c = e - r * N;
+            H_acc[r * EHR_LM_MAX_PARAMS + c] = Hm[r][c];
+        }
+        if (tid < N) {
+            g_acc[tid] = gv[tid];
+            th_acc[tid] = (double)lm_param_read(p, tid);
+        }
+    } else {  // the stored linearisation: the inputs of this call are not read again
+        for (int e = tid; e < N * N; e += 64) {
+            const int r = e / N, c = e - r * N;
+            Hm[r][c] = H_acc[r * EHR_LM_MAX_PARAMS + c];
+        }
+        if (tid < N) gv[tid] = g_acc[tid];
+    }
+    __syncthreads();
+    // 4. (H_acc + lambda D) delta = -g_acc / 2, D = diag H_acc, on the scaled system  (S H S + lambda I) y = -S g / 2,
+    //    S = D^-1/2, delta = S y; a parameter whose diagonal entry is <= 0 is left out
+    if (tid < N) {
+        const double d = Hm[tid][tid];
+        sv[tid] = d > 0.0 ? 1.0 / sqrt(d) : 0.0;
+    }
+    __syncthreads();
+    int retries = 0;
+    for (;;) {
+        const double lambda = sh_lambda;
+        for (int e = tid; e < N * N; e += 64) {
+            const int r = e / N, c = e - r * N;
+            double a = Hm[r][c] * sv[r] * sv[c];
+            if (r == c) a = sv[r] > 0.0 ? a + lambda : 1.0;
+            A[r][c] = a;
+        }
+        if (tid < N) rv[tid] = -0.5 * gv[tid] * sv[tid];
+        if (tid == 0) sh_fail = 0;
+        __syncthreads();
+        for (int j = 0; j < N; j++) {  // Cholesky, right-looking, the lower triangle in place
+            if (tid == 0) {
+                double piv = A[j][j];
+                if (!(piv > 0.0) || !lm_finite(piv)) {
+                    sh_fail = 1;
+                    piv = 1.0;
+                }
+                A[j][j] = sqrt(piv);
+            }
+            __syncthreads();
+            if (tid > j && tid < N) A[tid][j] = A[tid][j] / A[j][j];
+            __syncthreads();
+            if (tid > j && tid < N)
+                for (int k = j + 1; k <= tid; k++) A[tid][k] -= A[tid][j] * A[k][j];
+            __syncthreads();
+        }
+        if (!sh_fail || retries >= EHR_LM_MAX_RETRIES) break;
+        retries++;
+        __syncthreads();
+        if (tid == 0) {  // a non-positive pivot: raise lambda like a rejection and factor again
+            sh_lambda *= sh_nu;
+            sh_nu *= 2.0;
+        }
+        __syncthreads();
+    }
+    if (sh_fail) {  // the factorisation keeps failing: stop on the accepted point
+        if (tid < N) lm_param_write(p, tid, (float)th_acc[tid]);
+        if (tid == 0) {
+            st[EHR_LM_LAMBDA] = sh_lambda;
+            st[EHR_LM_NU] = sh_nu;
+            st[EHR_LM_RETRIES] += (double)retries;
+            st[EHR_LM_DONE] = 1.0;
+            st[EHR_LM_WHY] = 4.0;
+            if (row) row[2] = sh_lambda;
+        }
+        __syncthreads();
+        lm_write_K(p, tid);
+        return;
+    }
+    for (int j = 0; j < N; j++) {  // L z = r
+        if (tid == 0) yv[j] = rv[j] / A[j][j];
+        __syncthreads();
+        if (tid > j && tid < N) rv[tid] -= A[tid][j] * yv[j];
+        __syncthreads();
+    }
+    for (int j = N - 1; j >= 0; j--) {  // L^T y = z
+        if (tid == 0) yv[j] = yv[j] / A[j][j];
+        __syncthreads();
+        if (tid < j) yv[tid] -= A[j][tid] * yv[j];
+        __syncthreads();
+    }
+    if (tid < N) {
+        double s = 0.0;
+        for (int c = 0; c < N; c++) s += (Hm[tid][c] * sv[tid] * sv[c]) * yv[c];
+        hy[tid] = s;
+        dl[tid] = yv[tid] * sv[tid];
+        st[EHR_LM_DELTA + tid] = dl[tid];
+    }
+    __syncthreads();
+    // 5, 6. the predicted reduction, the stopping rule, the next trial
+    if (tid == 0) {
+        const double lambda = sh_lambda;
+        double pred = 0.0;
+        for (int k = 0; k < N; k++) pred += yv[k] * hy[k] + 2.0 * lambda * (yv[k] * yv[k]);
+        int small = 1;
+        for (int k = 0; k < N; k++) small = small && (dl[k] == 0.0 || fabs(dl[k]) < lm_spacing_f32((float)th_acc[k]));
+        int why = 0;
+        if (pred <= ftol * st[EHR_LM_F])
+            why = 1;
+        else if (lambda >= lambda_max)
+            why = 2;
+        else if (small)
+            why = 3;
+        st[EHR_LM_LAMBDA] = lambda;
+        st[EHR_LM_NU] = sh_nu;
+        st[EHR_LM_PRED] = pred;
+        st[EHR_LM_RETRIES] += (double)retries;
+        if (why) {
+            st[EHR_LM_DONE] = 1.0;
+            st[EHR_LM_WHY] = (double)why;
+        }
+        if (row) row[2] = lambda;
+        sh_small = why;
+    }
+    __syncthreads();
+    if (tid < N) lm_param_write(p, tid, sh_small ? (float)th_acc[tid] : (float)(th_acc[tid] + dl[tid]));
+    __syncthreads();
+    lm_write_K(p, tid);
+}
+
+}  // namespace ehr
+
+using namespace ehr;
+
+extern "C" {
+
+int ehr_lm_linearize(const float* dof, const float* K, const float* link_poses, int B, int L, int H, int W, float near_plane,
+                     float far_plane, const float* joint_frames, const uint32_t* upstream, const int32_t* joint_kind,
+                     const int32_t* free_list, int F, int J, int free4_mask, int tie_focal, int N, float* mvp, float* dmvp,
+                     void* stream) {
+    if (!dof || !K || !link_poses || !mvp || !dmvp) return fail(EHR_ERR_INVALID, "ehr_lm_linearize: NULL tensor");
+    if (F < 0 || (F > 0 && (!joint_frames || !upstream || !joint_kind || !free_list || J < 1 || J > 32)))
+        return fail(EHR_ERR_INVALID, "ehr_lm_linearize: free joints need joint_frames, upstream, joint_kind and the list (J %d <= 32)", J);
+    int Fi = 0;
+    if (free4_mask < 0 || free4_mask > 15 || (tie_focal != 0 && (free4_mask & 3) != 3))
+        return fail(EHR_ERR_INVALID, "ehr_lm_linearize: bad free intrinsics (mask %d, tie_focal %d)", free4_mask, tie_focal);
+    for (int i = 0; i < 4; i++) Fi += (free4_mask >> i) & 1;
+    if (tie_focal != 0) Fi -= 1;
+    if (N != 6 + F + Fi || N > EHR_LM_MAX_PARAMS)
+        return fail(EHR_ERR_INVALID, "ehr_lm_linearize: N %d is not 6 + %d free joints + %d free intrinsics, or exceeds %d", N, F,
+                    Fi, EHR_LM_MAX_PARAMS);
+    if (B < 1 || L < 1 || H < 1 || W < 1 || (long long)B * L * (N + 1) > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID, "ehr_lm_linearize: bad sizes (B %d, L %d, H %d, W %d)", B, L, H, W);
+    const long long total = (long long)B * L * (N + 1);
+    lm_linearize_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        dof, K, link_poses, B, L, H, W, near_plane, far_plane, joint_frames, upstream, joint_kind, free_list, F, J, free4_mask,
+        tie_focal, N, mvp, dmvp);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_lm_update(const double* info, const double* grad, const long long* count, const float* loss, int B, int N, float* dof,
+                  float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask, int tie_focal,
+                  const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                  void* stream) {
+    if (!info || !grad || !count || !loss || !dof || !state) return fail(EHR_ERR_INVALID, "ehr_lm_update: NULL tensor");
+    if (F < 0 || (F > 0 && (!offset || !free_list || J < 1 || J > 32)))
+        return fail(EHR_ERR_INVALID, "ehr_lm_update: free joints need offset and the list (J %d <= 32)", J);
+    if (free4_mask < 0 || free4_mask > 15 || (tie_focal != 0 && (free4_mask & 3) != 3) ||
+        (free4_mask != 0 && (!theta || !K0 || !K || H < 1 || W < 1)))
+        return fail(EHR_ERR_INVALID, "ehr_lm_update: bad free intrinsics (mask %d, tie_focal %d), or no theta / K0 / K", free4_mask,
+                    tie_focal);
+    int Fi = 0;
+    for (int i = 0; i < 4; i++) Fi += (free4_mask >> i) & 1;
+    if (tie_focal != 0) Fi -= 1;
+    // (N < 6 without free joints or intrinsics: the first N pose coordinates alone)
+    if ((N != 6 + F + Fi && !(F == 0 && Fi == 0 && N >= 1 && N < 6)) || N > EHR_LM_MAX_PARAMS || B < 1)
+        return fail(EHR_ERR_INVALID, "ehr_lm_update: N %d is not 6 + %d free joints + %d free intrinsics, or exceeds %d (B %d)", N, F,
+                    Fi, EHR_LM_MAX_PARAMS, B);
+    LmParams p = {dof, offset, free_list, F, J, theta, free4_mask, tie_focal, K0, K, H, W};
+    lm_update_kernel<<<1, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize, state,
+                                                       log && log_rows > 0 ? log : nullptr, log_rows);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,232 @@
+"""Levenberg-Marquardt on the information matrix of the mask loss (``ehr_lm_linearize`` / ``ehr_lm_update`` in
+include/ehr.h, csrc/ehr_lm.hip).
+
+Every solve of this package is first-order Adam with a learning rate per parameter group.  ``ehr_mask_information`` gives,
+for any parameters, the Gauss-Newton matrix, the gradient and the loss of the fused mask loss in one stream-ordered call;
+:class:`LevenbergMarquardt` turns that into a damped Gauss-Newton iteration that runs on the device without a host round trip
+
+    [ehr_joint_forward, if joints are free]  ->  ehr_lm_linearize  ->  ehr_mask_information  ->  ehr_lm_update
+
+on an existing step object's own context, plan, bound reference, weights and parameter tensors: scale-free (no learning rate
+per group), monotone (a trial is kept only if its loss is strictly lower) and self-stopping.  The matrix it ends on is the
+information matrix at the solution, so :func:`solve_lm` returns the :class:`easyhec_amd.information.InformationReport` of the
+accepted point without another call.
+
+It is a refinement BESIDE Adam, not a new default: it does not touch Adam's moments, step counters or ``history_ops``, has no
+weight decay (no prior towards the given intrinsics or zero offsets), and far from the optimum its quadratic model is poor
+(the squared error of binary silhouettes is linear in the displacement): the accept / reject rule, not the model, makes it
+safe.  It renders the float32 matrix ``ehr_pose_forward`` builds -- the loss it minimises is the loss the Adam solve reports,
+bit for bit -- where :func:`easyhec_amd.information.information_of` renders a float64-built one.  HIP only; no fallback."""
+import ctypes
+import types
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import _lib, fused, information
+
+__all__ = ["LevenbergMarquardt", "LmResult", "solve_lm", "WHY"]
+
+WHY = {0: "running", 1: "ftol: the predicted reduction is below ftol * loss", 2: "lambda_max: the damping reached its limit",
+       3: "step: every parameter's step is below float32's spacing", 4: "factorisation: the damped matrix kept failing to factor"}
+
+
+def _refuse(step):
+    """The steps the iteration cannot drive, each with its reason (worded like ``information._refuse``)."""
+    from .multistart import MultiStartPoseStep
+    from .rig_calib import RigJointStep
+    if isinstance(step, MultiStartPoseStep):
+        raise ValueError("solve_lm: not available for the multi-start step: its hypotheses are separate solves; ask for the "
+                         "winner's FusedPoseStep")
+    if isinstance(step, RigJointStep):
+        raise ValueError("solve_lm: not available for a rig: it is one system over several contexts (out of scope); the "
+                         "cameras' matrices are rig_information(rig_step)'s")
+    if getattr(step, "distributed", False) or getattr(step, "rccl", False) or getattr(step, "p2p", False):
+        raise ValueError("solve_lm: not available for a data-parallel job: each rank holds its own views, and the matrices "
+                         "are not exchanged")
+    for attr in ("glctx", "scene", "ref", "link_poses", "K", "model"):
+        if not hasattr(step, attr):
+            raise TypeError(f"solve_lm: {type(step).__name__} is not a launch-chain step (FusedPoseStep, JointPoseStep, "
+                            "IntrinsicsPoseStep, JointIntrinsicsPoseStep)")
+    if step.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("solve_lm: not available while a graph is being captured: ehr_mask_information sizes its scratch "
+                           "on the first call")
+    if not _lib.has_lm():
+        raise RuntimeError("this libehr_hip.so has no Levenberg-Marquardt kernels (ehr_lm_linearize): rebuild it")
+    if not _lib.has_information():
+        raise RuntimeError("this libehr_hip.so has no information kernel (ehr_mask_information): rebuild it")
+
+
+class LevenbergMarquardt:
+    """Drives ``step`` (``FusedPoseStep``, ``JointPoseStep``, ``IntrinsicsPoseStep`` or ``JointIntrinsicsPoseStep``) by
+    Levenberg-Marquardt iterations on the parameters it optimises, in the order of
+    :func:`easyhec_amd.information.information_of` (``names``).  ``lambda0``, ``ftol``, ``lambda_max``: the damping's start,
+    and the stopping rule's two thresholds (include/ehr.h, ``ehr_lm_update``); ``log_rows``: iterations the device log holds.
+
+    ``iterate(n)`` enqueues n iterations and never synchronises; ``state()`` makes one small copy; ``finalize()`` leaves the
+    accepted parameters in the step's tensors (a trial is in them between iterations)."""
+
+    def __init__(self, step, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256):
+        _refuse(step)
+        self.step, self.dev = step, step.dev
+        self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
+        dev = self.dev
+        self.names = [f"dof[{i}]" for i in range(6)]
+        kin = getattr(step, "kinematics", None)
+        self.kin = kin
+        free = list(step.free_joints) if kin is not None else []
+        self.F, self.J = len(free), (kin.J if kin is not None else 0)
+        self.free_list = torch.tensor(free, dtype=torch.int32, device=dev) if free else None
+        self.names += [f"offset[{j}]" for j in free]
+        self.free4_mask, self.tie_focal = 0, 0
+        if hasattr(step, "free_intrinsics"):
+            from .intrinsics_calib import _parse_free
+            mask, self.tie_focal, nm = _parse_free(step.free_intrinsics)
+            self.free4_mask = sum(1 << i for i in range(4) if mask[i])
+            self.names += [f"theta[{n}]" for n in nm]
+        self.N = N = len(self.names)
+        if N > _lib.LM_MAX_PARAMS:
+            raise ValueError(f"solve_lm: the step optimises {N} parameters; the kernels take {_lib.LM_MAX_PARAMS}")
+        B, L = step.B, step.L
+        self.mvp = torch.empty((B, L, 4, 4), device=dev)
+        self.dmvp = torch.empty((N, B, L, 4, 4), device=dev)
+        self.out = information._outputs(N, B, L, dev, True, False)
+        st = np.zeros(_lib.LM_STATE_DOUBLES)
+        st[_lib.LM_STATE["lambda"]], st[_lib.LM_STATE["nu"]] = self.lambda0, 2.0
+        self.state_block = torch.from_numpy(st).to(dev)
+        self.log_rows = int(log_rows)
+        self.log = torch.full((self.log_rows, 4), float("nan"), dtype=torch.float64, device=dev)
+
+    # -- guards: the context is shared state; never iterate on a plan or on weights that are not the step's ------------------
+    def _guard(self):
+        st = self.step
+        plan = getattr(st.glctx, "_plan", None)
+        if plan is None or plan.key != fused._plan_key(st.scene, st.B, st.H, st.W):
+            raise RuntimeError("solve_lm: the step's context holds another plan (somebody else rendered with it): take a "
+                               "step first, which plans and binds again")
+        if getattr(st.glctx, "_bound_weight", None) is not getattr(st, "weight", None):
+            raise RuntimeError("solve_lm: the weights bound to the step's context are not the step's (somebody else used "
+                               "the context): take a step first, which binds them again")
+        if st.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("solve_lm: not available while a graph is being captured")
+
+    def _linearize(self, stream):
+        st, kin = self.step, self.kin
+        _lib.check(_lib.lib().ehr_lm_linearize(
+            _lib.ptr(st.model.dof.data), _lib.ptr(st.K), _lib.ptr(st.link_poses), st.B, st.L, st.H, st.W,
+            ctypes.c_float(st.near), ctypes.c_float(st.far), _lib.ptr(st.joint_frames if self.F else None),
+            _lib.ptr(kin.upstream if self.F else None), _lib.ptr(kin.jkind if self.F else None), _lib.ptr(self.free_list),
+            self.F, self.J, self.free4_mask, self.tie_focal, self.N, _lib.ptr(self.mvp), _lib.ptr(self.dmvp), stream),
+            "ehr_lm_linearize")
+
+    def _update(self, stream, finalize=0):
+        st, o = self.step, self.out
+        intr = self.free4_mask != 0
+        _lib.check(_lib.lib().ehr_lm_update(
+            _lib.ptr(o.info), _lib.ptr(o.grad), _lib.ptr(o.count), _lib.ptr(o.loss), st.B, self.N, _lib.ptr(st.model.dof.data),
+            _lib.ptr(st.offsets if self.F else None), _lib.ptr(self.free_list), self.F, self.J,
+            _lib.ptr(st.theta if intr else None), self.free4_mask, self.tie_focal, _lib.ptr(st.K0 if intr else None),
+            _lib.ptr(st.K if intr else None), st.H, st.W, ctypes.c_double(self.ftol), ctypes.c_double(self.lambda_max),
+            int(finalize), _lib.ptr(self.state_block), _lib.ptr(self.log), self.log_rows, stream), "ehr_lm_update")
+
+    def _forward_kinematics(self, stream):
+        if self.kin is not None:
+            self.kin.launch(self.step, stream)
+
+    def iterate(self, n=1):
+        """Enqueue ``n`` iterations on the current stream; never synchronises.  After ``done`` an iteration only restores the
+        accepted parameters."""
+        self._guard()
+        st, o = self.step, self.out
+        with torch.cuda.device(self.dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for _ in range(int(n)):
+                self._forward_kinematics(stream)
+                self._linearize(stream)
+                information._launch(st.glctx, st.scene, self.mvp, self.dmvp, st.ref, o.info, o.grad, o.count, o.loss, None)
+                self._update(stream)
+        return self
+
+    def finalize(self):
+        """Leave the ACCEPTED parameters in the step's tensors (``model.dof``, the offsets, ``theta`` and ``K``; the link
+        poses follow the offsets).  Enqueued; never synchronises."""
+        with torch.cuda.device(self.dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._update(stream, finalize=1)
+            self._forward_kinematics(stream)
+        return self
+
+    def state(self):
+        """The state block as a namespace (one small copy; synchronises): lambda, nu, F_acc, pred, rho, F_trial, the counters
+        iterations / accepted / rejected / reported / retries, done, why, last, count, and theta [N], delta [N], g [N],
+        H [N,N] of the accepted point."""
+        s = self.state_block.cpu().numpy()
+        N = self.N
+        ns = types.SimpleNamespace(**{k: float(s[i]) for k, i in _lib.LM_STATE.items()})
+        for k in ("iterations", "accepted", "rejected", "reported", "done", "why", "last", "count", "retries"):
+            setattr(ns, k, int(getattr(ns, k)))
+        ns.theta = s[_lib.LM_THETA:_lib.LM_THETA + N].copy()
+        ns.delta = s[_lib.LM_DELTA:_lib.LM_DELTA + N].copy()
+        ns.g = s[_lib.LM_G:_lib.LM_G + N].copy()
+        ns.H = s[_lib.LM_H:_lib.LM_H + 32 * 32].reshape(32, 32)[:N, :N].copy()
+        ns.raw = s
+        return ns
+
+    def trajectory(self):
+        """[iterations, 4] float64 (CPU): per iteration the trial's loss (NaN: reported), 1 accepted / 0 rejected / -1
+        reported, lambda after the iteration, and the gain ratio rho (NaN unless accepted).  Synchronises."""
+        n = min(int(self.state_block[_lib.LM_STATE["iterations"]].item()), self.log_rows)
+        return self.log[:n].cpu().numpy()
+
+    def report(self, state=None):
+        """The :class:`easyhec_amd.information.InformationReport` of the accepted point, from the state block alone."""
+        s = self.state() if state is None else state
+        return information.InformationReport(s.H[None], self.names, s.g[None], [s.count], [s.F_acc])
+
+
+@dataclass
+class LmResult:
+    loss: float                 # F_acc: the summed per-view loss at the accepted point
+    iterations: int
+    accepted: int
+    rejected: int
+    reported: int
+    done: bool
+    why: str                    # the reason it stopped ("max_iters" where it did not stop by itself)
+    trajectory: np.ndarray      # [iterations,4]: loss, accepted flag, lambda, rho per iteration
+    report: object              # InformationReport at the accepted point
+    recoveries: list = field(default_factory=list)
+    state: object = None        # the final state namespace
+    lm: object = None           # the LevenbergMarquardt object
+
+
+def solve_lm(step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6):
+    """Levenberg-Marquardt on ``step``'s parameters from where they are: at most ``max_iters`` EFFECTIVE iterations (a
+    reported one -- the plan's job slots overflowed, the view needs the general-triangle pass -- is recovered from the way
+    ``_ChainStep`` recovers a step, and taken again), ``done`` polled every ``check_every`` iterations.  Ends with the accepted
+    parameters in the step's tensors; a captured chain stays valid.  Returns an :class:`LmResult`."""
+    lm = LevenbergMarquardt(step, lambda0=lambda0, ftol=ftol, lambda_max=lambda_max, log_rows=max_iters + 4 * check_every + 8)
+    recoveries, rounds, seen = [], 0, 0
+    while True:
+        s = lm.state()
+        if s.reported > seen:
+            seen = s.reported
+            what = step.recover_from_overflow() if hasattr(step, "recover_from_overflow") else False
+            if what:
+                recoveries.append(what)
+                if hasattr(step, "recoveries"):
+                    step.recoveries.append(what)
+            rounds += 1
+            if rounds > 4:
+                fused.check_status(step.glctx)
+                raise RuntimeError("solve_lm: iterations keep being reported as not taken (NaN loss)")
+        effective = s.iterations - s.reported
+        if s.done or effective >= max_iters:
+            break
+        lm.iterate(min(check_every, max_iters - effective))
+    lm.finalize()
+    s = lm.state()
+    why = WHY[s.why].split(":")[0] if s.done else "max_iters"
+    return LmResult(s.F_acc, s.iterations, s.accepted, s.rejected, s.reported, bool(s.done), why, lm.trajectory(),
+                    lm.report(s), recoveries, s, lm)

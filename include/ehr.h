@@ -511,6 +511,80 @@ int ehr_intrinsics_backward_adam(const float* grad_mvp, const float* tc_jac, con
                                  float* theta, float* adam_m, float* adam_v, int32_t* step_k, float lr, float beta1,
                                  float beta2, float eps, float weight_decay, float* K, float* grad_out, void* stream);
 
+/* Levenberg-Marquardt on the information matrix: a damped Gauss-Newton solve of the fused mask loss whose iteration is
+ *     [ehr_joint_forward, if joints are free] -> ehr_lm_linearize -> ehr_mask_information -> ehr_lm_update      on one stream,
+ * with no host round trip: the state of the solve lives in a device block (below).  Both calls take device pointers only, never
+ * allocate or synchronise and launch on `stream`.  Adam's moments, its step counters and the pose history are not touched, and
+ * there is no weight decay: this is a refinement beside the Adam solves, not a replacement.
+ * The N <= EHR_LM_MAX_PARAMS parameters are ordered as easyhec_amd.information.information_of orders them: dof[0..5], then
+ * offset[free_list[0..F)], then the free intrinsics in the order f (tie_focal: theta[0] and theta[1] as one) | fx, fy, then cx, cy;
+ * free4_mask has bit i set where theta[i] is free (tie_focal needs bits 0 and 1), and N = 6 + F + Fi.
+ *   ehr_lm_linearize : mvp [B,L,16] = ehr_pose_forward's, bit for bit (the same device functions: the solve minimises exactly the
+ *                      loss the Adam solve reports), and dmvp [N,B,L,16] = d MVP[b,l] / d parameter k, evaluated in float64 at
+ *                      the float32 inputs and rounded once.  With PF = proj(K) @ diag(1,-1,-1,1) and K as rendered:
+ *                          pose        PF @ (d Tc / d dof_i) @ link_poses[b,l]        (the exponential map's partials in float64)
+ *                          offset j    PF @ Tc @ D_blj, D as for ehr_joint_backward_adam; exactly zero where bit j of
+ *                                      upstream[l] is clear.  joint_frames, upstream, joint_kind: ehr_joint_forward's / the table's
+ *                          intrinsics  (d proj / d theta_i) @ diag(1,-1,-1,1) @ Tc @ link_poses[b,l]: the derivatives that s0..s3 of
+ *                                      ehr_intrinsics_backward_adam imply (2 fu / W, 2 fv / H, -2, 2), fu, fv = K[0], K[4];
+ *                                      tie_focal: the sum of the two focal tangents.
+ *                      One thread per (k, b, l) matrix.  F == 0: the joint pointers may be NULL.
+ *   ehr_lm_update    : one workgroup, float64, fixed order, no atomics.  info [B,N,N], grad [B,N], count [B], loss [B]: the outputs
+ *                      of ehr_mask_information at the trial the previous call wrote.  In order:
+ *                      1. H = sum_b info[b], g = sum_b grad[b], F = sum_b (double) loss[b], in view order.
+ *                      2. Any non-finite sum or a count < 0 (a REPORTED call): the accepted parameters are written back,
+ *                         `reported` is incremented, nothing else moves -- the next iteration renders the accepted point again.
+ *                      3. The first call accepts unconditionally; later ones iff F < F_acc.  Accept: the parameters (read back
+ *                         through the pointers), F, H, g and the pixel count are stored, rho = (F_acc - F) / pred,
+ *                         lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2.  Reject: lambda *= nu, nu *= 2, H_acc and g_acc stay
+ *                         (the call's inputs are not read again).
+ *                      4. (H_acc + lambda D) delta = -g_acc / 2, D = diag H_acc, solved as the scaled system
+ *                         (S H_acc S + lambda I) y = -S g_acc / 2, S = D^-1/2, delta = S y, by a Cholesky factorisation.  A
+ *                         parameter whose diagonal entry is <= 0 is left out (delta = 0).  A non-positive pivot raises lambda
+ *                         like a rejection and factors again, 8 times at the most (`retries`); then done with why = 4.
+ *                         pred = delta^T H_acc delta + 2 lambda delta^T D delta  >= 0  (from F(theta + delta) ~ F + g^T delta +
+ *                         delta^T H delta with the op's conventions).
+ *                      5. The stopping rule: pred <= ftol F_acc (why 1), else lambda >= lambda_max (2), else every |delta_k| is
+ *                         zero or below the float32 spacing at the accepted parameter (3).  It sets `done`; the accepted
+ *                         parameters are written back, and every later call only does that.  finalize != 0 does it on request.
+ *                      6. Otherwise the trial fl32(theta_acc + delta) is written through dof, offset and theta; where intrinsics
+ *                         are free, K is rewritten from theta by the "writing K" rule of ehr_intrinsics_backward_adam.
+ *                      N < 6 is accepted where nothing but the pose is free: the first N pose coordinates alone.
+ *                      log (may be NULL): [log_rows,4] float64; the call that is iteration i < log_rows writes row i =
+ *                      {F (NaN: reported), 1 accepted / 0 rejected / -1 reported, lambda after the call, rho (NaN unless accepted)}.
+ * The state block: EHR_LM_STATE_DOUBLES float64 (counters and flags are whole numbers, the accepted parameters float32 values,
+ * both held exactly).  The caller clears it and sets EHR_LM_LAMBDA (lambda_0) and EHR_LM_NU (2) before the first call.
+ * ehr_version() is unchanged: the presence of these symbols is the capability check. */
+#define EHR_LM_MAX_PARAMS 32
+#define EHR_LM_LAMBDA 0      /* the damping */
+#define EHR_LM_NU 1          /* its growth factor on the next rejection */
+#define EHR_LM_F 2           /* F_acc: the loss at the accepted point */
+#define EHR_LM_PRED 3        /* predicted reduction of the last solve */
+#define EHR_LM_RHO 4         /* gain ratio of the last acceptance */
+#define EHR_LM_F_TRIAL 5     /* the loss of the last trial that was not reported */
+#define EHR_LM_ITERATIONS 6  /* calls that were iterations: accepted + rejected + reported */
+#define EHR_LM_ACCEPTED 7
+#define EHR_LM_REJECTED 8
+#define EHR_LM_REPORTED 9
+#define EHR_LM_DONE 10
+#define EHR_LM_WHY 11        /* 1 ftol, 2 lambda_max, 3 step below float32's spacing, 4 the factorisation kept failing */
+#define EHR_LM_LAST 12       /* the last iteration: 1 accepted, 0 rejected, -1 reported */
+#define EHR_LM_COUNT 13      /* sum_b count[b] at the accepted point */
+#define EHR_LM_RETRIES 14    /* non-positive pivots met so far */
+#define EHR_LM_THETA 16      /* [32] the accepted parameters */
+#define EHR_LM_DELTA 48      /* [32] the last delta */
+#define EHR_LM_G 80          /* [32] g_acc */
+#define EHR_LM_H 112         /* [32][32] H_acc, row stride 32 */
+#define EHR_LM_STATE_DOUBLES 1136
+int ehr_lm_linearize(const float* dof, const float* K, const float* link_poses, int B, int L, int H, int W, float near_plane,
+                     float far_plane, const float* joint_frames, const uint32_t* upstream, const int32_t* joint_kind,
+                     const int32_t* free_list, int F, int J, int free4_mask, int tie_focal, int N, float* mvp, float* dmvp,
+                     void* stream);
+int ehr_lm_update(const double* info, const double* grad, const long long* count, const float* loss, int B, int N, float* dof,
+                  float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask, int tie_focal,
+                  const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state,
+                  double* log, int log_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
