@@ -59,6 +59,20 @@ MEASURED = {
     "test_fused_matches_oracle 120x160": 0.660, "test_fused_matches_oracle 480x640": 1.763,
     "test_fused_matches_oracle 100x150": 0.963, "span walker": 0.300,
 }
+# The scenes of tests/link_scenes.py (link counts 1 .. 32, ragged links, sub-tile images), MI355X, 2026-10-19, printed under
+#     pytest -m gpu tests/test_gpu_link_scenes.py -s
+# (uniform reference unless named; stateless and bound form bit-equal).  Larger than the robots' figures -- up to 5 units, and
+# 11 on the 7 x 31 image, the largest of the suite -- and still a quarter of the derived bar.
+MEASURED.update({
+    "link scene full32": 2.635, "link scene full32 binary": 3.738, "link scene full32 wide": 1.775,
+    "link scene full32_lazy": 1.777, "link scene units512": 4.044, "link scene units513": 3.581, "link scene prime7": 2.883,
+    "link scene first_empty": 2.030, "link scene last_empty": 1.186, "link scene only_one_live": 1.813,
+    "link scene L13x5": 3.368, "link scene L2": 0.550, "link scene L3": 0.548, "link scene L5": 1.324, "link scene L13": 2.740,
+    "link scene L17": 4.928, "link scene L31": 1.791, "link scene sub_1x1": 0.000, "link scene sub_1x40": 0.659,
+    "link scene sub_3x5": 0.403, "link scene sub_7x31": 11.066, "link scene sub_8x32": 4.011, "link scene sub_9x33": 1.147,
+    "link scene sub_5x70": 3.739, "link scene sub_40x4": 1.003, "link scene full32 weights speckle": 1.998,
+    "link scene full32 weights tiles": 2.405, "solver step link scene full32": 2.063, "solver step link scene L13": 2.971,
+})
 
 
 def block_bar(A):
