@@ -15,4 +15,8 @@ def __getattr__(name):
     if name in ("LevenbergMarquardt", "solve_lm", "LmResult"):
         from . import lm
         return getattr(lm, name)
+    # information-gain exploration (easyhec_amd/info_explorer.py), likewise
+    if name in ("InformationExplorer", "information_gain", "greedy_select"):
+        from . import info_explorer
+        return getattr(info_explorer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -86,6 +86,8 @@ SIGNATURES = {
     "ehr_lm_linearize": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3),
     "ehr_lm_update": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 +
                       [c_void_p] * 2 + [c_int] * 2 + [ctypes.c_double] * 2 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p]),
+    "ehr_information_gain": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_double, ctypes.c_uint32, c_void_p, c_void_p]),
+    "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
 }
 
 
@@ -171,6 +173,18 @@ def has_lm():
         return False
     l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
     return hasattr(l, "ehr_lm_linearize") and hasattr(l, "ehr_lm_update")
+
+
+def has_information_gain():
+    """True if the library has the exploration kernels (``ehr_information_gain`` / ``ehr_information_pick``); the symbols'
+    presence is the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
+    return hasattr(l, "ehr_information_gain") and hasattr(l, "ehr_information_pick")
+
+
+IG_MAX_PARAMS = 32  # include/ehr.h: EHR_IG_MAX_PARAMS
 
 
 # the state block of ehr_lm_update (include/ehr.h: EHR_LM_*), in float64 words

@@ -58,6 +58,35 @@ def _refuse(step):
         raise RuntimeError("this libehr_hip.so has no information kernel (ehr_mask_information): rebuild it")
 
 
+def parameter_layout(step):
+    """The parameters ``step`` optimises, in the order of :func:`easyhec_amd.information.information_of`, and what
+    ``ehr_lm_linearize`` needs to know of them: a namespace of ``names``, ``N``, ``kin`` (the step's joint table on the device, or
+    None), ``free`` (the free joints), ``F``, ``J``, ``free4_mask`` and ``tie_focal``."""
+    kin = getattr(step, "kinematics", None)
+    free = list(step.free_joints) if kin is not None else []
+    names = [f"dof[{i}]" for i in range(6)] + [f"offset[{j}]" for j in free]
+    free4_mask, tie_focal = 0, 0
+    if hasattr(step, "free_intrinsics"):
+        from .intrinsics_calib import _parse_free
+        mask, tie_focal, nm = _parse_free(step.free_intrinsics)
+        free4_mask = sum(1 << i for i in range(4) if mask[i])
+        names += [f"theta[{n}]" for n in nm]
+    return types.SimpleNamespace(names=names, N=len(names), kin=kin, free=free, F=len(free), J=kin.J if kin is not None else 0,
+                                 free4_mask=free4_mask, tie_focal=tie_focal)
+
+
+def launch_linearize(step, lay, free_list, link_poses, joint_frames, B, mvp, dmvp, stream):
+    """``ehr_lm_linearize`` at the step's current parameters (``model.dof``, ``K``) for B views given by ``link_poses`` [B,L,4,4]
+    (and ``joint_frames`` [B,J,6] where joints are free; ``free_list``: ``lay.free`` as an int32 device tensor) -> ``mvp``
+    [B,L,4,4], ``dmvp`` [N,B,L,4,4]."""
+    kin, F = lay.kin, lay.F
+    _lib.check(_lib.lib().ehr_lm_linearize(
+        _lib.ptr(step.model.dof.data), _lib.ptr(step.K), _lib.ptr(link_poses), B, step.L, step.H, step.W,
+        ctypes.c_float(step.near), ctypes.c_float(step.far), _lib.ptr(joint_frames if F else None),
+        _lib.ptr(kin.upstream if F else None), _lib.ptr(kin.jkind if F else None), _lib.ptr(free_list),
+        F, lay.J, lay.free4_mask, lay.tie_focal, lay.N, _lib.ptr(mvp), _lib.ptr(dmvp), stream), "ehr_lm_linearize")
+
+
 class LevenbergMarquardt:
     """Drives ``step`` (``FusedPoseStep``, ``JointPoseStep``, ``IntrinsicsPoseStep`` or ``JointIntrinsicsPoseStep``) by
     Levenberg-Marquardt iterations on the parameters it optimises, in the order of
@@ -72,20 +101,11 @@ class LevenbergMarquardt:
         self.step, self.dev = step, step.dev
         self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
         dev = self.dev
-        self.names = [f"dof[{i}]" for i in range(6)]
-        kin = getattr(step, "kinematics", None)
-        self.kin = kin
-        free = list(step.free_joints) if kin is not None else []
-        self.F, self.J = len(free), (kin.J if kin is not None else 0)
-        self.free_list = torch.tensor(free, dtype=torch.int32, device=dev) if free else None
-        self.names += [f"offset[{j}]" for j in free]
-        self.free4_mask, self.tie_focal = 0, 0
-        if hasattr(step, "free_intrinsics"):
-            from .intrinsics_calib import _parse_free
-            mask, self.tie_focal, nm = _parse_free(step.free_intrinsics)
-            self.free4_mask = sum(1 << i for i in range(4) if mask[i])
-            self.names += [f"theta[{n}]" for n in nm]
-        self.N = N = len(self.names)
+        self.layout = lay = parameter_layout(step)
+        self.names, self.kin, self.F, self.J = lay.names, lay.kin, lay.F, lay.J
+        self.free4_mask, self.tie_focal = lay.free4_mask, lay.tie_focal
+        self.free_list = torch.tensor(lay.free, dtype=torch.int32, device=dev) if lay.free else None
+        self.N = N = lay.N
         if N > _lib.LM_MAX_PARAMS:
             raise ValueError(f"solve_lm: the step optimises {N} parameters; the kernels take {_lib.LM_MAX_PARAMS}")
         B, L = step.B, step.L
@@ -112,13 +132,9 @@ class LevenbergMarquardt:
             raise RuntimeError("solve_lm: not available while a graph is being captured")
 
     def _linearize(self, stream):
-        st, kin = self.step, self.kin
-        _lib.check(_lib.lib().ehr_lm_linearize(
-            _lib.ptr(st.model.dof.data), _lib.ptr(st.K), _lib.ptr(st.link_poses), st.B, st.L, st.H, st.W,
-            ctypes.c_float(st.near), ctypes.c_float(st.far), _lib.ptr(st.joint_frames if self.F else None),
-            _lib.ptr(kin.upstream if self.F else None), _lib.ptr(kin.jkind if self.F else None), _lib.ptr(self.free_list),
-            self.F, self.J, self.free4_mask, self.tie_focal, self.N, _lib.ptr(self.mvp), _lib.ptr(self.dmvp), stream),
-            "ehr_lm_linearize")
+        st = self.step
+        launch_linearize(st, self.layout, self.free_list, st.link_poses, st.joint_frames if self.F else None, st.B, self.mvp,
+                         self.dmvp, stream)
 
     def _update(self, stream, finalize=0):
         st, o = self.step, self.out

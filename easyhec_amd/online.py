@@ -3,7 +3,8 @@ replaced by callbacks: per exploration round ``capture_data`` (robot + camera + 
 frame), ``rebuild`` (a fresh RBSolver from the configured initial pose over ALL frames so far, rbsolve_iter.py:277-285),
 ``do_fit`` (``num_epochs`` Adam iterations -- one ``ehr_solver_step`` launch chain each), ``explore_next_state``
 (space_explorer.py:87-96,152-185: sample camera poses from this round's optimisation history, score the candidate joint
-configurations by summed mask variance -- one ``ehr_mask_variance`` call --, move to the best).
+configurations by summed mask variance -- one ``ehr_mask_variance`` call --, move to the best; or, with
+``explore="information"``, by the information gain of easyhec_amd/info_explorer.py).
 
 Robot drivers, RealSense capture, PointRend / SAM segmentation and motion planning are the parts of the reference that
 stay outside this package; they enter as ``capture`` and ``candidates`` callables."""
@@ -13,6 +14,7 @@ import numpy as np
 import torch
 
 from .config import Cfg
+from .info_explorer import InformationExplorer
 from .rb_solver import RBSolver
 from .space_explorer import SpaceExplorer
 from .trainer import RBSolverTrainer
@@ -22,10 +24,16 @@ __all__ = ["OnlineCalibration"]
 
 class OnlineCalibration:
     def __init__(self, robot, K, H, W, init_Tc_c2b, capture, candidates, device="cuda:0", num_epochs=1000,
-                 explore_iters=5, sample=10, start=200, lr=0.003, seed=0):
+                 explore_iters=5, sample=10, start=200, lr=0.003, seed=0, explore="variance"):
         """capture(qpos) -> bool/float mask [H,W] of the robot as the camera sees it at that joint configuration;
         candidates(round) -> (qposes [Q,dof], valid [Q] bool or None): the joint configurations the planner would
-        accept this round (space_explorer.py:98-150 decides that with pymp / SAPIEN in the reference)."""
+        accept this round (space_explorer.py:98-150 decides that with pymp / SAPIEN in the reference).
+        explore: "variance" (the reference's mask-variance score, ``SpaceExplorer``) or "information" (the log-det information
+        gain of :class:`easyhec_amd.info_explorer.InformationExplorer`, built each round on that round's solve; it needs no
+        optimisation history, so ``sample`` and ``start`` are not used)."""
+        if explore not in ("variance", "information"):
+            raise ValueError(f"explore={explore!r}: 'variance' or 'information'")
+        self.explore = explore
         self.robot, self.K, self.H, self.W = robot, np.asarray(K, dtype=np.float64), int(H), int(W)
         self.init_Tc_c2b = np.asarray(init_Tc_c2b, dtype=np.float64)
         self.capture, self.candidates = capture, candidates
@@ -68,11 +76,15 @@ class OnlineCalibration:
             rec = {"round": it, "frames": len(self.qposes), "mask_loss": float(loss), "solve_s": t1 - t0}
             if it + 1 < self.explore_iters:                               # explore_next_state (rbsolve_iter.py:263-275)
                 cand, valid = self.candidates(it)
-                out = self.explorer.forward(cand, self.model.history_ops.detach().cpu(), start=self.start,
-                                            sample=self.sample, valid=valid, generator=self.gen)
+                if self.explore == "information":
+                    out = InformationExplorer(trainer.fast, robot=self.robot).forward(cand, valid=valid)
+                    scores = {"info_gain": float(out["gain"]), "gain_mean": float(out["gain_mean"])}
+                else:
+                    out = self.explorer.forward(cand, self.model.history_ops.detach().cpu(), start=self.start,
+                                                sample=self.sample, valid=valid, generator=self.gen)
+                    scores = {"variance": float(out["variance"]), "var_mean": float(out["var_mean"])}
                 torch.cuda.synchronize(self.device)
                 qpos = np.asarray(out["qpos"], dtype=np.float64)
-                rec.update(explore_s=time.perf_counter() - t1, variance=float(out["variance"]),
-                           var_mean=float(out["var_mean"]), candidates=int(len(cand)))
+                rec.update(explore_s=time.perf_counter() - t1, **scores, candidates=int(len(cand)))
             self.log.append(rec)
         return self.model.Tc_c2b().detach().cpu().numpy()

@@ -585,6 +585,35 @@ int ehr_lm_update(const double* info, const double* grad, const long long* count
                   const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state,
                   double* log, int log_rows, void* stream);
 
+/* Information-gain exploration: which candidate joint configuration to observe next.  A candidate is a group of S consecutive
+ * views of info [Q,S,N,N] -- ehr_mask_information's matrices of the views the candidate WOULD give (the op's info does not depend
+ * on the reference mask, so they exist before the candidate is observed); S > 1 averages over sampled poses or sums over cameras.
+ * Both calls take device pointers only, never allocate or synchronise and launch on `stream`; k rounds of gain + pick are 2k
+ * launches with no host round trip.  No atomics; every sum in a fixed order.  1 <= N <= EHR_IG_MAX_PARAMS, Q >= 1, S >= 1.
+ *   ehr_information_gain : A [N,N] float64 = what is already known (a prior plus the frames so far), symmetric, with a finite
+ *                          diagonal > 0 (otherwise EVERY gain is NaN).  H_q = scale * (info[q,0] + info[q,1] + ...), summed in
+ *                          view order; X0 = A, X1 = A + H_q.  Both are scaled by s_i = 1 / sqrt(A_ii) as (x_ij s_i) s_j and factored
+ *                          by Cholesky in float64; ld(X) = 2 sum_j log r_jj.  Where interest_mask (bit k: parameter k is of
+ *                          interest) does not cover all N bits, the same quantity of the sub-matrix on the COMPLEMENT indices
+ *                          (ascending) is subtracted: the log-determinant of the MARGINAL information of the parameters of
+ *                          interest, logdet X - logdet X_bb.  gain[q] = ld(X1) - ld(X0), both by the same device function in the
+ *                          same wave: a candidate whose H_q is all zeros gets exactly +0.0.  valid[q] == 0 (valid may be NULL)
+ *                          or taken[q] != 0 (taken may be NULL): gain = -inf, and that candidate's info is not read.  A
+ *                          non-finite entry of H_q or a pivot that is not positive: NaN (this is how a reported
+ *                          ehr_mask_information call surfaces).  A gain depends on A and the candidate's own matrices alone: the
+ *                          same bits alone, in any batch, at any position.  One wave per candidate.
+ *   ehr_information_pick : one workgroup.  q* = the lowest index among the candidates with the largest FINITE gain (NaN and -inf
+ *                          never win).  None: picked[round] = -1, picked_gain[round] = NaN, A and taken untouched.  Otherwise
+ *                          picked[round] = q*, picked_gain[round] = gain[q*], taken[q*] = 1 and A[e] = A[e] + H_q*[e] entry by
+ *                          entry, H_q* by the expression above (a product rounded, then a sum rounded): A stays exactly symmetric
+ *                          where the matrices are.
+ * ehr_version() is unchanged: the presence of these symbols is the capability check. */
+#define EHR_IG_MAX_PARAMS 32
+int ehr_information_gain(const double* A, const double* info, const int32_t* valid, const int32_t* taken, int Q, int S, int N,
+                         double scale, uint32_t interest_mask, double* gain, void* stream);
+int ehr_information_pick(const double* gain, const double* info, int Q, int S, int N, double scale, int round, double* A,
+                         int32_t* taken, int32_t* picked, double* picked_gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

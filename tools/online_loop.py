@@ -1,6 +1,7 @@
 """Simulated run of the reference's online loop (easyhec/trainer/rbsolve_iter.py:157-167): a hidden ground-truth camera
 pose plays the RealSense + segmentation network, uniformly sampled joint vectors play the planner.  Prints per-round
-records and the final pose error.  python tools/online_loop.py [--explore-iters 5] [--epochs 1000] [--candidates 1000]"""
+records and the final pose error.  python tools/online_loop.py [--explore-iters 5] [--epochs 1000] [--candidates 1000]
+[--explore variance|information]"""
 import argparse
 import json
 import os
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--candidates", type=int, default=1000)
     ap.add_argument("--sample", type=int, default=10)
     ap.add_argument("--scale", type=float, default=0.5, help="image scale relative to 1280x720")
+    ap.add_argument("--explore", choices=("variance", "information"), default="variance",
+                    help="how the next joint configuration is scored: mask variance (the reference's) or information gain")
     a = ap.parse_args()
     rb = load_robot("xarm7")
     W, H = int(1280 * a.scale), int(720 * a.scale)
@@ -46,7 +49,7 @@ def main():
         return rb.sample_qpos(a.candidates, rng, scale=0.9), None
 
     loop = OnlineCalibration(rb, K, H, W, init, capture, candidates, num_epochs=a.epochs,
-                             explore_iters=a.explore_iters, sample=a.sample)
+                             explore_iters=a.explore_iters, sample=a.sample, explore=a.explore)
     Tc = loop.fit(np.zeros(7))
     for r in loop.log:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}))
