@@ -15,6 +15,10 @@ def __getattr__(name):
     if name in ("LevenbergMarquardt", "solve_lm", "LmResult"):
         from . import lm
         return getattr(lm, name)
+    # its multi-start form (easyhec_amd/lm_multi.py), likewise
+    if name in ("MultiStartLM", "MultiLmResult", "solve_lm_multi", "solve_global_lm", "group_basins"):
+        from . import lm_multi
+        return getattr(lm_multi, name)
     # information-gain exploration (easyhec_amd/info_explorer.py), likewise
     if name in ("InformationExplorer", "information_gain", "greedy_select"):
         from . import info_explorer

@@ -86,6 +86,9 @@ SIGNATURES = {
     "ehr_lm_linearize": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3),
     "ehr_lm_update": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 +
                       [c_void_p] * 2 + [c_int] * 2 + [ctypes.c_double] * 2 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p]),
+    "ehr_lm_linearize_multi": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3),
+    "ehr_lm_update_multi": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] + [ctypes.c_double] * 2 + [c_int] +
+                            [c_void_p] * 2 + [c_int, c_void_p]),
     "ehr_information_gain": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_double, ctypes.c_uint32, c_void_p, c_void_p]),
     "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
 }
@@ -173,6 +176,15 @@ def has_lm():
         return False
     l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
     return hasattr(l, "ehr_lm_linearize") and hasattr(l, "ehr_lm_update")
+
+
+def has_lm_multi():
+    """True if the library has the multi-start Levenberg-Marquardt kernels (``ehr_lm_linearize_multi`` /
+    ``ehr_lm_update_multi``); the symbols' presence is the capability check, as for :func:`has_multistart`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
+    return hasattr(l, "ehr_lm_linearize_multi") and hasattr(l, "ehr_lm_update_multi")
 
 
 def has_information_gain():

@@ -11,6 +11,10 @@
 //                  predicted reduction, the stopping rule, and the next trial's parameters (or the accepted ones).  One
 //                  workgroup of one wave, float64 throughout, every sum in a fixed order.
 //
+//   lm_linearize_multi, lm_update_multi : the same two for P hypotheses of ONE problem (easyhec_amd/lm_multi.py, section 6m):
+//                  virtual view p * Bv + j takes dof[p] and link_poses[j]; one workgroup per hypothesis updates its own state
+//                  block.  Both call the device functions the solo kernels call, so hypothesis p has its solo solve's bits.
+//
 // No kernel here allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
@@ -108,18 +112,15 @@ __device__ __forceinline__ int lm_intrinsics_element(int q, int free4_mask, int 
     return -1;
 }
 
-__global__ void __launch_bounds__(256) lm_linearize_kernel(const float* __restrict__ dof, const float* __restrict__ K,
-                                                           const float* __restrict__ link_poses, int B, int L, int H, int W,
-                                                           float n, float f, const float* __restrict__ joint_frames,
-                                                           const unsigned* __restrict__ upstream,
-                                                           const int* __restrict__ joint_kind, const int* __restrict__ free_list,
-                                                           int F, int J, int free4_mask, int tie_focal, int N,
-                                                           float* __restrict__ mvp, float* __restrict__ dmvp) {
-    const int BL = B * L;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)(N + 1) * BL) return;
-    const int k = (int)(idx / BL) - 1, i = (int)(idx % BL);
-    const float* lpf = link_poses + (size_t)i * 16;
+// One (k, b, l) matrix of the linearisation, for both kernels below: k < 0 -> the matrix itself into `o` (16 floats), else the
+// tangent d MVP[b,l] / d theta_k.  dof: the 6 pose coordinates of this view's hypothesis; lpf: link_poses[b,l]; b, l: the view
+// and link the joint tables are read at (free joints only).
+__device__ __forceinline__ void lm_linearize_matrix(const float* __restrict__ dof, const float* __restrict__ K,
+                                                    const float* __restrict__ lpf, int k, int b, int l, int H, int W, float n,
+                                                    float f, const float* __restrict__ joint_frames,
+                                                    const unsigned* __restrict__ upstream, const int* __restrict__ joint_kind,
+                                                    const int* __restrict__ free_list, int F, int J, int free4_mask,
+                                                    int tie_focal, float* __restrict__ o) {
     if (k < 0) {  // the matrix itself: pose_forward_kernel's expressions
         Dual<1> T[16];
         se3_exp_dual<1>(dof, 1e-4f, T);
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(256) lm_linearize_kernel(const float* __restri
         for (int e = 0; e < 16; e++) Tc[e] = T[e].v;
         projection(K, H, W, n, f, P);
         mvp_from_pose(Tc, P, lpf, C);
-        for (int e = 0; e < 16; e++) mvp[(size_t)i * 16 + e] = C[e];
+        for (int e = 0; e < 16; e++) o[e] = C[e];
         return;
     }
     double Tc[16], dTc[16], lp[16], M[16], A[16], out[16];
@@ -150,7 +151,6 @@ __global__ void __launch_bounds__(256) lm_linearize_kernel(const float* __restri
         mat4_mul_f64(PF, M, out);
     } else if (k < 6 + F) {  // PF @ Tc @ D_blj
         const int j = free_list[k - 6];
-        const int b = i / L, l = i - b * L;
         const int kind = (j >= 0 && j < J) ? joint_kind[j] : 0;
         if (j >= 0 && j < J && ((upstream[l] >> j) & 1u) && (kind == 1 || kind == 2)) {
             const float* jf = joint_frames + ((size_t)b * J + j) * 6;
@@ -189,8 +189,38 @@ __global__ void __launch_bounds__(256) lm_linearize_kernel(const float* __restri
             if (el == 3) out[4 + c] = 2.0 * A[8 + c];
         }
     }
-    float* o = dmvp + ((size_t)k * BL + i) * 16;
     for (int e = 0; e < 16; e++) o[e] = (float)out[e];
+}
+
+__global__ void __launch_bounds__(256) lm_linearize_kernel(const float* __restrict__ dof, const float* __restrict__ K,
+                                                           const float* __restrict__ link_poses, int B, int L, int H, int W,
+                                                           float n, float f, const float* __restrict__ joint_frames,
+                                                           const unsigned* __restrict__ upstream,
+                                                           const int* __restrict__ joint_kind, const int* __restrict__ free_list,
+                                                           int F, int J, int free4_mask, int tie_focal, int N,
+                                                           float* __restrict__ mvp, float* __restrict__ dmvp) {
+    const int BL = B * L;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)(N + 1) * BL) return;
+    const int k = (int)(idx / BL) - 1, i = (int)(idx % BL);
+    const int b = i / L, l = i - b * L;
+    lm_linearize_matrix(dof, K, link_poses + (size_t)i * 16, k, b, l, H, W, n, f, joint_frames, upstream, joint_kind, free_list, F,
+                        J, free4_mask, tie_focal, k < 0 ? mvp + (size_t)i * 16 : dmvp + ((size_t)k * BL + i) * 16);
+}
+
+// P hypotheses: virtual view b = p * Bv + j takes dof[p] and link_poses[j] (ehr_solver_step_multi's layout); pose only.
+__global__ void __launch_bounds__(256) lm_linearize_multi_kernel(const float* __restrict__ dof, const float* __restrict__ K,
+                                                                 const float* __restrict__ link_poses, int P, int Bv, int L,
+                                                                 int H, int W, float n, float f, float* __restrict__ mvp,
+                                                                 float* __restrict__ dmvp) {
+    const int BL = P * Bv * L;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 7ll * BL) return;
+    const int k = (int)(idx / BL) - 1, i = (int)(idx % BL);
+    const int b = i / L, l = i - b * L;
+    const int p = b / Bv, j = b - p * Bv;
+    lm_linearize_matrix(dof + 6 * (size_t)p, K, link_poses + ((size_t)j * L + l) * 16, k, j, l, H, W, n, f, nullptr, nullptr,
+                        nullptr, nullptr, 0, 0, 0, 0, k < 0 ? mvp + (size_t)i * 16 : dmvp + ((size_t)k * BL + i) * 16);
 }
 
 // ---- the update ---------------------------------------------------------------------------------------------------------------
@@ -256,10 +286,12 @@ __device__ __forceinline__ double lm_spacing_f32(float x) {
     return ldexp(1.0, (e == 0 ? 1 : e) - 150);
 }
 
-__global__ void __launch_bounds__(64) lm_update_kernel(const double* __restrict__ info, const double* __restrict__ grad,
-                                                       const long long* __restrict__ count, const float* __restrict__ loss,
-                                                       int B, int N, LmParams p, double ftol, double lambda_max, int finalize,
-                                                       double* __restrict__ st, double* __restrict__ log, int log_rows) {
+// One solve's update by one workgroup of one wave (steps 1-6 of include/ehr.h), for both kernels below: B views summed in
+// order, the parameters behind p, the state block st and the log are this solve's own.
+__device__ __forceinline__ void lm_update_solve(const double* __restrict__ info, const double* __restrict__ grad,
+                                                const long long* __restrict__ count, const float* __restrict__ loss, int B,
+                                                int N, const LmParams& p, double ftol, double lambda_max, int finalize,
+                                                double* __restrict__ st, double* __restrict__ log, int log_rows) {
     __shared__ double Hm[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];  // the call's sum, then H_acc
     __shared__ double A[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];   // the scaled, damped system and its factor
     __shared__ double gv[EHR_LM_MAX_PARAMS], sv[EHR_LM_MAX_PARAMS], yv[EHR_LM_MAX_PARAMS], rv[EHR_LM_MAX_PARAMS],
@@ -484,6 +516,27 @@ __global__ void __launch_bounds__(64) lm_update_kernel(const double* __restrict_
     lm_write_K(p, tid);
 }
 
+__global__ void __launch_bounds__(64) lm_update_kernel(const double* __restrict__ info, const double* __restrict__ grad,
+                                                       const long long* __restrict__ count, const float* __restrict__ loss,
+                                                       int B, int N, LmParams p, double ftol, double lambda_max, int finalize,
+                                                       double* __restrict__ st, double* __restrict__ log, int log_rows) {
+    lm_update_solve(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize, st, log, log_rows);
+}
+
+// P hypotheses, one workgroup each: hypothesis p owns views [p Bv, (p + 1) Bv), dof[p], state block p and log rows p.  Reported,
+// done and finalize are per hypothesis: a workgroup returns or restores by its own block alone.
+__global__ void __launch_bounds__(64) lm_update_multi_kernel(const double* __restrict__ info, const double* __restrict__ grad,
+                                                             const long long* __restrict__ count,
+                                                             const float* __restrict__ loss, int Bv, int N,
+                                                             float* __restrict__ dof, double ftol, double lambda_max,
+                                                             int finalize, double* __restrict__ st, double* __restrict__ log,
+                                                             int log_rows) {
+    const size_t h = blockIdx.x, v = h * (size_t)Bv;
+    const LmParams p = {dof + 6 * h, nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, 0, 0};
+    lm_update_solve(info + v * N * N, grad + v * N, count + v, loss + v, Bv, N, p, ftol, lambda_max, finalize,
+                    st + h * EHR_LM_STATE_DOUBLES, log ? log + h * (size_t)log_rows * 4 : nullptr, log_rows);
+}
+
 }  // namespace ehr
 
 using namespace ehr;
@@ -536,6 +589,32 @@ int ehr_lm_update(const double* info, const double* grad, const long long* count
     LmParams p = {dof, offset, free_list, F, J, theta, free4_mask, tie_focal, K0, K, H, W};
     lm_update_kernel<<<1, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize, state,
                                                        log && log_rows > 0 ? log : nullptr, log_rows);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_lm_linearize_multi(const float* dof, const float* K, const float* link_poses, int P, int Bv, int L, int H, int W,
+                           float near_plane, float far_plane, float* mvp, float* dmvp, void* stream) {
+    if (!dof || !K || !link_poses || !mvp || !dmvp) return fail(EHR_ERR_INVALID, "ehr_lm_linearize_multi: NULL tensor");
+    if (P < 1 || Bv < 1 || L < 1 || H < 1 || W < 1 || (long long)P * Bv * L * 7 > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID, "ehr_lm_linearize_multi: bad sizes (P %d, Bv %d, L %d, H %d, W %d)", P, Bv, L, H, W);
+    const long long total = (long long)P * Bv * L * 7;
+    lm_linearize_multi_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        dof, K, link_poses, P, Bv, L, H, W, near_plane, far_plane, mvp, dmvp);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_lm_update_multi(const double* info, const double* grad, const long long* count, const float* loss, int P, int Bv, int N,
+                        float* dof, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                        void* stream) {
+    if (!info || !grad || !count || !loss || !dof || !state) return fail(EHR_ERR_INVALID, "ehr_lm_update_multi: NULL tensor");
+    if (P < 1 || Bv < 1 || N < 1 || N > 6 || (long long)P * Bv > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID, "ehr_lm_update_multi: bad sizes (P %d, Bv %d), or N %d outside 1..6 (the pose alone)", P, Bv,
+                    N);
+    lm_update_multi_kernel<<<(unsigned)P, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, Bv, N, dof, ftol, lambda_max,
+                                                                       finalize, state, log && log_rows > 0 ? log : nullptr,
+                                                                       log_rows);
     EHR_LAUNCH_CHECK();
     return EHR_OK;
 }

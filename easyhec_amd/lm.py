@@ -87,6 +87,20 @@ def launch_linearize(step, lay, free_list, link_poses, joint_frames, B, mvp, dmv
         F, lay.J, lay.free4_mask, lay.tie_focal, lay.N, _lib.ptr(mvp), _lib.ptr(dmvp), stream), "ehr_lm_linearize")
 
 
+def state_namespace(s, N):
+    """One state block of ``ehr_lm_update`` (``s``: its EHR_LM_STATE_DOUBLES float64 on the host) as the namespace
+    :meth:`LevenbergMarquardt.state` documents."""
+    ns = types.SimpleNamespace(**{k: float(s[i]) for k, i in _lib.LM_STATE.items()})
+    for k in ("iterations", "accepted", "rejected", "reported", "done", "why", "last", "count", "retries"):
+        setattr(ns, k, int(getattr(ns, k)))
+    ns.theta = s[_lib.LM_THETA:_lib.LM_THETA + N].copy()
+    ns.delta = s[_lib.LM_DELTA:_lib.LM_DELTA + N].copy()
+    ns.g = s[_lib.LM_G:_lib.LM_G + N].copy()
+    ns.H = s[_lib.LM_H:_lib.LM_H + 32 * 32].reshape(32, 32)[:N, :N].copy()
+    ns.raw = s
+    return ns
+
+
 class LevenbergMarquardt:
     """Drives ``step`` (``FusedPoseStep``, ``JointPoseStep``, ``IntrinsicsPoseStep`` or ``JointIntrinsicsPoseStep``) by
     Levenberg-Marquardt iterations on the parameters it optimises, in the order of
@@ -177,17 +191,7 @@ class LevenbergMarquardt:
         """The state block as a namespace (one small copy; synchronises): lambda, nu, F_acc, pred, rho, F_trial, the counters
         iterations / accepted / rejected / reported / retries, done, why, last, count, and theta [N], delta [N], g [N],
         H [N,N] of the accepted point."""
-        s = self.state_block.cpu().numpy()
-        N = self.N
-        ns = types.SimpleNamespace(**{k: float(s[i]) for k, i in _lib.LM_STATE.items()})
-        for k in ("iterations", "accepted", "rejected", "reported", "done", "why", "last", "count", "retries"):
-            setattr(ns, k, int(getattr(ns, k)))
-        ns.theta = s[_lib.LM_THETA:_lib.LM_THETA + N].copy()
-        ns.delta = s[_lib.LM_DELTA:_lib.LM_DELTA + N].copy()
-        ns.g = s[_lib.LM_G:_lib.LM_G + N].copy()
-        ns.H = s[_lib.LM_H:_lib.LM_H + 32 * 32].reshape(32, 32)[:N, :N].copy()
-        ns.raw = s
-        return ns
+        return state_namespace(self.state_block.cpu().numpy(), self.N)
 
     def trajectory(self):
         """[iterations, 4] float64 (CPU): per iteration the trial's loss (NaN: reported), 1 accepted / 0 rejected / -1

@@ -585,6 +585,33 @@ int ehr_lm_update(const double* info, const double* grad, const long long* count
                   const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state,
                   double* log, int log_rows, void* stream);
 
+/* Multi-start Levenberg-Marquardt: the two calls above for P hypotheses of ONE problem, so that an iteration of all of them is
+ *     ehr_lm_linearize_multi -> ehr_mask_information (P*Bv views) -> ehr_lm_update_multi                    on one stream,
+ * whatever P is.  Pose only: no joint offsets, no intrinsics (N = 6 tangents; the update takes N in 1..6 like the solo entry where
+ * nothing but the pose is free).  Device pointers only; neither call allocates, synchronises or uses an atomic.  The contract is
+ * ehr_solver_step_multi's: hypothesis p is, bit for bit, its solo solve -- both kernels call the device functions of the solo
+ * kernels.
+ *   ehr_lm_linearize_multi : virtual view b = p * Bv + j takes dof[p] and link_poses[j] (ehr_solver_step_multi's layout; K and
+ *                            link_poses are shared, never copied).  mvp [P*Bv,L,16], dmvp [6,P*Bv,L,16]; views [p Bv, (p+1) Bv)
+ *                            of both hold the bits ehr_lm_linearize(dof + 6 p, ..., B = Bv, F = 0, free4_mask = 0, N = 6) writes.
+ *                            One thread per (k, b, l) matrix.
+ *   ehr_lm_update_multi    : a grid of P workgroups of one wave.  Workgroup p runs steps 1-6 of ehr_lm_update on its own slices:
+ *                            views [p Bv, (p+1) Bv) of info / grad / count / loss summed in view order, dof + 6 p,
+ *                            state + p * EHR_LM_STATE_DOUBLES and log + p * log_rows * 4 (log may be NULL).  Reported, done and
+ *                            finalize apply to ONE hypothesis: a non-finite sum or a count < 0 among hypothesis p's views discards
+ *                            p's trial only; a hypothesis that is done only restores its accepted pose while the others move;
+ *                            finalize != 0 restores all P accepted poses and changes nothing else.  The caller prepares every
+ *                            state block as for ehr_lm_update.
+ * Both refuse (EHR_ERR_INVALID) NULL tensors, P < 1, Bv < 1 and sizes whose matrix count overflows 32 bits; the update also N
+ * outside 1..6.  Out of scope: free joints or intrinsics per hypothesis, a shared-reference form of ehr_mask_information (the
+ * caller tiles the reference), retiring finished hypotheses from the render.
+ * ehr_version() is unchanged: the presence of these symbols is the capability check. */
+int ehr_lm_linearize_multi(const float* dof, const float* K, const float* link_poses, int P, int Bv, int L, int H, int W,
+                           float near_plane, float far_plane, float* mvp, float* dmvp, void* stream);
+int ehr_lm_update_multi(const double* info, const double* grad, const long long* count, const float* loss, int P, int Bv, int N,
+                        float* dof, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                        void* stream);
+
 /* Information-gain exploration: which candidate joint configuration to observe next.  A candidate is a group of S consecutive
  * views of info [Q,S,N,N] -- ehr_mask_information's matrices of the views the candidate WOULD give (the op's info does not depend
  * on the reference mask, so they exist before the candidate is observed); S > 1 averages over sampled poses or sums over cameras.
