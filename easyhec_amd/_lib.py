@@ -63,6 +63,8 @@ SIGNATURES = {
     "ehr_fused_bind_weight": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_mask_variance": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
     "ehr_mask_overlap": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p, c_void_p, c_int, c_void_p]),
+    "ehr_mask_distance": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ehr_mask_cost": (c_int, [c_void_p] * 6 + [c_int] * 8 + [c_void_p, c_int, c_void_p]),
     "ehr_comm_unique_id": (c_int, [c_void_p]),
     "ehr_comm_init": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "ehr_comm_allreduce": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
@@ -126,6 +128,15 @@ def has_pose_search():
     if not os.path.exists(LIB_PATH):
         return False
     return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_overlap")
+
+
+def has_soft_search():
+    """True if the library has the pose search's soft score (``ehr_mask_distance`` and ``ehr_mask_cost``); the symbols'
+    presence is the capability check, as for :func:`has_pose_search`."""
+    if not os.path.exists(LIB_PATH):
+        return False
+    so = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
+    return hasattr(so, "ehr_mask_distance") and hasattr(so, "ehr_mask_cost")
 
 
 def has_weighted_loss():

@@ -79,6 +79,9 @@ struct InfoCall {
     double* grad;       // [B][N]
     long long* count;   // [B]
 };
+int vbuf_cost(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+              const int32_t* cost, int C, int Q, int S, int L, int V, int T, int H, int W, long long* sums, hipStream_t stream,
+              int* handled);
 int vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
                const int32_t* opp, float* mvp, const float* ref, int B, int L, int V, int T, int H, int W, float* mask,
                float* loss, float* grad_mvp, const StepHead* head, const StepTail* tail, hipStream_t stream,
@@ -153,6 +156,7 @@ struct ehr_ctx {
     // space-explorer scoring (ehr_mask_variance) keeps its own scratch so that it never disturbs a solver plan
     ehr::Scratch sc_counts, sc_offsets, sc_entries, sc_posc;
     ehr::Scratch sc_img;  // pose search (ehr_mask_overlap), exact path only: a pass's masks u8 [views][H][W] | its score sink i64 [views]
+    ehr::Scratch sc_dist;  // distance transform (ehr_mask_distance): the column distances u16 [S][H][W] between its two passes
     size_t sc_entries_cap = 0;
     // ... and, for the coverage-only chain of the scoring op (ehr_vbuf.hip: vbuf_score), the static cluster index of its mesh
     ehr::Scratch sc_clus, sc_misc;  // (sc_misc: link boxes | meta block | hint lists | sticky flag | sums | coverage words | the op's own, VbScoreMisc)
@@ -176,7 +180,7 @@ struct ehr_ctx {
     unsigned long long scratch_moves() const {
         unsigned long long n = 0;
         for (const ehr::Scratch* s : {&counts, &offsets, &entries, &vb_clus, &vb_heavy, &vb_idx, &vb_boxes, &vb_units, &vb_acc,
-                                      &vb_posc, &vb_jobs, &vb_spill, &vb_refsum, &vb_hstate, &vb_hstate_m, &sc_counts, &sc_offsets, &sc_entries, &sc_posc, &sc_clus, &sc_misc, &sc_img})
+                                      &vb_posc, &vb_jobs, &vb_spill, &vb_refsum, &vb_hstate, &vb_hstate_m, &sc_counts, &sc_offsets, &sc_entries, &sc_posc, &sc_clus, &sc_misc, &sc_img, &sc_dist})
             n += s->moves;
         return n;
     }

@@ -550,6 +550,7 @@ int ehr_ctx_destroy(ehr_ctx* c) {
     c->sc_clus.release();
     c->sc_misc.release();
     c->sc_img.release();
+    c->sc_dist.release();
     c->vb_clus.release();
     c->vb_idx.release();
     c->vb_heavy.release();
@@ -579,7 +580,7 @@ size_t ehr_ctx_scratch_bytes(ehr_ctx* c) {
     size_t n = 0;
     for (const Scratch* s : {&c->counts, &c->ranges, &c->rkeys, &c->offsets, &c->entries, &c->vb_clus, &c->vb_heavy, &c->vb_idx, &c->vb_boxes, &c->vb_units,
                              &c->vb_acc, &c->vb_posc, &c->vb_jobs, &c->vb_spill, &c->vb_refsum, &c->vb_hstate, &c->vb_hstate_m, &c->sc_counts, &c->sc_offsets,
-                             &c->sc_entries, &c->sc_posc, &c->sc_clus, &c->sc_misc, &c->sc_img})
+                             &c->sc_entries, &c->sc_posc, &c->sc_clus, &c->sc_misc, &c->sc_img, &c->sc_dist})
         n += s->cap;
     return n;
 }

@@ -189,6 +189,39 @@ score_overlap_reduce_kernel(const unsigned char* __restrict__ img, const float* 
     }
 }
 
+// Pose search, soft score, exact path: a pass's masks against the cost images cost [C][S][H][W] (int32, row 0 = top like
+// the masks).  Same geometry as score_overlap_reduce_kernel; sums [.][C+1] = {area, sum_0 .. sum_{C-1}} per global view,
+// 64-bit integer atomics per wave (two's complement: negative sums wrap to the right int64).
+__global__ void __launch_bounds__(256)
+score_cost_reduce_kernel(const unsigned char* __restrict__ img, const int32_t* __restrict__ cost, int C, int S, int HW, long long v0,
+                         unsigned long long* __restrict__ sums) {
+    const long long v = v0 + blockIdx.y;
+    const int s = (int)(v % S);
+    const unsigned char* const m = img + (size_t)blockIdx.y * HW;
+    const int32_t* const cs = cost + (size_t)s * HW;  // + c * S * HW
+    unsigned area = 0;
+    long long t[4] = {0, 0, 0, 0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256)
+        if (m[i] != 0) {
+            area++;
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                if (c < C) t[c] += cs[(size_t)c * S * HW + i];
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        area += __shfl_xor(area, o, 64);
+#pragma unroll
+        for (int c = 0; c < 4; c++) t[c] += __shfl_xor(t[c], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0 && area) {
+        atomicAdd(&sums[(size_t)(C + 1) * v], (unsigned long long)area);
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (c < C && t[c]) atomicAdd(&sums[(size_t)(C + 1) * v + 1 + c], (unsigned long long)t[c]);
+    }
+}
+
 }  // namespace ehr
 
 using namespace ehr;
@@ -308,6 +341,33 @@ extern "C" int ehr_mask_variance(ehr_ctx* ctx, const float* verts, const int32_t
     return score_tiles(ctx, "ehr_mask_variance", verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, score, count, chunk_views, stream);
 }
 
+// The exact path of the pose search's two ops: every (candidate, view) is a single-pose candidate of the tile
+// implementation, whose count image is then the mask; passes of at most chunk_views views, bounded by the scratch for their
+// images (256 MiB) and the reducer's grid (32768).  reduce(grid, img, HW, v0) launches the op's reducer over a pass's masks
+// (u8 [n][H][W], row 0 = top; blockIdx.y = view of the pass, global view v0 + y = candidate * S + s).
+template <class Reduce>
+static int score_single_views(ehr_ctx* ctx, const char* what, const float* verts, const int32_t* tris, const int32_t* vert_link,
+                              const float* mvp, int Q, int S, int L, int V, int T, int H, int W, int chunk_views, hipStream_t stream,
+                              Reduce reduce) {
+    if (chunk_views <= 0) chunk_views = 512;
+    const size_t HW = (size_t)H * W;
+    const long long views = (long long)Q * S;
+    const int pass = (int)std::max<long long>(1, std::min<long long>({views, (long long)chunk_views, 32768ll, (long long)(((size_t)256 << 20) / HW)}));
+    int rc;
+    const size_t img_bytes = ((size_t)pass * HW + 7) & ~(size_t)7;
+    if ((rc = ctx->sc_img.reserve(img_bytes + (size_t)pass * sizeof(int64_t)))) return rc;
+    uint8_t* img = (uint8_t*)ctx->sc_img.ptr;
+    int64_t* sink = (int64_t*)(img + img_bytes);  // (the variance of one mask: all zero)
+    for (long long v0 = 0; v0 < views; v0 += pass) {
+        const int n = (int)std::min<long long>(pass, views - v0);
+        if ((rc = score_tiles(ctx, what, verts, tris, vert_link, mvp + (size_t)v0 * L * 16, n, 1, L, V, T, H, W, sink, img, chunk_views, stream)))
+            return rc;
+        reduce(dim3((unsigned)std::min<size_t>((HW + 2047) / 2048, 16), n), img, (int)HW, v0);
+        EHR_LAUNCH_CHECK();
+    }
+    return EHR_OK;
+}
+
 extern "C" int ehr_mask_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link,
                                 const float* mvp, const float* ref, int Q, int S, int L, int V, int T, int H, int W,
                                 int64_t* overlap, int64_t* ref_area, int chunk_views, void* stream_) {
@@ -324,27 +384,34 @@ extern "C" int ehr_mask_overlap(ehr_ctx* ctx, const float* verts, const int32_t*
         if (rc2) return rc2;
         if (handled) return EHR_OK;
     }
-    // The exact path: every (candidate, view) is a single-pose candidate of the tile implementation, whose count image is
-    // then the mask; passes of at most chunk_views views, bounded by the scratch for their images (256 MiB) and the reducer's grid (32768).
-    if (chunk_views <= 0) chunk_views = 512;
-    const size_t HW = (size_t)H * W;
-    const long long views = (long long)Q * S;
-    const int pass = (int)std::max<long long>(1, std::min<long long>({views, (long long)chunk_views, 32768ll, (long long)(((size_t)256 << 20) / HW)}));
-    int rc;
-    const size_t img_bytes = ((size_t)pass * HW + 7) & ~(size_t)7;
-    if ((rc = ctx->sc_img.reserve(img_bytes + (size_t)pass * sizeof(int64_t)))) return rc;
-    uint8_t* img = (uint8_t*)ctx->sc_img.ptr;
-    int64_t* sink = (int64_t*)(img + img_bytes);  // (the variance of one mask: all zero)
-    EHR_HIP(hipMemsetAsync(overlap, 0, (size_t)views * 2 * sizeof(int64_t), stream));
+    EHR_HIP(hipMemsetAsync(overlap, 0, (size_t)Q * S * 2 * sizeof(int64_t), stream));
     EHR_HIP(hipMemsetAsync(ref_area, 0, (size_t)S * sizeof(int64_t), stream));
-    for (long long v0 = 0; v0 < views; v0 += pass) {
-        const int n = (int)std::min<long long>(pass, views - v0);
-        if ((rc = score_tiles(ctx, "ehr_mask_overlap", verts, tris, vert_link, mvp + (size_t)v0 * L * 16, n, 1, L, V, T, H, W, sink, img,
-                              chunk_views, stream)))
-            return rc;
-        score_overlap_reduce_kernel<<<dim3((unsigned)std::min<size_t>((HW + 2047) / 2048, 16), n), 256, 0, stream>>>(
-            img, ref, S, (int)HW, v0, (unsigned long long*)overlap, (unsigned long long*)ref_area);
-        EHR_LAUNCH_CHECK();
+    return score_single_views(ctx, "ehr_mask_overlap", verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, chunk_views, stream,
+                              [&](dim3 grid, const uint8_t* img, int HW, long long v0) {
+                                  score_overlap_reduce_kernel<<<grid, 256, 0, stream>>>(img, ref, S, HW, v0, (unsigned long long*)overlap,
+                                                                                        (unsigned long long*)ref_area);
+                              });
+}
+
+extern "C" int ehr_mask_cost(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+                             const int32_t* cost, int C, int Q, int S, int L, int V, int T, int H, int W, int64_t* sums,
+                             int chunk_views, void* stream_) {
+    if (!ctx) return fail(EHR_ERR_INVALID, "ehr_mask_cost: ctx is NULL");
+    if (!verts || !tris || !mvp || !cost || !sums) return fail(EHR_ERR_INVALID, "ehr_mask_cost: NULL tensor");
+    if (Q <= 0 || L <= 0 || V <= 0 || T <= 0 || H <= 0 || W <= 0) return fail(EHR_ERR_INVALID, "ehr_mask_cost: bad sizes");
+    if (C < 1 || C > 4) return fail(EHR_ERR_INVALID, "ehr_mask_cost: C must be in [1, 4], got %d", C);
+    if (S < 1 || S > SCORE_MAX_S) return fail(EHR_ERR_INVALID, "ehr_mask_cost: S must be in [1, %d]", SCORE_MAX_S);
+    if (H > 32768 || W > 32768) return fail(EHR_ERR_INVALID, "ehr_mask_cost: resolution above 32768 is unsupported");
+    hipStream_t stream = (hipStream_t)stream_;
+    {   // the coverage-only chain, where the call allows it (ehr_vbuf.hip)
+        int handled = 0;
+        const int rc2 = vbuf_cost(ctx, verts, tris, vert_link, mvp, cost, C, Q, S, L, V, T, H, W, (long long*)sums, stream, &handled);
+        if (rc2) return rc2;
+        if (handled) return EHR_OK;
     }
-    return EHR_OK;
+    EHR_HIP(hipMemsetAsync(sums, 0, (size_t)Q * S * (C + 1) * sizeof(int64_t), stream));
+    return score_single_views(ctx, "ehr_mask_cost", verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, chunk_views, stream,
+                              [&](dim3 grid, const uint8_t* img, int HW, long long v0) {
+                                  score_cost_reduce_kernel<<<grid, 256, 0, stream>>>(img, cost, C, S, HW, v0, (unsigned long long*)sums);
+                              });
 }

@@ -3024,6 +3024,150 @@ vb_overlap_count_kernel(BinGeom g, int nq, int S, int per_wave, const u64* __res
     }
 }
 
+// Pose search, soft score (ehr_mask_cost), once per call: the cost images cost [C][S][H][W] (int32, row 0 = top) in a
+// tile-major layout that follows the coverage words' bit order, cpack [S][nt][C][256]: value 32 r + col of a tile is the
+// pixel of coverage bit (r & 1) * 32 + col of word r >> 1, so the four pixels under nibble n of word w are the int4 at
+// 16 w + n -- lane = (tile row, four columns) as in vb_overlap_pack_ref_kernel, and a wave stores a channel's tile as one
+// contiguous KB.  Pixels beyond W / H cost 0.  blockIdx.y = view, blockIdx.z = channel.
+__global__ void __launch_bounds__(256)
+vb_cost_pack_kernel(BinGeom g, const int32_t* __restrict__ cost, int S, int C, int32_t* __restrict__ cpack) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = blockIdx.y, c = blockIdx.z;
+    const int r = lane >> 3, c4 = (lane & 7) * 4;
+    const int32_t* const img = cost + ((size_t)c * S + s) * g.H * g.W;
+    for (int tile = blockIdx.x * 4 + wave; tile < g.nt; tile += gridDim.x * 4) {
+        const int tx = tile % g.ntx, ty = tile / g.ntx;
+        const int ix = tx * EHR_TILE_W + c4, iy = ty * EHR_TILE_H + r;
+        int v[4] = {0, 0, 0, 0};
+        if (iy < g.H) {
+            const int32_t* const row = img + (size_t)(g.H - 1 - iy) * g.W;  // tile rows count from the image's bottom
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (ix + j < g.W) v[j] = row[ix + j];
+        }
+        reinterpret_cast<int4*>(cpack + (((size_t)s * g.nt + tile) * C + c) * 256)[lane] = make_int4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// Sums C per-lane values over the wave, all channels in one pass: the first two exchanges (xor 1, xor 2) halve the channels
+// a lane carries, the other four are a plain butterfly.  Every lane ends with the wave's total of channel lane & 3 (C > 2),
+// lane & 1 (C == 2) or the only one: 6 or 7 64-bit shuffles instead of 6 C.
+template <int C>
+__device__ __forceinline__ long long vb_cost_wave_sum(const long long (&t)[C], int lane) {
+    long long x = t[0];
+    if constexpr (C >= 2) {
+        const bool odd = lane & 1;
+        x = (odd ? t[1] : t[0]) + __shfl_xor(odd ? t[0] : t[1], 1, 64);                 // channel lane & 1
+        if constexpr (C > 2) {
+            const long long t3 = (C > 3) ? t[C - 1] : 0ll;
+            const long long y = (odd ? t3 : t[2]) + __shfl_xor(odd ? t[2] : t3, 1, 64);  // channel 2 + (lane & 1)
+            const bool up = lane & 2;
+            x = (up ? y : x) + __shfl_xor(up ? x : y, 2, 64);                           // channel lane & 3
+        } else {
+            x += __shfl_xor(x, 2, 64);
+        }
+    } else {
+        x += __shfl_xor(x, 1, 64);
+        x += __shfl_xor(x, 2, 64);
+    }
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// Pose search, soft score, last stage of a chunk: per (candidate, view) the integers |render| and, per channel, the sum
+// of the cost under the render.  A wave owns `per_wave` tiles of ONE candidate, a stride of nt / per_wave apart: the covered
+// tiles, where all the fetching is, lie together, and a strided range hands every wave of a candidate about the same
+// number of them (consecutive ranges left a tenth of the waves with all the work).  As in vb_overlap_count_kernel lane
+// 4 s + k fetches coverage word k of view s, 16 views per round trip, four tiles in flight.  Only where a (candidate, view, tile) holds a set bit at all are its cost values fetched, U views a turn so that
+// their loads are in flight together: the wave takes a view's four words by shuffle, lane l looks at nibble l & 15 of word
+// l >> 4 and, if it is not empty, loads the int4 under it per channel (a KB per channel when every lane does); the picked
+// values are summed over the wave in 64 bits (vb_cost_wave_sum) and lane 4 s + c of the view keeps channel c's total next to
+// its word's popcount.  Flushed once per wave and block of 16 views: one 64-bit integer atomic per value on the
+// (candidate, view)'s own 128-byte line {area, sum_0 .. sum_{C-1}} (two's complement: a sum of negative costs wraps to the
+// right int64).  Re-arms the link boxes and hands the PREVIOUS chunk's lines to the caller's packed [.,S,C+1] array with
+// plain stores, like the overlap kernel (the last launch has nq = 0).
+template <int C>
+__global__ void __launch_bounds__(256)
+vb_cost_count_kernel(BinGeom g, int nq, int S, int per_wave, const u64* __restrict__ tcov, const int32_t* __restrict__ cpack,
+                     unsigned long long* __restrict__ cacc, int* __restrict__ lbox, int nlbox,
+                     unsigned long long* __restrict__ prev_cacc, long long* __restrict__ prev_out, int prev_n) {
+    static_assert(C >= 1 && C <= 4, "a view's four lanes keep one channel each");
+    constexpr int U = C <= 2 ? 4 : 2;  // views whose cost loads are in flight together (U C int4 per lane)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nlbox; i += gridDim.x * 256) lbox[i] = (i & 2) ? INT_MIN : INT_MAX;
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < prev_n; i += 256)
+#pragma unroll
+            for (int c = 0; c <= C; c++) {
+                prev_out[(C + 1) * (size_t)i + c] = (long long)prev_cacc[16 * (size_t)i + c];
+                prev_cacc[16 * (size_t)i + c] = 0ull;
+            }
+    const int wq = (g.nt + per_wave - 1) / per_wave;       // waves per candidate
+    const long long wid = (long long)blockIdx.x * 4 + wave;
+    if (wid >= (long long)nq * wq) return;
+    const int q = (int)(wid / wq), r = (int)(wid - (long long)q * wq);  // this wave: tiles r, r + wq, r + 2 wq, .. of candidate q
+    const int k = lane & 3;
+    const int sub = lane >> 4, nib = (lane & 15) * 4;
+    for (int s0 = 0; s0 < S; s0 += 16) {
+        const int ls = s0 + (lane >> 2);
+        const bool on = ls < S;
+        const u64* const cov = tcov + ((size_t)q * g.nt * S + (on ? ls : 0)) * 4 + k;   // + tile * S * 4
+        unsigned area = 0;
+        long long csum = 0;
+        for (int t0 = r; t0 < g.nt; t0 += 4 * wq) {
+            u64 m[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) m[j] = (on && t0 + j * wq < g.nt) ? cov[(size_t)(t0 + j * wq) * S * 4] : 0ull;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int tile = t0 + j * wq;
+                if (tile >= g.nt) break;                      // (wave-uniform)
+                const u64 nz = __ballot(m[j] != 0ull);
+                if (nz == 0) continue;                        // (most tiles hold nothing)
+                area += __popcll(m[j]);
+                u64 vm = (nz | (nz >> 1) | (nz >> 2) | (nz >> 3)) & 0x1111111111111111ull;  // bit 4 v: view s0 + v holds something
+                while (vm) {                                  // (wave-uniform) U views a turn: their loads are in flight together
+                    int sl[U];
+                    unsigned bits[U];
+                    int4 v[U][C];
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        sl[u] = vm ? __builtin_ctzll(vm) : -1;
+                        vm &= vm - 1;
+                        bits[u] = 0;
+                        if (sl[u] >= 0) {
+                            const unsigned lo = (unsigned)__shfl((int)(unsigned)m[j], sl[u] + sub, 64);
+                            const unsigned hi = (unsigned)__shfl((int)(unsigned)(m[j] >> 32), sl[u] + sub, 64);
+                            bits[u] = (unsigned)(((((u64)hi) << 32) | lo) >> nib) & 15u;
+                        }
+                        const int4* const p = reinterpret_cast<const int4*>(cpack + (((size_t)(s0 + (max(sl[u], 0) >> 2)) * g.nt + tile) * C) * 256) + lane;
+#pragma unroll
+                        for (int c = 0; c < C; c++) v[u][c] = bits[u] ? p[c * 64] : make_int4(0, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        if (sl[u] < 0) break;
+                        long long t[C];
+#pragma unroll
+                        for (int c = 0; c < C; c++)
+                            t[c] = (long long)((bits[u] & 1u) ? v[u][c].x : 0) + (long long)((bits[u] & 2u) ? v[u][c].y : 0) +
+                                   (long long)((bits[u] & 4u) ? v[u][c].z : 0) + (long long)((bits[u] & 8u) ? v[u][c].w : 0);
+                        const long long mine = vb_cost_wave_sum<C>(t, lane);
+                        if ((lane & ~3) == sl[u] && k < C) csum += mine;
+                    }
+                }
+            }
+        }
+        area += __shfl_xor(area, 1, 64);
+        area += __shfl_xor(area, 2, 64);
+        if (area) {  // (then the view exists; no coverage, no cost)
+            unsigned long long* const line = cacc + 16 * ((size_t)q * S + ls);
+            if (k == 0) atomicAdd(&line[0], (unsigned long long)area);
+            if (k < C && csum) atomicAdd(&line[1 + k], (unsigned long long)csum);
+        }
+    }
+}
+
 // [T][3] int32 -> [T] int4 (one aligned 16-byte gather per triangle in the silhouette analysis)
 __global__ void vb_pad_kernel(const int32_t* __restrict__ a, int T, int4* __restrict__ out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -4165,6 +4309,90 @@ int ehr::vbuf_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, con
                       hipStream_t stream, int* handled) {
     VbOverlapStage st;
     st.ref = ref; st.overlap = overlap; st.ref_area = ref_area; st.Q = Q; st.S = S;
+    return vb_cov_chain(ctx, verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, stream, handled, st);
+}
+
+// The soft score's own part of the coverage chain's scratch
+struct VbCostMisc {
+    unsigned long long* cacc;   // [2][Bc][16] {area, sum_0 .. sum_{C-1}} of a (candidate, view), one 128-byte line each, double buffered
+    int32_t* cpack;             // [S][nt][C][256] the cost images, tile-major in the coverage words' bit order (1 KB per channel, view and tile)
+};
+static VbCostMisc vb_cost_misc(void* base, size_t Bc, int S, int nt, int C, size_t* bytes = nullptr) {
+    VbCarve c{(uintptr_t)base};
+    VbCostMisc m;
+    m.cacc = c.take<unsigned long long>(2 * 16 * Bc, 128);
+    m.cpack = c.take<int32_t>((size_t)S * nt * C * 256, 128);
+    if (bytes) *bytes = c.at - (uintptr_t)base;
+    return m;
+}
+
+// Last stage of the pose search's soft score: the cost images packed once per call (begin), then vb_cost_count_kernel per
+// chunk, sums collected in VbCostMisc::cacc and handed to `sums` [Q][S][C+1] by the next launch.
+constexpr int VB_COST_WAVE_ITEMS = 8;  // tiles of a candidate a wave of the count kernel owns, at least; only waves that met coverage
+                                       // flush, so a line sees at most nt / 8 atomics per value and mostly far fewer
+struct VbCostStage {
+    const char* op = "ehr_mask_cost";
+    const int32_t* cost;
+    long long* sums;
+    int Q, S, C;
+    VbCostMisc o = {};
+    unsigned long long* prev_cacc = nullptr;
+    long long* prev_out = nullptr;
+    int prev_n = 0, flip = 0;
+    size_t own_bytes(int Bc, int nt) const {
+        size_t bytes;
+        vb_cost_misc(nullptr, Bc, S, nt, C, &bytes);
+        return bytes;
+    }
+    void count(int wgs, const VbCovChunk& c, int nq, int per_wave, unsigned long long* cacc, int nlbox, hipStream_t stream) const {
+        auto go = [&](auto kernel) {
+            kernel<<<wgs, 256, 0, stream>>>(c.g, nq, c.S, per_wave, c.m.tcov, o.cpack, cacc, c.m.lbox, nlbox, prev_cacc, prev_out, prev_n);
+        };
+        switch (C) {
+            case 1: go(vb_cost_count_kernel<1>); break;
+            case 2: go(vb_cost_count_kernel<2>); break;
+            case 3: go(vb_cost_count_kernel<3>); break;
+            default: go(vb_cost_count_kernel<4>); break;
+        }
+    }
+    int begin(const VbCovChunk& c, hipStream_t stream) {
+        o = vb_cost_misc(c.m.own, c.Bc, c.S, c.g.nt, C);
+        EHR_HIP(hipMemsetAsync(o.cacc, 0, 2 * 16 * (size_t)c.Bc * sizeof(unsigned long long), stream));
+        EHR_HIP(hipMemsetAsync(sums, 0, (size_t)Q * c.S * (C + 1) * sizeof(long long), stream));
+        vb_cost_pack_kernel<<<dim3(std::min((c.g.nt + 3) / 4, 256), c.S, C), 256, 0, stream>>>(c.g, cost, c.S, C, o.cpack);
+        EHR_LAUNCH_CHECK();
+        prev_cacc = o.cacc;
+        prev_out = sums;
+        count(64, c, 0, 1, o.cacc, c.nlbox, stream);
+        EHR_LAUNCH_CHECK();
+        return EHR_OK;
+    }
+    int chunk(const VbCovChunk& c, int q0, int nq, hipStream_t stream) {
+        unsigned long long* const cacc = o.cacc + (size_t)flip * 16 * c.Bc;
+        const long long total = (long long)nq * c.g.nt;
+        const long long max_waves = 4ll * VB_SCORE_COUNT_GRID * c.num_cus;
+        const int per_wave = (int)std::max<long long>(VB_COST_WAVE_ITEMS, (total + max_waves - 1) / max_waves);
+        const long long waves = (long long)nq * ((c.g.nt + per_wave - 1) / per_wave);  // (the kernel forms the same quotient)
+        count((int)((waves + 3) / 4), c, nq, per_wave, cacc, c.nlbox, stream);
+        EHR_LAUNCH_CHECK();
+        prev_cacc = cacc;
+        prev_out = sums + (size_t)q0 * c.S * (C + 1);
+        prev_n = nq * c.S;
+        flip ^= 1;
+        return EHR_OK;
+    }
+    int end(const VbCovChunk& c, hipStream_t stream) {
+        count(1, c, 0, 1, o.cacc, 0, stream);
+        EHR_LAUNCH_CHECK();
+        return EHR_OK;
+    }
+};
+
+int ehr::vbuf_cost(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+                   const int32_t* cost, int C, int Q, int S, int L, int V, int T, int H, int W, long long* sums,
+                   hipStream_t stream, int* handled) {
+    VbCostStage st;
+    st.cost = cost; st.sums = sums; st.Q = Q; st.S = S; st.C = C;
     return vb_cov_chain(ctx, verts, tris, vert_link, mvp, Q, S, L, V, T, H, W, stream, handled, st);
 }
 

@@ -282,14 +282,15 @@ def solve_lm_multi(model, batch, starts, max_iters=50, check_every=5, lambda0=1e
 
 
 def solve_global_lm(model, batch, Tc_init, Q, P, max_iters=50, check_every=5, trans_sigma_m=0.03, rot_sigma_deg=4.0, seed=0,
-                    extra=None, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, slack=None):
+                    extra=None, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, slack=None, score="xor", cap_px=None):
     """A global solve that needs no tuning: :func:`easyhec_amd.pose_search.search_starts` (Q candidates scored by mask
     overlap, the best P kept), then :func:`solve_lm_multi` from its starts -> ``(PoseSearchResult, MultiLmResult)``.  The
     winner's accepted dof is written into ``model.dof``; ``history_ops`` and any Adam state stay untouched, as for
     ``solve_lm``.  Hypothesis 0 is ``Tc_init``: it is the plain ``solve_lm`` from there bit for bit, so the winner's loss
-    never exceeds it."""
+    never exceeds it.  ``score`` and ``cap_px`` go to ``search_starts`` (``score="soft"``: the soft IoU, which still ranks
+    candidates that no longer overlap the observed masks, so the draw may be wide)."""
     from .pose_search import search_starts
-    search = search_starts(model, batch, Tc_init, Q, P, trans_sigma_m, rot_sigma_deg, seed, extra=extra)
+    search = search_starts(model, batch, Tc_init, Q, P, trans_sigma_m, rot_sigma_deg, seed, extra=extra, score=score, cap_px=cap_px)
     res = solve_lm_multi(model, batch, search.starts, max_iters=max_iters, check_every=check_every, lambda0=lambda0, ftol=ftol,
                          lambda_max=lambda_max, slack=slack)
     with torch.no_grad():

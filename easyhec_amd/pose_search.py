@@ -5,8 +5,13 @@ starts blind.  Here a few thousand candidate poses are scored against the observ
 (include/ehr.h): per (candidate, view) the exact integers |render|, |render & ref| and |ref|, from
 which the non-antialiased SSE of the solver (``xor``) and the silhouette IoU follow.  The best candidates become the starts
 of :func:`easyhec_amd.multistart.solve_multistart`; start 0 is always the pose the caller already has, and every
-hypothesis equals its solo solve bit for bit, so searching is never worse than not searching.  HIP only: CPU tensors
-raise, there is no fallback."""
+hypothesis equals its solo solve bit for bit, so searching is never worse than not searching.
+
+``xor`` only means something while a candidate still overlaps the observed mask: without overlap it is area + ref_area,
+which ranks a candidate by how small it renders.  ``score="soft"`` ranks by a soft IoU built on the
+exact distance transform of the observed masks (``ehr_mask_distance``) and the cost sums of ``ehr_mask_cost``: it falls
+with the distance to the observed mask for as long as the render is within ``cap_px`` pixels of it, so the candidates may
+be drawn tens of centimetres and degrees wide.  HIP only: CPU tensors raise, there is no fallback."""
 import ctypes
 from dataclasses import dataclass
 
@@ -16,7 +21,8 @@ import torch
 from . import _lib
 from .multistart import rank_losses, sample_starts, solve_multistart
 
-__all__ = ["mask_overlap", "mask_overlap_valid", "overlap_scores", "candidate_mvps", "search_starts", "solve_global", "PoseSearchResult"]
+__all__ = ["mask_overlap", "mask_overlap_valid", "overlap_scores", "mask_distance", "mask_cost", "soft_costs", "soft_iou_scores", "candidate_mvps",
+           "search_starts", "solve_global", "PoseSearchResult"]
 
 
 def mask_overlap(glctx, scene, mvp, ref, chunk_views=0):
@@ -79,6 +85,97 @@ def overlap_scores(inter, area, ref_area):
     return xor, iou.mean(dim=1)
 
 
+def mask_distance(glctx, ref, cap_px):
+    """ref [S,H,W] float masks on the HIP device (row 0 = top, foreground iff > 0.5, NaN is background) -> ``d2 [S,H,W]``
+    int32 on the device: the exact squared Euclidean distance to the nearest foreground pixel of the same view, capped at
+    ``cap_px ** 2`` (0 on the foreground; ``cap_px ** 2`` everywhere in a view without foreground).  ``cap_px`` in
+    [1, 4096].  Launches only: no synchronisation."""
+    if ref.dim() != 3:
+        raise ValueError("ref must be [S,H,W]")
+    if not ref.is_cuda:
+        raise RuntimeError("mask_distance: ref must live on the HIP device (there is no CPU path)")
+    if not _lib.has_soft_search():
+        raise RuntimeError("libehr_hip.so has no ehr_mask_distance: rebuild it (python -m easyhec_amd.build)")
+    S, H, W = (int(n) for n in ref.shape)
+    ref = ref.contiguous().float()
+    d2 = torch.empty((S, H, W), dtype=torch.int32, device=ref.device)
+    with torch.cuda.device(ref.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_lib.lib().ehr_mask_distance(glctx.handle, _lib.ptr(ref), S, H, W, int(cap_px), _lib.ptr(d2), stream),
+                   "ehr_mask_distance")
+    return d2
+
+
+def mask_cost(glctx, scene, mvp, cost, chunk_views=0):
+    """mvp [Q,S,L,4,4] float32 as for :func:`mask_overlap`, cost [S,H,W] or [C,S,H,W] integer images (row 0 = top, any
+    int32 values, C <= 4), both on the HIP device -> ``(area [Q,S], sums [Q,S,C])``, int64 on the device: ``area`` =
+    |render|, ``sums[q,s,c]`` = the sum of ``cost[c,s]`` over the pixels of the render; exact and order independent.  The
+    op reads int32: a wider integer tensor is converted, so its values must fit."""
+    if mvp.dim() != 5 or mvp.shape[-2:] != (4, 4):
+        raise ValueError("mvp must be [Q,S,L,4,4]")
+    if cost.dim() == 3:
+        cost = cost[None]
+    if cost.dim() != 4:
+        raise ValueError("cost must be [S,H,W] or [C,S,H,W]")
+    if not mvp.is_cuda or not cost.is_cuda:
+        raise RuntimeError("mask_cost: tensors must live on the HIP device (there is no CPU path)")
+    if not _lib.has_soft_search():
+        raise RuntimeError("libehr_hip.so has no ehr_mask_cost: rebuild it (python -m easyhec_amd.build)")
+    if cost.dtype.is_floating_point or cost.dtype == torch.bool:
+        raise ValueError("cost must be an integer tensor (its values are summed exactly)")
+    Q, S, L = mvp.shape[:3]
+    C = int(cost.shape[0])
+    if L != scene.num_links:
+        raise ValueError(f"mvp has {L} links, the scene {scene.num_links}")
+    if not 1 <= C <= 4:
+        raise ValueError(f"cost has {C} channels, 1 to 4 are supported")
+    if cost.shape[1] != S:
+        raise ValueError(f"mvp has {S} views, cost {cost.shape[1]}")
+    if cost.device != mvp.device:
+        raise ValueError("mvp and cost must be on the same device")
+    H, W = int(cost.shape[2]), int(cost.shape[3])
+    mvp = mvp.contiguous().float()
+    cost = cost.contiguous().to(torch.int32)
+    sums = torch.empty((Q, S, C + 1), dtype=torch.int64, device=mvp.device)
+    with torch.cuda.device(mvp.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_lib.lib().ehr_mask_cost(glctx.handle, _lib.ptr(scene.verts), _lib.ptr(scene.tris), _lib.ptr(scene.vert_link),
+                                            _lib.ptr(mvp), _lib.ptr(cost), C, Q, S, L, scene.num_verts, scene.num_tris, H, W,
+                                            _lib.ptr(sums), int(chunk_views), stream), "ehr_mask_cost")
+    return sums[..., 0], sums[..., 1:]
+
+
+def soft_iou_scores(area, inter, ksum, ref_area, cap_px):
+    """``soft [Q]`` float64 from the integers of :func:`mask_cost` (any device): per (candidate, view)
+    ``ksum / (cap_px * union)`` with ``union = area + ref_area - inter`` (1.0 where the union is empty), then the mean over
+    the views.  ``ksum`` is the sum over the render of ``k = cap_px - floor(sqrt(d2))``: ``cap_px`` on the reference,
+    falling to 0 at ``cap_px`` pixels from it, so ``ksum <= cap_px * area <= cap_px * union`` and
+
+    * ``0 <= soft <= 1``;
+    * ``soft == 1`` iff every view renders exactly its reference (every rendered pixel on the reference and none of the
+      reference left over);
+    * ``soft == 0`` iff no render comes within ``cap_px`` pixels of its reference (a render that left the image
+      included)."""
+    area, inter, ksum = torch.as_tensor(area).long(), torch.as_tensor(inter).long(), torch.as_tensor(ksum).long()
+    ra = torch.as_tensor(ref_area).long().to(area.device)[None, :]
+    union = area + ra - inter
+    soft = torch.where(union > 0, ksum.double() / (float(cap_px) * union.clamp(min=1).double()),
+                       torch.ones_like(union, dtype=torch.float64))
+    return soft.mean(dim=1)
+
+
+def soft_costs(d2, cap_px, valid=None):
+    """The cost images of the soft score from ``d2 [S,H,W]`` (:func:`mask_distance`), int32 on its device:
+    ``[fg, k]`` with ``fg = d2 == 0`` and ``k = cap_px - floor(sqrt(d2))`` (in float64: exact for every d2 <= 4096 ** 2), or
+    ``[fg & valid, k * valid, valid]`` under a bool ``valid [S,H,W]``."""
+    fg = (d2 == 0).to(torch.int32)
+    k = int(cap_px) - torch.floor(torch.sqrt(d2.double())).to(torch.int32)
+    if valid is None:
+        return torch.stack([fg, k])
+    v = valid.to(torch.int32)
+    return torch.stack([fg * v, k * v, v])
+
+
 def candidate_mvps(K, H, W, Tc_c2b, link_poses, n=0.001, f=10.0):
     """[Q,Bv,L,4,4] = proj(K) @ (opencv2blender @ (Tc_c2b[q] @ link_poses[v,l])): the projection, flip and association of
     :func:`easyhec_amd.fused.mvp_matrices`, for Q candidate poses in one batched expression on Tc_c2b's device."""
@@ -95,19 +192,29 @@ class PoseSearchResult:
     candidates: np.ndarray      # [Q(+extra),4,4] float64 every scored pose; candidate 0 is Tc_init
     xor: torch.Tensor           # [Q] int64 (CPU): sum over the views of |render xor ref|
     iou: torch.Tensor           # [Q] float64 (CPU): mean silhouette IoU over the views
-    ranking: list               # candidate indices, best (smallest xor) first, ties by index
+    ranking: list               # candidate indices, best first (smallest xor, or largest soft), ties by index
     inter: torch.Tensor         # [Q,Bv] int64 (CPU)
     area: torch.Tensor          # [Q,Bv] int64 (CPU)
     ref_area: torch.Tensor      # [Bv] int64 (CPU)
+    soft: torch.Tensor = None   # [Q] float64 (CPU): the soft IoU (soft_iou_scores); None under score="xor"
+    score: str = "xor"          # what `ranking` was made by
 
 
-def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg=4.0, seed=0, extra=None, chunk_views=0):
+def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg=4.0, seed=0, extra=None, chunk_views=0,
+                  score="xor", cap_px=None):
     """Scores Q candidate poses around ``Tc_init`` (:func:`easyhec_amd.multistart.sample_starts`: candidate 0 is ``Tc_init``
     itself; ``extra`` [E,4,4]: further poses of the caller's, scored after them) against ``batch['mask']`` in one
     :func:`mask_overlap` call and returns the P starts for :func:`easyhec_amd.multistart.solve_multistart`: start 0 is
     ALWAYS ``Tc_init``, then the best P - 1 other candidates by ``xor`` (ascending, ties by index).  With per-pixel weights
     (``batch['weight']``) the candidates are ranked on the valid pixels only (:func:`mask_overlap_valid`); the integers
-    returned are then the restricted ones."""
+    returned are then the restricted ones.
+
+    ``score="soft"``: one :func:`mask_distance` of the masks (``cap_px``, default ``max(H, W) // 4``) and one
+    :func:`mask_cost` call instead; the candidates are ranked by :func:`soft_iou_scores`, descending, ties by index.
+    ``xor`` and ``iou`` are still filled in, from the same call's integers.  Under weights every cost image is multiplied
+    by ``valid = weight > 0`` and a third channel gives the restricted area."""
+    if score not in ("xor", "soft"):
+        raise ValueError(f"search_starts: score must be 'xor' or 'soft', got {score!r}")
     for k in ("mask", "link_poses", "K"):
         if not torch.is_tensor(batch[k]) or batch[k].device.type != "cuda":
             raise RuntimeError(f"search_starts: batch['{k}'] must be a tensor on the HIP device (there is no CPU path)")
@@ -122,6 +229,28 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
     ref = batch["mask"].to(dev, torch.float32)
     lp = batch["link_poses"].to(dev, torch.float32)
     mvp = candidate_mvps(batch["K"][0].to(dev, torch.float32), H, W, torch.tensor(cands, dtype=torch.float32, device=dev), lp)
+    if score == "soft":
+        glctx, scene = model._ensure_renderer().glctx, model._ensure_scene()
+        cap = max(H, W) // 4 if cap_px is None else int(cap_px)
+        d2 = mask_distance(glctx, ref, cap)
+        valid = None
+        if batch.get("weight") is not None:
+            if batch["weight"].shape != ref.shape:
+                raise ValueError("weight must have the masks' shape")
+            valid = batch["weight"].to(dev) > 0
+        cost = soft_costs(d2, cap, valid)
+        area, sums = mask_cost(glctx, scene, mvp, cost, chunk_views=chunk_views)
+        inter, ksum = sums[..., 0], sums[..., 1]
+        if valid is not None:
+            area = sums[..., 2]
+        ref_area = cost[0].sum(dim=(1, 2), dtype=torch.int64)
+        soft = soft_iou_scores(area, inter, ksum, ref_area, cap).cpu()
+        xor, iou = overlap_scores(inter, area, ref_area)
+        xor, iou = xor.cpu(), iou.cpu()
+        ranking = rank_losses(-soft.numpy())
+        picked = [0] + [i for i in ranking if i != 0][:P - 1]
+        return PoseSearchResult(starts=cands[picked].copy(), candidates=cands, xor=xor, iou=iou, ranking=ranking,
+                                inter=inter.cpu(), area=area.cpu(), ref_area=ref_area.cpu(), soft=soft, score="soft")
     if batch.get("weight") is not None:
         inter, area, ref_area = mask_overlap_valid(model._ensure_renderer().glctx, model._ensure_scene(), mvp, ref,
                                                    batch["weight"].to(dev, torch.float32), chunk_views=chunk_views)
@@ -137,9 +266,10 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
 
 
 def solve_global(cfg, model, batch, Tc_init, Q, P, num_steps, trans_sigma_m=0.03, rot_sigma_deg=4.0, seed=0, tail=20,
-                 slack=None, extra=None):
+                 slack=None, extra=None, score="xor", cap_px=None):
     """:func:`search_starts`, then :func:`easyhec_amd.multistart.solve_multistart` from its starts ->
     ``(PoseSearchResult, MultiStartResult)``; ``model.dof`` holds the winner.  Hypothesis 0 is the plain solve from
-    ``Tc_init``, bit for bit, so the winner's tail loss never exceeds it."""
-    search = search_starts(model, batch, Tc_init, Q, P, trans_sigma_m, rot_sigma_deg, seed, extra=extra)
+    ``Tc_init``, bit for bit, so the winner's tail loss never exceeds it.  ``score`` and ``cap_px`` go to
+    :func:`search_starts`."""
+    search = search_starts(model, batch, Tc_init, Q, P, trans_sigma_m, rot_sigma_deg, seed, extra=extra, score=score, cap_px=cap_px)
     return search, solve_multistart(cfg, model, batch, search.starts, num_steps, tail=tail, slack=slack)

@@ -404,6 +404,38 @@ int ehr_mask_overlap(ehr_ctx* ctx, const float* verts, const int32_t* tris, cons
                      const float* ref, int Q, int S, int L, int V, int T, int H, int W, int64_t* overlap,
                      int64_t* ref_area, int chunk_views, void* stream);
 
+/* Pose search, soft score.  |render xor ref| ranks a candidate that no longer overlaps the observed
+ * mask by how SMALL it renders; a cost image built from the distance to the observed mask ranks it by how FAR it is.
+ *
+ * ehr_mask_distance: exact capped squared Euclidean distance transform of the observed masks.
+ *   ref [S,H,W] float32, row 0 = top; a pixel is foreground iff ref > 0.5f (NaN is background): ehr_mask_overlap's rule;
+ *   d2 [S,H,W] int32 (device) = min(cap_px^2, min over the foreground (x', y') of (x - x')^2 + (y - y')^2): 0 on the
+ *   foreground, cap_px^2 everywhere in a view without foreground;
+ *   cap_px in [1, 4096], else EHR_ERR_INVALID with a message.
+ * Two passes, every decision in integers (column distances as u16, then per row the minimum of dx^2 + g^2 over the
+ * columns within the cap, from an LDS-staged window): exact for every cap_px in the range, no float rounding anywhere.
+ * The call only launches on `stream`: no synchronisation, nothing read back.  Its scratch (2 bytes per pixel) comes from
+ * the context and only grows: once a call of the same size has been made the call is capturable in a hipGraph.
+ *
+ * ehr_mask_cost: per (candidate, view) the sums of up to four int32 cost images under the render.
+ *   verts .. mvp, Q, S, L, V, T, H, W: as for ehr_mask_overlap (same render rule, same argument limits);
+ *   cost [C,S,H,W] int32, row 0 = top, any values; C in [1, 4];
+ *   sums [Q,S,C+1] int64 (device): {area, sum_0, .., sum_{C-1}} with area = |render| and
+ *   sum_c = sum over the pixels of the render of cost[c,s,pixel].
+ * The sums are exact and independent of launch order (64-bit integer atomics only; H W <= 2^30, so they cannot overflow).
+ * Same two implementations as ehr_mask_overlap, same chunk_views and EHR_SCORE_PATH.  On the coverage chain the cost
+ * images are packed once per call into a tile-major layout in the coverage words' bit order (1 KB per channel, view and
+ * 32x8 tile; pixels beyond W or H cost 0), and per chunk of candidates a count kernel fetches the values only under
+ * (candidate, view, tile) words that are not zero.  If coverage cannot decide a pixel the WHOLE call is redone by the
+ * per-triangle tile implementation on the Q x S single-pose views, in passes of at most chunk_views views (<= 0: 512),
+ * each reduced against the cost images to the same integers.  Like ehr_mask_overlap the call synchronises and may
+ * allocate: NOT capturable.
+ * ehr_version() is unchanged: the presence of these two symbols is the capability check. */
+int ehr_mask_distance(ehr_ctx* ctx, const float* ref, int S, int H, int W, int cap_px, int32_t* d2, void* stream);
+int ehr_mask_cost(ehr_ctx* ctx, const float* verts, const int32_t* tris, const int32_t* vert_link, const float* mvp,
+                  const int32_t* cost, int C, int Q, int S, int L, int V, int T, int H, int W, int64_t* sums,
+                  int chunk_views, void* stream);
+
 /* Joint-offset calibration: the joint zero errors of the arm are fitted together with the camera pose.  Two small kernels
  * AROUND the launch chain of ehr_solver_step, which itself is unchanged: it reads link_poses from device memory on every call
  * and leaves grad_mvp [B,L,16] and the pose it rendered (tc_jac[0:16]) behind.  A step is
