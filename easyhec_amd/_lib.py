@@ -113,98 +113,60 @@ def lib():
     return _lib
 
 
-def has_multistart():
-    """True if the library has the multi-start step (``ehr_solver_step_multi``).  The ABI version did not change with it:
-    the symbol's presence is the capability check (looked up on the bare library, so it also answers for an ``EHR_LIB``
-    build that predates it, which :func:`lib` would refuse to bind)."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_solver_step_multi")
-
-
-def has_pose_search():
-    """True if the library has the pose search's overlap op (``ehr_mask_overlap``); the symbol's presence is the capability
-    check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_overlap")
-
-
-def has_soft_search():
-    """True if the library has the pose search's soft score (``ehr_mask_distance`` and ``ehr_mask_cost``); the symbols'
-    presence is the capability check, as for :func:`has_pose_search`."""
+def has_symbols(*names):
+    """True if the library exports every one of ``names``.  The ABI version does not change when an entry is added: the
+    symbols' presence is the capability check, looked up on the bare library (the loaded one where there is one), so it also
+    answers for an ``EHR_LIB`` build that predates them, which :func:`lib` would refuse to bind.  False where the file is
+    missing."""
     if not os.path.exists(LIB_PATH):
         return False
     so = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
-    return hasattr(so, "ehr_mask_distance") and hasattr(so, "ehr_mask_cost")
+    return all(hasattr(so, n) for n in names)
+
+
+# what each feature needs of the library (the names tests and tools ask by)
+def has_multistart():
+    return has_symbols("ehr_solver_step_multi")
+
+
+def has_pose_search():
+    return has_symbols("ehr_mask_overlap")
+
+
+def has_soft_search():
+    return has_symbols("ehr_mask_distance", "ehr_mask_cost")
 
 
 def has_weighted_loss():
-    """True if the library has the per-pixel weights of the mask loss (``ehr_fused_bind_weight``); the symbol's presence is
-    the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_fused_bind_weight")
+    return has_symbols("ehr_fused_bind_weight")
 
 
 def has_joint_offsets():
-    """True if the library has the joint-offset kernels (``ehr_joint_forward`` / ``ehr_joint_backward_adam``); the symbols'
-    presence is the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
-    return hasattr(l, "ehr_joint_forward") and hasattr(l, "ehr_joint_backward_adam")
+    return has_symbols("ehr_joint_forward", "ehr_joint_backward_adam")
 
 
 def has_rig():
-    """True if the library has the camera rig's finish stage (``ehr_rig_backward_adam``); the symbol's presence is the
-    capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_rig_backward_adam")
+    return has_symbols("ehr_rig_backward_adam")
 
 
 def has_intrinsics():
-    """True if the library has the intrinsics refinement's kernel (``ehr_intrinsics_backward_adam``); the symbol's presence
-    is the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_intrinsics_backward_adam")
+    return has_symbols("ehr_intrinsics_backward_adam")
 
 
 def has_information():
-    """True if the library has the information matrix of the mask loss (``ehr_mask_information``); the symbol's presence is
-    the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    return hasattr(_lib if _lib is not None else ctypes.CDLL(LIB_PATH), "ehr_mask_information")
+    return has_symbols("ehr_mask_information")
 
 
 def has_lm():
-    """True if the library has the Levenberg-Marquardt kernels (``ehr_lm_linearize`` / ``ehr_lm_update``); the symbols'
-    presence is the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
-    return hasattr(l, "ehr_lm_linearize") and hasattr(l, "ehr_lm_update")
+    return has_symbols("ehr_lm_linearize", "ehr_lm_update")
 
 
 def has_lm_multi():
-    """True if the library has the multi-start Levenberg-Marquardt kernels (``ehr_lm_linearize_multi`` /
-    ``ehr_lm_update_multi``); the symbols' presence is the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
-    return hasattr(l, "ehr_lm_linearize_multi") and hasattr(l, "ehr_lm_update_multi")
+    return has_symbols("ehr_lm_linearize_multi", "ehr_lm_update_multi")
 
 
 def has_information_gain():
-    """True if the library has the exploration kernels (``ehr_information_gain`` / ``ehr_information_pick``); the symbols'
-    presence is the capability check, as for :func:`has_multistart`."""
-    if not os.path.exists(LIB_PATH):
-        return False
-    l = _lib if _lib is not None else ctypes.CDLL(LIB_PATH)
-    return hasattr(l, "ehr_information_gain") and hasattr(l, "ehr_information_pick")
+    return has_symbols("ehr_information_gain", "ehr_information_pick")
 
 
 IG_MAX_PARAMS = 32  # include/ehr.h: EHR_IG_MAX_PARAMS

@@ -1,11 +1,16 @@
-"""``_ChainStep`` -- what :class:`easyhec_amd.fast.FusedPoseStep` and :class:`easyhec_amd.multistart.MultiStartPoseStep`
-have in common: a plan on a rasterizer context with the reference masks bound to it, a launch chain that is enqueued or
-replayed from the context's hipGraph, and the protocol around a REPORTED step (NaN loss, pose and Adam untouched: the
-slot-limited plan overflowed, or the view needs the general-triangle pass) -- the non-blocking look at the loss, the
-recovery, and the loop that takes an exact number of effective steps.
+"""``_PlannedContext`` and ``_ChainStep``.
 
-A subclass sets ``glctx``, ``scene``, ``dev``, ``H``, ``W``, ``B`` (the views the plan holds), ``ref`` (the masks, shared by
-``B / ref.shape[0]`` poses), ``weight`` (per-pixel weights of the loss shaped like ``ref``, or None) and ``loss`` (one element
+``_PlannedContext`` -- what everything that renders through a plan of its own has in common
+(:class:`easyhec_amd.fast.FusedPoseStep`, :class:`easyhec_amd.multistart.MultiStartPoseStep`,
+:class:`easyhec_amd.lm_multi.MultiStartLM`): the job-slot policy, the plan on a rasterizer context with the weights and the
+reference masks bound to it, and what the context's status says after a REPORTED call (NaN loss, parameters untouched: the
+slot-limited plan overflowed, or the view needs the general-triangle pass).  A user sets ``glctx``, ``scene``, ``H``, ``W``,
+``B`` (the views the plan holds), ``ref`` (the masks, shared by ``B / ref.shape[0]`` poses) and ``weight`` (per-pixel weights
+of the loss shaped like ``ref``, or None), and calls :meth:`_PlannedContext._init_plan`.
+
+``_ChainStep`` -- the two Adam steppers on top of it: a launch chain that is enqueued or replayed from the context's
+hipGraph, and the protocol around a reported step -- the non-blocking look at the loss, the recovery with its graph
+handling, and the loop that takes an exact number of effective steps.  A subclass also sets ``dev`` and ``loss`` (one element
 per pose), provides ``_enqueue(want_mask, stream=None)`` and
 ``steps_done`` (Adam's own counter, which only advances on real steps; reading it synchronises), and ends its constructor
 with :meth:`_init_chain`."""
@@ -86,12 +91,12 @@ class _ReportedStepProtocol:
         return hist[~torch.isnan(hist).all(dim=1)]  # (reported steps: NaN in every element, taken by nobody)
 
 
-class _ChainStep(_ReportedStepProtocol):
-    def _init_chain(self, slack):
+class _PlannedContext:
+    def _init_plan(self, slack):
         # job slots: `slack` per view tile (default: half as many slots as a view has tiles) instead of one per (view,
         # link, tile) -- 30 MB instead of 0.48 GB of scratch at 8 views 720p x 8 links; the workloads here use a tenth of
         # that (a robot's links touch ~5 % of a frame's tiles).  A view that needs more (every pixel under more than
-        # `slack` link boxes on average: a close-up) is REPORTED -- NaN loss, dof and Adam state untouched -- and
+        # `slack` link boxes on average: a close-up) is REPORTED -- NaN loss, parameters untouched -- and
         # :meth:`recover_from_overflow` plans again with a slot for every (view, link, tile).  EHR_VB_SLACK overrides (0 = all).
         # (Small images: at least 256 slots per view -- a link's box touches a few tiles however small the frame is.)
         if slack is None and "EHR_VB_SLACK" not in os.environ:
@@ -100,8 +105,6 @@ class _ChainStep(_ReportedStepProtocol):
         else:
             self.slack = float(os.environ["EHR_VB_SLACK"]) if slack is None else float(slack)
         self._plan_and_bind()
-        self._graph = None
-        self._init_protocol()  # (a NaN seen there triggers recover_from_overflow(); `recoveries` notes what it did)
 
     def _plan_and_bind(self):
         fused._ensure_plan(self.glctx, self.scene, self.B, self.H, self.W, slack=self.slack)
@@ -112,6 +115,40 @@ class _ChainStep(_ReportedStepProtocol):
         if weight is not None or getattr(self.glctx, "_bound_weight", None) is not None:
             fused.bind_weight(self.glctx, self.scene, weight, views=self.B)
         fused.bind_ref(self.glctx, self.scene, self.ref, views=self.B)
+
+    def _overflow_status(self):
+        """What the context reports (``ehr_fused_status``; synchronises): False (nothing), "general-triangle pass"
+        (EHR_ERR_RETRY: the call met triangles for that pass, and the context launches it from now on) or "job slots" (the
+        slot-limited plan overflowed).  Raises on an overflow of a plan that already has every slot."""
+        with torch.cuda.device(self.glctx.device):
+            rc = _lib.lib().ehr_fused_status(self.glctx.handle)
+        if rc == 0:
+            return False
+        if rc == _lib.EHR_ERR_RETRY:
+            return "general-triangle pass"
+        if self.slack == 0.0:
+            _lib.check(rc, "fused render")
+        return "job slots"
+
+    def _plan_every_slot(self):
+        self.slack = 0.0
+        self._plan_and_bind()
+
+    def recover_from_overflow(self):
+        """Call when calls were reported (NaN loss).  Synchronises.  Returns what :meth:`_overflow_status` found; after
+        "job slots" the context is planned again with a slot for every (view, link, tile), the weights and the reference
+        bound again.  The reported calls changed nothing, so the caller simply goes on."""
+        what = self._overflow_status()
+        if what == "job slots":
+            self._plan_every_slot()
+        return what
+
+
+class _ChainStep(_PlannedContext, _ReportedStepProtocol):
+    def _init_chain(self, slack):
+        self._init_plan(slack)
+        self._graph = None
+        self._init_protocol()  # (a NaN seen there triggers recover_from_overflow(); `recoveries` notes what it did)
 
     def _host_copies_stale(self):
         """Called where the chain has written, or is about to write, device state that the host may hold a copy of."""
@@ -175,29 +212,20 @@ class _ChainStep(_ReportedStepProtocol):
         if the context reports nothing: the steps since the report changed nothing (dof, Adam moments and step counter stay
         untouched on a NaN, and the chain's head writes the unchanged pose to the SAME history row again: include/ehr.h,
         ehr_solver_step), so the caller simply goes on stepping.  Raises on any other overflow."""
-        with torch.cuda.device(self.glctx.device):
-            rc = _lib.lib().ehr_fused_status(self.glctx.handle)
         # (on every rank of a data-parallel job alike, whichever rank's views caused the report: the reduced loss was NaN for
         #  all of them, none of them stepped, and each of them kept recording the unchanged pose in one and the same row)
         self._host_copies_stale()
-        if rc == 0:
-            return False
-        had_graph = bool(self._graph)
-        if rc == _lib.EHR_ERR_RETRY:
-            # the step met triangles for the general-triangle pass, which the chain had not been launching: the context
-            # has switched it on; a captured chain is recorded again with it
+        what = self._overflow_status()
+        if what:
+            # "general-triangle pass": the chain had not been launching it, so a captured chain is recorded again with it;
+            # "job slots": the graph is released before the plan it was recorded on is replaced
+            had_graph = bool(self._graph)
+            self.release_graph()
+            if what == "job slots":
+                self._plan_every_slot()
             if had_graph:
-                self.release_graph()
                 self.capture()
-            return "general-triangle pass"
-        if self.slack == 0.0:
-            _lib.check(rc, "fused render")
-        self.release_graph()
-        self.slack = 0.0
-        self._plan_and_bind()
-        if had_graph:
-            self.capture()
-        return "job slots"
+        return what
 
     def _recover_and_note(self):
         what = self.recover_from_overflow()

@@ -87,6 +87,18 @@ def _private_weight(batch, dev):
     return None if w is None else w.to(dev, torch.float32).contiguous().clone()
 
 
+def _hip_device(who, model, batch):
+    """The model's device, after the one check of everything that takes a model and a batch without a step object: the
+    model and ``batch['mask' | 'link_poses' | 'K']`` on a HIP device, else raise in ``who``'s name."""
+    dev = model.dof.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who} runs on a HIP device only: move the model with .cuda() first (there is no CPU path)")
+    for k in ("mask", "link_poses", "K"):
+        if not torch.is_tensor(batch[k]) or batch[k].device.type != "cuda":
+            raise RuntimeError(f"{who}: batch['{k}'] must be a tensor on the HIP device")
+    return dev
+
+
 def refuse_unsupported(kw, available, starts, data_parallel, missing):
     """The refusals every solve built on ``FusedPoseStep`` makes before it constructs one, each raised with the caller's
     own reason: ``starts=`` among the keywords ``kw`` (a call ported from ``MultiStartPoseStep`` gets the reason, not a

@@ -16,7 +16,12 @@ It is a refinement BESIDE Adam, not a new default: it does not touch Adam's mome
 weight decay (no prior towards the given intrinsics or zero offsets), and far from the optimum its quadratic model is poor
 (the squared error of binary silhouettes is linear in the displacement): the accept / reject rule, not the model, makes it
 safe.  It renders the float32 matrix ``ehr_pose_forward`` builds -- the loss it minimises is the loss the Adam solve reports,
-bit for bit -- where :func:`easyhec_amd.information.information_of` renders a float64-built one.  HIP only; no fallback."""
+bit for bit -- where :func:`easyhec_amd.information.information_of` renders a float64-built one.  HIP only; no fallback.
+
+The iteration and the solve loop are written once, for P state blocks: ``_LmDriver`` owns the
+buffers, the guard, ``iterate`` / ``finalize`` and the reading of the state, ``_run_to_convergence`` the polling loop.
+:class:`LevenbergMarquardt` is the driver with one block on a step object's context;
+:class:`easyhec_amd.lm_multi.MultiStartLM` is the driver with P blocks on a context of its own."""
 import ctypes
 import types
 from dataclasses import dataclass, field
@@ -101,49 +106,109 @@ def state_namespace(s, N):
     return ns
 
 
-class LevenbergMarquardt:
+class _LmDriver:
+    """The Levenberg-Marquardt iteration for P state blocks, whatever it drives: the buffers, the guard, the launch chain
+    of an iteration and the reading of the state.  A subclass sets what it renders with -- ``glctx``, ``scene``, ``ref``,
+    ``weight``, ``B`` (the views of the plan), ``H``, ``W``, ``L``, ``dev``, ``N``, ``names`` -- then calls
+    :meth:`_init_driver`, and provides the two C calls ``_linearize(stream)`` and ``_update(stream, finalize=0)``.
+    ``_forward_kinematics(stream)``, where a subclass has one, is launched ahead of every linearisation and behind the
+    finalising update.  ``who`` names the owner in the guard's messages."""
+    who, _forward_kinematics = "solve_lm", None
+
+    def _init_driver(self, P, lambda0, ftol, lambda_max, log_rows):
+        N, B, L, dev = self.N, self.B, self.L, self.dev
+        if N > _lib.LM_MAX_PARAMS:
+            raise ValueError(f"{self.who}: the step optimises {N} parameters; the kernels take {_lib.LM_MAX_PARAMS}")
+        self.P = P
+        self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
+        self.mvp = torch.empty((B, L, 4, 4), device=dev)
+        self.dmvp = torch.empty((N, B, L, 4, 4), device=dev)
+        self.out = information._outputs(N, B, L, dev, True, False)
+        st = np.zeros((P, _lib.LM_STATE_DOUBLES))
+        st[:, _lib.LM_STATE["lambda"]], st[:, _lib.LM_STATE["nu"]] = self.lambda0, 2.0
+        self.state_block = self._state = torch.from_numpy(st).to(dev)  # (a subclass may publish views of the two)
+        self.log_rows = int(log_rows)
+        self.log = self._log = torch.full((P, self.log_rows, 4), float("nan"), dtype=torch.float64, device=dev)
+        self.calls = 0  # iterations enqueued so far: a hypothesis's `iterations` falls behind it once it is done
+
+    # -- guards: the context is shared state; never iterate on a plan or on weights that are not the owner's -----------------
+    def _guard(self):
+        plan = getattr(self.glctx, "_plan", None)
+        if plan is None or plan.key != fused._plan_key(self.scene, self.B, self.H, self.W):
+            raise RuntimeError(f"{self.who}: its context holds another plan (somebody else rendered with it): plan and "
+                               "bind again first (a step object does when it takes a step)")
+        if getattr(self.glctx, "_bound_weight", None) is not self.weight:
+            raise RuntimeError(f"{self.who}: the weights bound to its context are not its own (somebody else used the "
+                               "context): bind them again first (a step object does when it takes a step)")
+        if self.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self.who}: not available while a graph is being captured")
+
+    def iterate(self, n=1):
+        """Enqueue ``n`` iterations (of every hypothesis) on the current stream; never synchronises.  After ``done`` an
+        iteration only restores the accepted parameters."""
+        self._guard()
+        o, forward_kinematics = self.out, self._forward_kinematics
+        with torch.cuda.device(self.dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for _ in range(int(n)):
+                if forward_kinematics is not None:
+                    forward_kinematics(stream)
+                self._linearize(stream)
+                information._launch(self.glctx, self.scene, self.mvp, self.dmvp, self.ref, o.info, o.grad, o.count, o.loss, None)
+                self._update(stream)
+                self.calls += 1
+        return self
+
+    def finalize(self):
+        """Leave the ACCEPTED parameters in the owner's tensors.  Enqueued; never synchronises."""
+        with torch.cuda.device(self.dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self._update(stream, finalize=1)
+            if self._forward_kinematics is not None:
+                self._forward_kinematics(stream)
+        return self
+
+    def states(self):
+        """The P state blocks as a list of namespaces (one copy of [P,EHR_LM_STATE_DOUBLES]; synchronises): lambda, nu,
+        F_acc, pred, rho, F_trial, the counters iterations / accepted / rejected / reported / retries, done, why, last,
+        count, and theta [N], delta [N], g [N], H [N,N] of the accepted point."""
+        s = self._state.cpu().numpy()
+        return [state_namespace(s[p], self.N) for p in range(self.P)]
+
+    def trajectory(self, p):
+        """Hypothesis p's [iterations, 4] float64 (CPU): per iteration the trial's loss (NaN: reported), 1 accepted / 0
+        rejected / -1 reported, lambda after the iteration, and the gain ratio rho (NaN unless accepted).  Synchronises."""
+        n = min(int(self._state[p, _lib.LM_STATE["iterations"]].item()), self.log_rows)
+        return self._log[p, :n].cpu().numpy()
+
+    def report(self, p, state=None):
+        """The :class:`easyhec_amd.information.InformationReport` of hypothesis p's accepted point, from its state block."""
+        s = self.states()[p] if state is None else state
+        return information.InformationReport(s.H[None], self.names, s.g[None], [s.count], [s.F_acc])
+
+
+class LevenbergMarquardt(_LmDriver):
     """Drives ``step`` (``FusedPoseStep``, ``JointPoseStep``, ``IntrinsicsPoseStep`` or ``JointIntrinsicsPoseStep``) by
     Levenberg-Marquardt iterations on the parameters it optimises, in the order of
     :func:`easyhec_amd.information.information_of` (``names``).  ``lambda0``, ``ftol``, ``lambda_max``: the damping's start,
     and the stopping rule's two thresholds (include/ehr.h, ``ehr_lm_update``); ``log_rows``: iterations the device log holds.
 
     ``iterate(n)`` enqueues n iterations and never synchronises; ``state()`` makes one small copy; ``finalize()`` leaves the
-    accepted parameters in the step's tensors (a trial is in them between iterations)."""
+    accepted parameters in the step's tensors (``model.dof``, the offsets, ``theta`` and ``K``; the link poses follow the
+    offsets; a trial is in them between iterations).  ``state_block`` [EHR_LM_STATE_DOUBLES] and ``log`` [log_rows,4] are the
+    one hypothesis's."""
 
     def __init__(self, step, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256):
         _refuse(step)
         self.step, self.dev = step, step.dev
-        self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
-        dev = self.dev
+        self.glctx, self.scene, self.ref, self.weight = step.glctx, step.scene, step.ref, getattr(step, "weight", None)
+        self.B, self.L, self.H, self.W = step.B, step.L, step.H, step.W
         self.layout = lay = parameter_layout(step)
-        self.names, self.kin, self.F, self.J = lay.names, lay.kin, lay.F, lay.J
+        self.names, self.N, self.kin, self.F, self.J = lay.names, lay.N, lay.kin, lay.F, lay.J
         self.free4_mask, self.tie_focal = lay.free4_mask, lay.tie_focal
-        self.free_list = torch.tensor(lay.free, dtype=torch.int32, device=dev) if lay.free else None
-        self.N = N = lay.N
-        if N > _lib.LM_MAX_PARAMS:
-            raise ValueError(f"solve_lm: the step optimises {N} parameters; the kernels take {_lib.LM_MAX_PARAMS}")
-        B, L = step.B, step.L
-        self.mvp = torch.empty((B, L, 4, 4), device=dev)
-        self.dmvp = torch.empty((N, B, L, 4, 4), device=dev)
-        self.out = information._outputs(N, B, L, dev, True, False)
-        st = np.zeros(_lib.LM_STATE_DOUBLES)
-        st[_lib.LM_STATE["lambda"]], st[_lib.LM_STATE["nu"]] = self.lambda0, 2.0
-        self.state_block = torch.from_numpy(st).to(dev)
-        self.log_rows = int(log_rows)
-        self.log = torch.full((self.log_rows, 4), float("nan"), dtype=torch.float64, device=dev)
-
-    # -- guards: the context is shared state; never iterate on a plan or on weights that are not the step's ------------------
-    def _guard(self):
-        st = self.step
-        plan = getattr(st.glctx, "_plan", None)
-        if plan is None or plan.key != fused._plan_key(st.scene, st.B, st.H, st.W):
-            raise RuntimeError("solve_lm: the step's context holds another plan (somebody else rendered with it): take a "
-                               "step first, which plans and binds again")
-        if getattr(st.glctx, "_bound_weight", None) is not getattr(st, "weight", None):
-            raise RuntimeError("solve_lm: the weights bound to the step's context are not the step's (somebody else used "
-                               "the context): take a step first, which binds them again")
-        if st.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("solve_lm: not available while a graph is being captured")
+        self.free_list = torch.tensor(lay.free, dtype=torch.int32, device=self.dev) if lay.free else None
+        self._init_driver(1, lambda0, ftol, lambda_max, log_rows)
+        self.state_block, self.log = self._state[0], self._log[0]  # (views: the same memory)
 
     def _linearize(self, stream):
         st = self.step
@@ -164,45 +229,17 @@ class LevenbergMarquardt:
         if self.kin is not None:
             self.kin.launch(self.step, stream)
 
-    def iterate(self, n=1):
-        """Enqueue ``n`` iterations on the current stream; never synchronises.  After ``done`` an iteration only restores the
-        accepted parameters."""
-        self._guard()
-        st, o = self.step, self.out
-        with torch.cuda.device(self.dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for _ in range(int(n)):
-                self._forward_kinematics(stream)
-                self._linearize(stream)
-                information._launch(st.glctx, st.scene, self.mvp, self.dmvp, st.ref, o.info, o.grad, o.count, o.loss, None)
-                self._update(stream)
-        return self
-
-    def finalize(self):
-        """Leave the ACCEPTED parameters in the step's tensors (``model.dof``, the offsets, ``theta`` and ``K``; the link
-        poses follow the offsets).  Enqueued; never synchronises."""
-        with torch.cuda.device(self.dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self._update(stream, finalize=1)
-            self._forward_kinematics(stream)
-        return self
-
     def state(self):
-        """The state block as a namespace (one small copy; synchronises): lambda, nu, F_acc, pred, rho, F_trial, the counters
-        iterations / accepted / rejected / reported / retries, done, why, last, count, and theta [N], delta [N], g [N],
-        H [N,N] of the accepted point."""
-        return state_namespace(self.state_block.cpu().numpy(), self.N)
+        """The state block as one namespace: :meth:`_LmDriver.states` of the one hypothesis."""
+        return self.states()[0]
 
     def trajectory(self):
-        """[iterations, 4] float64 (CPU): per iteration the trial's loss (NaN: reported), 1 accepted / 0 rejected / -1
-        reported, lambda after the iteration, and the gain ratio rho (NaN unless accepted).  Synchronises."""
-        n = min(int(self.state_block[_lib.LM_STATE["iterations"]].item()), self.log_rows)
-        return self.log[:n].cpu().numpy()
+        """[iterations, 4] float64 (CPU): :meth:`_LmDriver.trajectory` of the one hypothesis.  Synchronises."""
+        return super().trajectory(0)
 
     def report(self, state=None):
         """The :class:`easyhec_amd.information.InformationReport` of the accepted point, from the state block alone."""
-        s = self.state() if state is None else state
-        return information.InformationReport(s.H[None], self.names, s.g[None], [s.count], [s.F_acc])
+        return super().report(0, state)
 
 
 @dataclass
@@ -221,31 +258,48 @@ class LmResult:
     lm: object = None           # the LevenbergMarquardt object
 
 
+def _run_to_convergence(driver, max_iters, check_every, recover, check_status, who):
+    """The polling loop of :func:`solve_lm` and :func:`easyhec_amd.lm_multi.solve_lm_multi`.  Every round reads the
+    driver's states once.  If more iterations were reported than before (NaN loss: not taken), ``recover()`` is called and
+    what it did (if anything) is noted -- at most 4 such rounds, the fifth calls ``check_status()`` and raises in ``who``'s
+    name.  The hypotheses that are not done have each taken ``iterations - reported`` EFFECTIVE iterations: the loop ends
+    when none is left or the one that has taken fewest has taken ``max_iters``, otherwise ``check_every`` more (at most the
+    rest) are enqueued.  Ends with ``finalize()``; returns what the recoveries did, in order."""
+    recoveries, rounds, seen = [], 0, 0
+    while True:
+        S = driver.states()
+        reported = sum(s.reported for s in S)
+        if reported > seen:
+            seen = reported
+            what = recover()
+            if what:
+                recoveries.append(what)
+            rounds += 1
+            if rounds > 4:
+                check_status()
+                raise RuntimeError(f"{who}: iterations keep being reported as not taken (NaN loss)")
+        running = [s.iterations - s.reported for s in S if not s.done]
+        if not running or min(running) >= max_iters:
+            break
+        driver.iterate(min(check_every, max_iters - min(running)))
+    driver.finalize()
+    return recoveries
+
+
 def solve_lm(step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6):
     """Levenberg-Marquardt on ``step``'s parameters from where they are: at most ``max_iters`` EFFECTIVE iterations (a
     reported one -- the plan's job slots overflowed, the view needs the general-triangle pass -- is recovered from the way
     ``_ChainStep`` recovers a step, and taken again), ``done`` polled every ``check_every`` iterations.  Ends with the accepted
     parameters in the step's tensors; a captured chain stays valid.  Returns an :class:`LmResult`."""
     lm = LevenbergMarquardt(step, lambda0=lambda0, ftol=ftol, lambda_max=lambda_max, log_rows=max_iters + 4 * check_every + 8)
-    recoveries, rounds, seen = [], 0, 0
-    while True:
-        s = lm.state()
-        if s.reported > seen:
-            seen = s.reported
-            what = step.recover_from_overflow() if hasattr(step, "recover_from_overflow") else False
-            if what:
-                recoveries.append(what)
-                if hasattr(step, "recoveries"):
-                    step.recoveries.append(what)
-            rounds += 1
-            if rounds > 4:
-                fused.check_status(step.glctx)
-                raise RuntimeError("solve_lm: iterations keep being reported as not taken (NaN loss)")
-        effective = s.iterations - s.reported
-        if s.done or effective >= max_iters:
-            break
-        lm.iterate(min(check_every, max_iters - effective))
-    lm.finalize()
+
+    def recover():
+        what = step.recover_from_overflow() if hasattr(step, "recover_from_overflow") else False
+        if what and hasattr(step, "recoveries"):
+            step.recoveries.append(what)
+        return what
+
+    recoveries = _run_to_convergence(lm, max_iters, check_every, recover, lambda: fused.check_status(step.glctx), "solve_lm")
     s = lm.state()
     why = WHY[s.why].split(":")[0] if s.done else "max_iters"
     return LmResult(s.F_acc, s.iterations, s.accepted, s.rejected, s.reported, bool(s.done), why, lm.trajectory(),

@@ -11,17 +11,21 @@ thread per matrix over all of them, and the update is one workgroup per hypothes
     ehr_lm_linearize_multi  ->  ehr_mask_information (P * Bv views)  ->  ehr_lm_update_multi
 
 Every hypothesis is, bit for bit, its solo ``solve_lm`` on a ``FusedPoseStep`` built on that start
-(tests/test_gpu_lm_multi.py).  Pose only: no joint offsets, no intrinsics.  HIP only; no fallback."""
+(tests/test_gpu_lm_multi.py).  Pose only: no joint offsets, no intrinsics.  HIP only; no fallback.
+
+This module holds what is particular to P starts: the context of its own, the tiled reference, the two ``_multi`` C calls
+and the ranked result.  The iteration and the solve loop are :mod:`easyhec_amd.lm`'s, the slot policy and the recovery
+:class:`easyhec_amd.chain_step._PlannedContext`'s."""
 import ctypes
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
-from . import _lib, dr, fused, information
-from .fast import _private_weight
-from .lm import WHY, state_namespace
+from . import _lib, dr, fused
+from .chain_step import _PlannedContext
+from .fast import _hip_device, _private_weight
+from .lm import WHY, _LmDriver, _run_to_convergence
 from .multistart import _starts_to_dof, rank_losses
 from .se3 import se3_exp_map
 
@@ -55,17 +59,7 @@ def group_basins(poses, ranking, trans_tol_m=1e-3, rot_tol_deg=0.1):
     return basins + lost
 
 
-def _check_batch(who, model, batch):
-    dev = model.dof.device
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who} runs on a HIP device only: move the model with .cuda() first (there is no CPU path)")
-    for k in ("mask", "link_poses", "K"):
-        if not torch.is_tensor(batch[k]) or batch[k].device.type != "cuda":
-            raise RuntimeError(f"{who}: batch['{k}'] must be a tensor on the HIP device")
-    return dev
-
-
-class MultiStartLM:
+class MultiStartLM(_PlannedContext, _LmDriver):
     """:class:`easyhec_amd.lm.LevenbergMarquardt` for P hypotheses of one problem (``starts``: [P,4,4] poses or [P,6] dofs, as
     for :class:`easyhec_amd.multistart.MultiStartPoseStep`).  ``lambda0``, ``ftol``, ``lambda_max``, ``log_rows``: as there,
     per hypothesis; ``slack``: job slots per tile of a VIRTUAL view, as for the launch-chain steps.
@@ -79,11 +73,14 @@ class MultiStartLM:
 
     ``iterate(n)`` enqueues n iterations of every hypothesis and never synchronises (a hypothesis that is done only has its
     accepted pose restored; its views are still rendered); ``state()`` makes one copy; ``finalize()`` leaves the accepted
-    poses in ``dof``."""
+    poses in ``dof``.  The buffers, the guard and the iteration are :class:`easyhec_amd.lm._LmDriver`'s; the slot policy, the
+    plan with its bindings and ``recover_from_overflow()`` -- call it when iterations were reported -- are
+    :class:`easyhec_amd.chain_step._PlannedContext`'s, as for the launch-chain steps."""
+    who = "MultiStartLM"
 
     def __init__(self, model, batch, starts, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256, near=0.001, far=10.0,
                  slack=None):
-        self.dev = dev = _check_batch("MultiStartLM", model, batch)
+        self.dev = dev = _hip_device("MultiStartLM", model, batch)
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("MultiStartLM: not available while a graph is being captured: ehr_mask_information sizes its "
                                "scratch on the first call")
@@ -101,65 +98,16 @@ class MultiStartLM:
         self.K = batch["K"][0].to(dev, torch.float32).contiguous()
         self.Bv, self.L = self.link_poses.shape[0], self.link_poses.shape[1]
         self.dof = _starts_to_dof(starts).to(dev)
-        self.P = P = self.dof.shape[0]
-        self.B = B = P * self.Bv  # virtual views
+        P = self.dof.shape[0]
+        self.B = P * self.Bv  # virtual views
         self.N, self.names = 6, list(NAMES)
         ref = batch["mask"].to(dev, torch.float32)
         assert self.L == self.scene.num_links and ref.shape == (self.Bv, self.H, self.W)
         assert self.weight is None or self.weight.shape == ref.shape
         self.ref = ref.repeat(P, 1, 1).contiguous()  # private and tiled: [P*Bv,H,W]
         self.near, self.far = near, far
-        self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
-        self.mvp = torch.empty((B, self.L, 4, 4), device=dev)
-        self.dmvp = torch.empty((6, B, self.L, 4, 4), device=dev)
-        self.out = information._outputs(6, B, self.L, dev, True, False)
-        st = np.zeros((P, _lib.LM_STATE_DOUBLES))
-        st[:, _lib.LM_STATE["lambda"]], st[:, _lib.LM_STATE["nu"]] = self.lambda0, 2.0
-        self.state_block = torch.from_numpy(st).to(dev)
-        self.log_rows = int(log_rows)
-        self.log = torch.full((P, self.log_rows, 4), float("nan"), dtype=torch.float64, device=dev)
-        self.calls = 0  # iterations enqueued so far: a hypothesis's `iterations` falls behind it once it is done
-        # job slots per virtual view: _ChainStep's rule
-        if slack is None and "EHR_VB_SLACK" not in os.environ:
-            ntiles = ((self.W + 31) // 32) * ((self.H + 7) // 8)
-            self.slack = max(0.5, 256.0 / ntiles)
-        else:
-            self.slack = float(os.environ["EHR_VB_SLACK"]) if slack is None else float(slack)
-        self._plan_and_bind()
-
-    def _plan_and_bind(self):
-        fused._ensure_plan(self.glctx, self.scene, self.B, self.H, self.W, slack=self.slack)
-        if self.weight is not None:  # (the weights first: binding them unbinds the reference)
-            fused.bind_weight(self.glctx, self.scene, self.weight, views=self.B)
-        fused.bind_ref(self.glctx, self.scene, self.ref, views=self.B)
-
-    def recover_from_overflow(self):
-        """Call when iterations were reported.  Synchronises.  What :meth:`easyhec_amd.chain_step._ChainStep.recover_from_overflow`
-        does, on this object's context: "general-triangle pass" (the context launches it from now on), "job slots" (planned
-        again with a slot for every (view, link, tile), weights and reference bound again), or False where the context reports
-        nothing.  Raises on any other overflow."""
-        with torch.cuda.device(self.dev):
-            rc = _lib.lib().ehr_fused_status(self.glctx.handle)
-        if rc == 0:
-            return False
-        if rc == _lib.EHR_ERR_RETRY:
-            return "general-triangle pass"
-        if self.slack == 0.0:
-            _lib.check(rc, "fused render")
-        self.slack = 0.0
-        self._plan_and_bind()
-        return "job slots"
-
-    # -- guards: the context is this object's own, but nothing keeps a caller from rendering with it ---------------------------
-    def _guard(self):
-        plan = getattr(self.glctx, "_plan", None)
-        if plan is None or plan.key != fused._plan_key(self.scene, self.B, self.H, self.W):
-            raise RuntimeError("MultiStartLM: its context holds another plan (somebody else rendered with it)")
-        if getattr(self.glctx, "_bound_weight", None) is not self.weight:
-            raise RuntimeError("MultiStartLM: the weights bound to its context are not its own (somebody else used the "
-                               "context)")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("MultiStartLM: not available while a graph is being captured")
+        self._init_driver(P, lambda0, ftol, lambda_max, log_rows)
+        self._init_plan(slack)  # (job slots per VIRTUAL view)
 
     def _linearize(self, stream):
         _lib.check(_lib.lib().ehr_lm_linearize_multi(
@@ -174,41 +122,9 @@ class MultiStartLM:
             _lib.ptr(self.dof), ctypes.c_double(self.ftol), ctypes.c_double(self.lambda_max), int(finalize),
             _lib.ptr(self.state_block), _lib.ptr(self.log), self.log_rows, stream), "ehr_lm_update_multi")
 
-    def iterate(self, n=1):
-        """Enqueue ``n`` iterations of every hypothesis on the current stream; never synchronises."""
-        self._guard()
-        o = self.out
-        with torch.cuda.device(self.dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for _ in range(int(n)):
-                self._linearize(stream)
-                information._launch(self.glctx, self.scene, self.mvp, self.dmvp, self.ref, o.info, o.grad, o.count, o.loss,
-                                    None)
-                self._update(stream)
-                self.calls += 1
-        return self
-
-    def finalize(self):
-        """Leave the ACCEPTED pose of every hypothesis in ``dof``.  Enqueued; never synchronises."""
-        with torch.cuda.device(self.dev):
-            self._update(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), finalize=1)
-        return self
-
     def state(self):
-        """The P state blocks as a list of namespaces with the fields of :meth:`easyhec_amd.lm.LevenbergMarquardt.state` (one
-        copy of [P,EHR_LM_STATE_DOUBLES]; synchronises)."""
-        s = self.state_block.cpu().numpy()
-        return [state_namespace(s[p], self.N) for p in range(self.P)]
-
-    def trajectory(self, p):
-        """Hypothesis p's [iterations,4] float64 (CPU), as :meth:`easyhec_amd.lm.LevenbergMarquardt.trajectory`."""
-        n = min(int(self.state_block[p, _lib.LM_STATE["iterations"]].item()), self.log_rows)
-        return self.log[p, :n].cpu().numpy()
-
-    def report(self, p, state=None):
-        """The :class:`easyhec_amd.information.InformationReport` of hypothesis p's accepted point, from its state block."""
-        s = self.state()[p] if state is None else state
-        return information.InformationReport(s.H[None], self.names, s.g[None], [s.count], [s.F_acc])
+        """:meth:`easyhec_amd.lm._LmDriver.states`: the P state blocks as a list of namespaces (one copy; synchronises)."""
+        return self.states()
 
     def memory_bytes(self):
         """Device memory of this solve's context (``ehr_ctx_scratch_bytes``) plus the tiled reference."""
@@ -260,24 +176,8 @@ def solve_lm_multi(model, batch, starts, max_iters=50, check_every=5, lambda0=1e
     accepted pose) -- no tail mean.  The model is NOT written.  Returns a :class:`MultiLmResult`."""
     ms = MultiStartLM(model, batch, starts, lambda0=lambda0, ftol=ftol, lambda_max=lambda_max,
                       log_rows=max_iters + 4 * check_every + 8, near=near, far=far, slack=slack)
-    recoveries, rounds, seen = [], 0, 0
-    while True:
-        S = ms.state()
-        reported = sum(s.reported for s in S)
-        if reported > seen:
-            seen = reported
-            what = ms.recover_from_overflow()
-            if what:
-                recoveries.append(what)
-            rounds += 1
-            if rounds > 4:
-                fused.check_status(ms.glctx)
-                raise RuntimeError("solve_lm_multi: iterations keep being reported as not taken (NaN loss)")
-        running = [s.iterations - s.reported for s in S if not s.done]
-        if not running or min(running) >= max_iters:
-            break
-        ms.iterate(min(check_every, max_iters - min(running)))
-    ms.finalize()
+    recoveries = _run_to_convergence(ms, max_iters, check_every, ms.recover_from_overflow,
+                                     lambda: fused.check_status(ms.glctx), "solve_lm_multi")
     return _result(ms, recoveries)
 
 

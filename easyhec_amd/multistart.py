@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .chain_step import _ChainStep, check_solver_settings
-from .fast import _f, _private_weight
+from .fast import _f, _hip_device, _private_weight
 from .se3 import se3_log_map
 from .synthetic import perturb_pose
 
@@ -65,13 +65,7 @@ class MultiStartPoseStep(_ChainStep):
 
     def __init__(self, model, batch, starts, lr=0.003, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0005, near=0.001,
                  far=10.0, slack=None):
-        dev = model.dof.device
-        if dev.type != "cuda":
-            raise RuntimeError("MultiStartPoseStep runs on a HIP device only: move the model with .cuda() first "
-                               "(there is no CPU path)")
-        for k in ("mask", "link_poses", "K"):
-            if not torch.is_tensor(batch[k]) or batch[k].device.type != "cuda":
-                raise RuntimeError(f"MultiStartPoseStep: batch['{k}'] must be a tensor on the HIP device")
+        dev = _hip_device("MultiStartPoseStep", model, batch)
         if not _lib.has_multistart():
             raise RuntimeError("libehr_hip.so has no ehr_solver_step_multi: rebuild it (python -m easyhec_amd.build)")
         self.model = model

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .fast import _hip_device
 from .multistart import rank_losses, sample_starts, solve_multistart
 
 __all__ = ["mask_overlap", "mask_overlap_valid", "overlap_scores", "mask_distance", "mask_cost", "soft_costs", "soft_iou_scores", "candidate_mvps",
@@ -215,10 +216,7 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
     by ``valid = weight > 0`` and a third channel gives the restricted area."""
     if score not in ("xor", "soft"):
         raise ValueError(f"search_starts: score must be 'xor' or 'soft', got {score!r}")
-    for k in ("mask", "link_poses", "K"):
-        if not torch.is_tensor(batch[k]) or batch[k].device.type != "cuda":
-            raise RuntimeError(f"search_starts: batch['{k}'] must be a tensor on the HIP device (there is no CPU path)")
-    dev = batch["mask"].device
+    dev = _hip_device("search_starts", model, batch)
     if P < 1 or Q < P:
         raise ValueError("search_starts: need 1 <= P <= Q")
     Tc_init = np.asarray(Tc_init, dtype=np.float64)
@@ -229,8 +227,8 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
     ref = batch["mask"].to(dev, torch.float32)
     lp = batch["link_poses"].to(dev, torch.float32)
     mvp = candidate_mvps(batch["K"][0].to(dev, torch.float32), H, W, torch.tensor(cands, dtype=torch.float32, device=dev), lp)
+    glctx, scene, soft = model._ensure_renderer().glctx, model._ensure_scene(), None
     if score == "soft":
-        glctx, scene = model._ensure_renderer().glctx, model._ensure_scene()
         cap = max(H, W) // 4 if cap_px is None else int(cap_px)
         d2 = mask_distance(glctx, ref, cap)
         valid = None
@@ -245,24 +243,17 @@ def search_starts(model, batch, Tc_init, Q, P, trans_sigma_m=0.03, rot_sigma_deg
             area = sums[..., 2]
         ref_area = cost[0].sum(dim=(1, 2), dtype=torch.int64)
         soft = soft_iou_scores(area, inter, ksum, ref_area, cap).cpu()
-        xor, iou = overlap_scores(inter, area, ref_area)
-        xor, iou = xor.cpu(), iou.cpu()
-        ranking = rank_losses(-soft.numpy())
-        picked = [0] + [i for i in ranking if i != 0][:P - 1]
-        return PoseSearchResult(starts=cands[picked].copy(), candidates=cands, xor=xor, iou=iou, ranking=ranking,
-                                inter=inter.cpu(), area=area.cpu(), ref_area=ref_area.cpu(), soft=soft, score="soft")
-    if batch.get("weight") is not None:
-        inter, area, ref_area = mask_overlap_valid(model._ensure_renderer().glctx, model._ensure_scene(), mvp, ref,
-                                                   batch["weight"].to(dev, torch.float32), chunk_views=chunk_views)
+    elif batch.get("weight") is not None:
+        inter, area, ref_area = mask_overlap_valid(glctx, scene, mvp, ref, batch["weight"].to(dev, torch.float32),
+                                                   chunk_views=chunk_views)
     else:
-        inter, area, ref_area = mask_overlap(model._ensure_renderer().glctx, model._ensure_scene(), mvp, ref,
-                                             chunk_views=chunk_views)
+        inter, area, ref_area = mask_overlap(glctx, scene, mvp, ref, chunk_views=chunk_views)
     xor, iou = overlap_scores(inter, area, ref_area)
     xor, iou = xor.cpu(), iou.cpu()
-    ranking = rank_losses(xor.numpy())
+    ranking = rank_losses(xor.numpy() if soft is None else -soft.numpy())
     picked = [0] + [i for i in ranking if i != 0][:P - 1]
     return PoseSearchResult(starts=cands[picked].copy(), candidates=cands, xor=xor, iou=iou, ranking=ranking,
-                            inter=inter.cpu(), area=area.cpu(), ref_area=ref_area.cpu())
+                            inter=inter.cpu(), area=area.cpu(), ref_area=ref_area.cpu(), soft=soft, score=score)
 
 
 def solve_global(cfg, model, batch, Tc_init, Q, P, num_steps, trans_sigma_m=0.03, rot_sigma_deg=4.0, seed=0, tail=20,
