@@ -19,6 +19,10 @@ def __getattr__(name):
     if name in ("MultiStartLM", "MultiLmResult", "solve_lm_multi", "solve_global_lm", "group_basins"):
         from . import lm_multi
         return getattr(lm_multi, name)
+    # its form for a camera rig (easyhec_amd/lm_rig.py), likewise
+    if name in ("RigLM", "solve_lm_rig"):
+        from . import lm_rig
+        return getattr(lm_rig, name)
     # information-gain exploration (easyhec_amd/info_explorer.py), likewise
     if name in ("InformationExplorer", "information_gain", "greedy_select"):
         from . import info_explorer

@@ -91,6 +91,8 @@ SIGNATURES = {
     "ehr_lm_linearize_multi": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3),
     "ehr_lm_update_multi": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] + [ctypes.c_double] * 2 + [c_int] +
                             [c_void_p] * 2 + [c_int, c_void_p]),
+    "ehr_lm_update_rig": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
+                          [c_void_p] * 2 + [c_int, c_void_p]),
     "ehr_information_gain": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_double, ctypes.c_uint32, c_void_p, c_void_p]),
     "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
 }
@@ -165,6 +167,10 @@ def has_lm_multi():
     return has_symbols("ehr_lm_linearize_multi", "ehr_lm_update_multi")
 
 
+def has_lm_rig():
+    return has_symbols("ehr_lm_update_rig")
+
+
 def has_information_gain():
     return has_symbols("ehr_information_gain", "ehr_information_pick")
 
@@ -183,6 +189,11 @@ class RigCamera(ctypes.Structure):
     _fields_ = [(k, c_void_p) for k in ("grad_mvp", "tc_jac", "K", "link_poses", "joint_frames", "red", "dof", "adam_m",
                                         "adam_v", "step", "loss_out", "grad_out")] + \
                [("B", c_int), ("H", c_int), ("W", c_int), ("near_plane", c_float), ("far_plane", c_float)]
+
+
+class LmRigCamera(ctypes.Structure):
+    """``ehr_lm_rig_camera`` of include/ehr.h, field for field."""
+    _fields_ = [(k, c_void_p) for k in ("info", "grad", "count", "loss", "dof")] + [("B", c_int)]
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

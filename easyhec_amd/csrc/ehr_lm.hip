@@ -15,6 +15,10 @@
 //                  virtual view p * Bv + j takes dof[p] and link_poses[j]; one workgroup per hypothesis updates its own state
 //                  block.  Both call the device functions the solo kernels call, so hypothesis p has its solo solve's bits.
 //
+//   lm_update_rig : the update for C cameras that share the joint offsets (easyhec_amd/lm_rig.py, section 6o): ONE system of
+//                  6 C + F parameters summed from the cameras' own (6 + F) matrices; its own gathering head, then the steps
+//                  every update shares (lm_update_rest) over the rig's parameter accessor.
+//
 // No kernel here allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
@@ -286,42 +290,48 @@ __device__ __forceinline__ double lm_spacing_f32(float x) {
     return ldexp(1.0, (e == 0 ? 1 : e) - 150);
 }
 
-// One solve's update by one workgroup of one wave (steps 1-6 of include/ehr.h), for both kernels below: B views summed in
-// order, the parameters behind p, the state block st and the log are this solve's own.
-__device__ __forceinline__ void lm_update_solve(const double* __restrict__ info, const double* __restrict__ grad,
-                                                const long long* __restrict__ count, const float* __restrict__ loss, int B,
-                                                int N, const LmParams& p, double ftol, double lambda_max, int finalize,
-                                                double* __restrict__ st, double* __restrict__ log, int log_rows) {
-    __shared__ double Hm[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];  // the call's sum, then H_acc
-    __shared__ double A[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];   // the scaled, damped system and its factor
-    __shared__ double gv[EHR_LM_MAX_PARAMS], sv[EHR_LM_MAX_PARAMS], yv[EHR_LM_MAX_PARAMS], rv[EHR_LM_MAX_PARAMS],
-        hy[EHR_LM_MAX_PARAMS], dl[EHR_LM_MAX_PARAMS];
-    __shared__ double sh_F, sh_cnt, sh_lambda, sh_nu;
-    __shared__ int sh_accept, sh_fail, sh_small;
+// What the pieces of one update share in LDS; the kernel declares ONE of these and hands it to them.
+struct LmShared {
+    double Hm[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];  // the call's sum, then H_acc
+    double A[EHR_LM_MAX_PARAMS][EHR_LM_MAX_PARAMS + 1];   // the scaled, damped system and its factor
+    double gv[EHR_LM_MAX_PARAMS], sv[EHR_LM_MAX_PARAMS], yv[EHR_LM_MAX_PARAMS], rv[EHR_LM_MAX_PARAMS], hy[EHR_LM_MAX_PARAMS],
+        dl[EHR_LM_MAX_PARAMS];
+    double F, cnt, lambda, nu;
+    int accept, fail, small;
+};
+
+// An update is three pieces, each called by all 64 threads of the one wave: lm_update_restore (finalize or done: only the
+// accepted parameters are written back), a gathering head (step 1: lm_update_gather for one problem's views, the rig's own
+// in lm_update_rig_kernel) and lm_update_rest (steps 2-6).  The two that write parameters do so through an accessor P:
+// lm_param_read(p, k), lm_param_write(p, k, x) and lm_write_K(p, tid) overloaded for it.
+template <class P>
+__device__ __forceinline__ bool lm_update_restore(int N, const P& p, int finalize, const double* __restrict__ st) {
     const int tid = threadIdx.x;
-    double* const th_acc = st + EHR_LM_THETA;
-    double* const H_acc = st + EHR_LM_H;
-    double* const g_acc = st + EHR_LM_G;
+    if (finalize == 0 && st[EHR_LM_DONE] == 0.0) return false;
     const bool have = st[EHR_LM_ACCEPTED] > 0.0;  // a point has been accepted
-    if (finalize != 0 || st[EHR_LM_DONE] != 0.0) {  // only restore the accepted parameters
-        if (have && tid < N) lm_param_write(p, tid, (float)th_acc[tid]);
-        __syncthreads();
-        if (have) lm_write_K(p, tid);
-        return;
-    }
-    // 1. the call's sums, in view order
+    if (have && tid < N) lm_param_write(p, tid, (float)st[EHR_LM_THETA + tid]);
+    __syncthreads();
+    if (have) lm_write_K(p, tid);
+    return true;
+}
+
+// 1. the call's sums, in view order, into sh.Hm, sh.gv, sh.F, sh.cnt; returns this thread's "a sum is bad"
+__device__ __forceinline__ int lm_update_gather(const double* __restrict__ info, const double* __restrict__ grad,
+                                                const long long* __restrict__ count, const float* __restrict__ loss, int B,
+                                                int N, LmShared& sh) {
+    const int tid = threadIdx.x;
     int bad = 0;
     for (int e = tid; e < N * N; e += 64) {
         const int r = e / N, c = e - r * N;
         double s = 0.0;
         for (int b = 0; b < B; b++) s += info[((size_t)b * N + r) * N + c];
-        Hm[r][c] = s;
+        sh.Hm[r][c] = s;
         bad |= !lm_finite(s);
     }
     if (tid < N) {
         double s = 0.0;
         for (int b = 0; b < B; b++) s += grad[(size_t)b * N + tid];
-        gv[tid] = s;
+        sh.gv[tid] = s;
         bad |= !lm_finite(s);
     }
     if (tid == 0) {
@@ -332,9 +342,25 @@ __device__ __forceinline__ void lm_update_solve(const double* __restrict__ info,
             c += (double)count[b];
         }
         bad |= !lm_finite(s);
-        sh_F = s;
-        sh_cnt = c;
+        sh.F = s;
+        sh.cnt = c;
     }
+    return bad;
+}
+
+// Steps 2-6 on what a head left in sh (bad: the head's per-thread flag; it is joined here).
+template <class P>
+__device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, const P& p, double ftol, double lambda_max,
+                                               double* __restrict__ st, double* __restrict__ log, int log_rows) {
+    auto &Hm = sh.Hm, &A = sh.A;  // (the names the steps below were written with)
+    auto &gv = sh.gv, &sv = sh.sv, &yv = sh.yv, &rv = sh.rv, &hy = sh.hy, &dl = sh.dl;
+    double &sh_F = sh.F, &sh_cnt = sh.cnt, &sh_lambda = sh.lambda, &sh_nu = sh.nu;
+    int &sh_accept = sh.accept, &sh_fail = sh.fail, &sh_small = sh.small;
+    const int tid = threadIdx.x;
+    double* const th_acc = st + EHR_LM_THETA;
+    double* const H_acc = st + EHR_LM_H;
+    double* const g_acc = st + EHR_LM_G;
+    const bool have = st[EHR_LM_ACCEPTED] > 0.0;  // a point has been accepted
     const int it = (int)st[EHR_LM_ITERATIONS];
     double* const row = (log && it < log_rows) ? log + (size_t)it * 4 : nullptr;  // (thread 0's)
     bad = __syncthreads_or(bad);
@@ -520,7 +546,10 @@ __global__ void __launch_bounds__(64) lm_update_kernel(const double* __restrict_
                                                        const long long* __restrict__ count, const float* __restrict__ loss,
                                                        int B, int N, LmParams p, double ftol, double lambda_max, int finalize,
                                                        double* __restrict__ st, double* __restrict__ log, int log_rows) {
-    lm_update_solve(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize, st, log, log_rows);
+    __shared__ LmShared sh;
+    if (lm_update_restore(N, p, finalize, st)) return;
+    const int bad = lm_update_gather(info, grad, count, loss, B, N, sh);
+    lm_update_rest(sh, bad, N, p, ftol, lambda_max, st, log, log_rows);
 }
 
 // P hypotheses, one workgroup each: hypothesis p owns views [p Bv, (p + 1) Bv), dof[p], state block p and log rows p.  Reported,
@@ -531,10 +560,107 @@ __global__ void __launch_bounds__(64) lm_update_multi_kernel(const double* __res
                                                              float* __restrict__ dof, double ftol, double lambda_max,
                                                              int finalize, double* __restrict__ st, double* __restrict__ log,
                                                              int log_rows) {
+    __shared__ LmShared sh;
     const size_t h = blockIdx.x, v = h * (size_t)Bv;
     const LmParams p = {dof + 6 * h, nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, 0, 0};
-    lm_update_solve(info + v * N * N, grad + v * N, count + v, loss + v, Bv, N, p, ftol, lambda_max, finalize,
-                    st + h * EHR_LM_STATE_DOUBLES, log ? log + h * (size_t)log_rows * 4 : nullptr, log_rows);
+    st += h * EHR_LM_STATE_DOUBLES;
+    log = log ? log + h * (size_t)log_rows * 4 : nullptr;
+    if (lm_update_restore(N, p, finalize, st)) return;
+    const int bad = lm_update_gather(info + v * N * N, grad + v * N, count + v, loss + v, Bv, N, sh);
+    lm_update_rest(sh, bad, N, p, ftol, lambda_max, st, log, log_rows);
+}
+
+// ---- the rig: C cameras, one system of N = 6 C + F parameters (easyhec_amd/lm_rig.py) -------------------
+#define EHR_LM_RIG_MAX_CAMERAS (EHR_LM_MAX_PARAMS / 6)
+
+struct LmRigCameras {  // the host's array, by value in the kernel's arguments (unused entries zeroed)
+    ehr_lm_rig_camera c[EHR_LM_RIG_MAX_CAMERAS];
+};
+
+struct LmRigParams {  // cam0.dof[0..5], cam1.dof[0..5], ..., then the free joints' SHARED offsets; cams: the array in LDS
+    const ehr_lm_rig_camera* cams;
+    int C;
+    float* offset;
+    const int* free_list;
+    int F, J;
+};
+__device__ __forceinline__ float lm_param_read(const LmRigParams& p, int k) {
+    if (k < 6 * p.C) return p.cams[k / 6].dof[k % 6];
+    const int j = p.free_list[k - 6 * p.C];
+    return (j >= 0 && j < p.J) ? p.offset[j] : 0.f;
+}
+__device__ __forceinline__ void lm_param_write(const LmRigParams& p, int k, float x) {
+    if (k < 6 * p.C) {
+        p.cams[k / 6].dof[k % 6] = x;
+    } else {
+        const int j = p.free_list[k - 6 * p.C];
+        if (j >= 0 && j < p.J) p.offset[j] = x;
+    }
+}
+__device__ __forceinline__ void lm_write_K(const LmRigParams&, int) {}  // (no intrinsics in a rig)
+
+// One workgroup of one wave.  The head: per camera the solo sums (from 0.0, in view order) of its [Nc,Nc] matrix, [Nc] gradient,
+// loss and count, Nc = 6 + F, embedded in camera order into the cleared [N,N] system -- local i < 6 -> 6 c + i, local 6 + f ->
+// 6 C + f.  Camera c's local entry (r, col) is thread (r Nc + col) % 64's for every c, so the entries that several cameras add
+// to (the offsets' block) are added by ONE thread in camera order.  Any camera's bad sum reports the call for the whole rig.
+__global__ void __launch_bounds__(64) lm_update_rig_kernel(LmRigCameras cams, int C, float* __restrict__ offset,
+                                                           const int* __restrict__ free_list, int F, int J, double ftol,
+                                                           double lambda_max, int finalize, double* __restrict__ st,
+                                                           double* __restrict__ log, int log_rows) {
+    __shared__ LmShared sh;
+    __shared__ ehr_lm_rig_camera cam_s[EHR_LM_RIG_MAX_CAMERAS];
+    const int tid = threadIdx.x;
+    // the by-value array into LDS, every index a constant: a per-thread run-time index into it would put it in scratch
+    if (tid == 0) {
+#pragma unroll
+        for (int c = 0; c < EHR_LM_RIG_MAX_CAMERAS; c++) cam_s[c] = cams.c[c];
+    }
+    __syncthreads();
+    const int N = 6 * C + F, Nc = 6 + F;
+    const LmRigParams p = {cam_s, C, offset, free_list, F, J};
+    if (lm_update_restore(N, p, finalize, st)) return;
+    for (int e = tid; e < N * N; e += 64) sh.Hm[e / N][e % N] = 0.0;
+    if (tid < N) sh.gv[tid] = 0.0;
+    __syncthreads();
+    int bad = 0;
+    double Fsum = 0.0, nsum = 0.0;  // (thread 0's)
+    for (int c = 0; c < C; c++) {
+        const double* __restrict__ info = cam_s[c].info;
+        const double* __restrict__ grad = cam_s[c].grad;
+        const int B = cam_s[c].B;
+        for (int e = tid; e < Nc * Nc; e += 64) {
+            const int r = e / Nc, col = e - r * Nc;
+            double s = 0.0;
+            for (int b = 0; b < B; b++) s += info[((size_t)b * Nc + r) * Nc + col];
+            bad |= !lm_finite(s);
+            sh.Hm[r < 6 ? 6 * c + r : 6 * C + (r - 6)][col < 6 ? 6 * c + col : 6 * C + (col - 6)] += s;
+        }
+        if (tid < Nc) {
+            double s = 0.0;
+            for (int b = 0; b < B; b++) s += grad[(size_t)b * Nc + tid];
+            bad |= !lm_finite(s);
+            sh.gv[tid < 6 ? 6 * c + tid : 6 * C + (tid - 6)] += s;
+        }
+        if (tid == 0) {
+            const long long* __restrict__ count = cam_s[c].count;
+            const float* __restrict__ loss = cam_s[c].loss;
+            double s = 0.0, n = 0.0;
+            for (int b = 0; b < B; b++) {
+                s += (double)loss[b];
+                bad |= count[b] < 0;
+                n += (double)count[b];
+            }
+            bad |= !lm_finite(s);
+            Fsum += s;
+            nsum += n;
+        }
+    }
+    if (tid == 0) {
+        bad |= !lm_finite(Fsum);
+        sh.F = Fsum;
+        sh.cnt = nsum;
+    }
+    lm_update_rest(sh, bad, N, p, ftol, lambda_max, st, log, log_rows);
 }
 
 }  // namespace ehr
@@ -615,6 +741,28 @@ int ehr_lm_update_multi(const double* info, const double* grad, const long long*
     lm_update_multi_kernel<<<(unsigned)P, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, Bv, N, dof, ftol, lambda_max,
                                                                        finalize, state, log && log_rows > 0 ? log : nullptr,
                                                                        log_rows);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_lm_update_rig(const ehr_lm_rig_camera* cams, int C, float* offset, const int32_t* free_list, int F, int J, double ftol,
+                      double lambda_max, int finalize, double* state, double* log, int log_rows, void* stream) {
+    if (!cams || !state) return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: NULL cameras or state");
+    if (F < 0 || (F > 0 && (!offset || !free_list || J < 1 || J > 32)))
+        return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: free joints need offset and the list (J %d <= 32)", J);
+    if (C < 1 || C > EHR_LM_RIG_MAX_CAMERAS || 6 * C + F > EHR_LM_MAX_PARAMS)
+        return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: %d cameras and %d free joints are N = %d parameters; 1 <= C and N <= %d",
+                    C, F, 6 * C + F, EHR_LM_MAX_PARAMS);
+    LmRigCameras by_value = {};
+    for (int c = 0; c < C; c++) {  // (a HOST array: every field can be judged here)
+        const ehr_lm_rig_camera& k = cams[c];
+        if (!k.info || !k.grad || !k.count || !k.loss || !k.dof)
+            return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: camera %d has a NULL pointer", c);
+        if (k.B < 1) return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: camera %d has B %d < 1", c, k.B);
+        by_value.c[c] = k;
+    }
+    lm_update_rig_kernel<<<1, 64, 0, (hipStream_t)stream>>>(by_value, C, offset, free_list, F, J, ftol, lambda_max, finalize, state,
+                                                           log && log_rows > 0 ? log : nullptr, log_rows);
     EHR_LAUNCH_CHECK();
     return EHR_OK;
 }

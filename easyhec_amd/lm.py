@@ -21,7 +21,8 @@ bit for bit -- where :func:`easyhec_amd.information.information_of` renders a fl
 The iteration and the solve loop are written once, for P state blocks: ``_LmDriver`` owns the
 buffers, the guard, ``iterate`` / ``finalize`` and the reading of the state, ``_run_to_convergence`` the polling loop.
 :class:`LevenbergMarquardt` is the driver with one block on a step object's context;
-:class:`easyhec_amd.lm_multi.MultiStartLM` is the driver with P blocks on a context of its own."""
+:class:`easyhec_amd.lm_multi.MultiStartLM` is the driver with P blocks on a context of its own;
+:class:`easyhec_amd.lm_rig.RigLM` is the driver with one block over the C contexts of a camera rig (section 6o)."""
 import ctypes
 import types
 from dataclasses import dataclass, field
@@ -45,8 +46,8 @@ def _refuse(step):
         raise ValueError("solve_lm: not available for the multi-start step: its hypotheses are separate solves; ask for the "
                          "winner's FusedPoseStep")
     if isinstance(step, RigJointStep):
-        raise ValueError("solve_lm: not available for a rig: it is one system over several contexts (out of scope); the "
-                         "cameras' matrices are rig_information(rig_step)'s")
+        raise ValueError("solve_lm: not available for a rig: it is one system over several contexts; that solve is "
+                         "solve_lm_rig(rig_step) (easyhec_amd.lm_rig)")
     if getattr(step, "distributed", False) or getattr(step, "rccl", False) or getattr(step, "p2p", False):
         raise ValueError("solve_lm: not available for a data-parallel job: each rank holds its own views, and the matrices "
                          "are not exchanged")
@@ -108,22 +109,28 @@ def state_namespace(s, N):
 
 class _LmDriver:
     """The Levenberg-Marquardt iteration for P state blocks, whatever it drives: the buffers, the guard, the launch chain
-    of an iteration and the reading of the state.  A subclass sets what it renders with -- ``glctx``, ``scene``, ``ref``,
-    ``weight``, ``B`` (the views of the plan), ``H``, ``W``, ``L``, ``dev``, ``N``, ``names`` -- then calls
-    :meth:`_init_driver`, and provides the two C calls ``_linearize(stream)`` and ``_update(stream, finalize=0)``.
-    ``_forward_kinematics(stream)``, where a subclass has one, is launched ahead of every linearisation and behind the
-    finalising update.  ``who`` names the owner in the guard's messages."""
-    who, _forward_kinematics = "solve_lm", None
+    of an iteration and the reading of the state.  It renders through a list of UNITS, ``units``: a unit carries what one
+    ``ehr_mask_information`` call works on -- ``glctx``, ``scene``, ``ref``, ``weight``, ``B`` (the views of the plan), ``H``,
+    ``W``, ``L``, ``N`` (its tangents) -- gets ``mvp``, ``dmvp`` and the information outputs ``out`` from
+    :meth:`_init_driver`, and provides ``_linearize(stream)`` and, where it has one, ``_forward_kinematics(stream)``, which
+    is launched ahead of every linearisation and behind the finalising update.  ``label`` names it in the guard's messages.
+    A driver with one context is its own one unit (:class:`LevenbergMarquardt`, :class:`easyhec_amd.lm_multi.MultiStartLM`);
+    the rig has one per camera (:class:`easyhec_amd.lm_rig.RigLM`).  A subclass sets ``dev``, ``N`` (the parameters of a
+    state block) and ``names``, calls :meth:`_init_driver`, and provides the ONE C call ``_update(stream, finalize=0)``.
+    ``who`` names the owner in the guard's messages."""
+    who, label, _forward_kinematics = "solve_lm", "", None
 
-    def _init_driver(self, P, lambda0, ftol, lambda_max, log_rows):
-        N, B, L, dev = self.N, self.B, self.L, self.dev
+    def _init_driver(self, P, lambda0, ftol, lambda_max, log_rows, units=None):
+        N, dev = self.N, self.dev
         if N > _lib.LM_MAX_PARAMS:
             raise ValueError(f"{self.who}: the step optimises {N} parameters; the kernels take {_lib.LM_MAX_PARAMS}")
         self.P = P
         self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
-        self.mvp = torch.empty((B, L, 4, 4), device=dev)
-        self.dmvp = torch.empty((N, B, L, 4, 4), device=dev)
-        self.out = information._outputs(N, B, L, dev, True, False)
+        self.units = [self] if units is None else list(units)
+        for u in self.units:
+            u.mvp = torch.empty((u.B, u.L, 4, 4), device=dev)
+            u.dmvp = torch.empty((u.N, u.B, u.L, 4, 4), device=dev)
+            u.out = information._outputs(u.N, u.B, u.L, dev, True, False)
         st = np.zeros((P, _lib.LM_STATE_DOUBLES))
         st[:, _lib.LM_STATE["lambda"]], st[:, _lib.LM_STATE["nu"]] = self.lambda0, 2.0
         self.state_block = self._state = torch.from_numpy(st).to(dev)  # (a subclass may publish views of the two)
@@ -131,15 +138,16 @@ class _LmDriver:
         self.log = self._log = torch.full((P, self.log_rows, 4), float("nan"), dtype=torch.float64, device=dev)
         self.calls = 0  # iterations enqueued so far: a hypothesis's `iterations` falls behind it once it is done
 
-    # -- guards: the context is shared state; never iterate on a plan or on weights that are not the owner's -----------------
+    # -- guards: a context is shared state; never iterate on a plan or on weights that are not the owner's -------------------
     def _guard(self):
-        plan = getattr(self.glctx, "_plan", None)
-        if plan is None or plan.key != fused._plan_key(self.scene, self.B, self.H, self.W):
-            raise RuntimeError(f"{self.who}: its context holds another plan (somebody else rendered with it): plan and "
-                               "bind again first (a step object does when it takes a step)")
-        if getattr(self.glctx, "_bound_weight", None) is not self.weight:
-            raise RuntimeError(f"{self.who}: the weights bound to its context are not its own (somebody else used the "
-                               "context): bind them again first (a step object does when it takes a step)")
+        for u in self.units:
+            plan = getattr(u.glctx, "_plan", None)
+            if plan is None or plan.key != fused._plan_key(u.scene, u.B, u.H, u.W):
+                raise RuntimeError(f"{self.who}: {u.label}its context holds another plan (somebody else rendered with it): "
+                                   "plan and bind again first (a step object does when it takes a step)")
+            if getattr(u.glctx, "_bound_weight", None) is not u.weight:
+                raise RuntimeError(f"{self.who}: {u.label}the weights bound to its context are not its own (somebody else "
+                                   "used the context): bind them again first (a step object does when it takes a step)")
         if self.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"{self.who}: not available while a graph is being captured")
 
@@ -147,14 +155,15 @@ class _LmDriver:
         """Enqueue ``n`` iterations (of every hypothesis) on the current stream; never synchronises.  After ``done`` an
         iteration only restores the accepted parameters."""
         self._guard()
-        o, forward_kinematics = self.out, self._forward_kinematics
         with torch.cuda.device(self.dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             for _ in range(int(n)):
-                if forward_kinematics is not None:
-                    forward_kinematics(stream)
-                self._linearize(stream)
-                information._launch(self.glctx, self.scene, self.mvp, self.dmvp, self.ref, o.info, o.grad, o.count, o.loss, None)
+                for u in self.units:
+                    if u._forward_kinematics is not None:
+                        u._forward_kinematics(stream)
+                    u._linearize(stream)
+                    o = u.out
+                    information._launch(u.glctx, u.scene, u.mvp, u.dmvp, u.ref, o.info, o.grad, o.count, o.loss, None)
                 self._update(stream)
                 self.calls += 1
         return self
@@ -164,8 +173,9 @@ class _LmDriver:
         with torch.cuda.device(self.dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             self._update(stream, finalize=1)
-            if self._forward_kinematics is not None:
-                self._forward_kinematics(stream)
+            for u in self.units:
+                if u._forward_kinematics is not None:
+                    u._forward_kinematics(stream)
         return self
 
     def states(self):

@@ -644,6 +644,40 @@ int ehr_lm_update_multi(const double* info, const double* grad, const long long*
                         float* dof, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
                         void* stream);
 
+/* Levenberg-Marquardt over a camera rig: C fixed cameras watch one arm and share its joint offsets (ehr_rig_backward_adam's
+ * setting), solved as ONE system of N = 6 C + F <= EHR_LM_MAX_PARAMS parameters in the order of
+ * easyhec_amd.information.rig_information: cam0.dof[0..5], cam1.dof[0..5], ..., then offset[free_list[0..F)].  One iteration is
+ *     per camera c : ehr_joint_forward (qpos_c, the SHARED offsets) -> ehr_lm_linearize (camera c's dof, K, link_poses,
+ *                    joint_frames; N_c = 6 + F) -> ehr_mask_information on camera c's context
+ *                    -> info_c [B_c,N_c,N_c], grad_c [B_c,N_c], count_c [B_c], loss_c [B_c]
+ *     once         : ehr_lm_update_rig                                                                      on one stream.
+ * The three per-camera calls are used as they are.  `cams` is a HOST array of C structs of device pointers: it is validated
+ * here (EHR_ERR_INVALID for a NULL pointer, B_c < 1, C < 1 or N > EHR_LM_MAX_PARAMS) and travels to the kernel by value.  One
+ * workgroup of one wave, float64, fixed order, no atomics; never allocates or synchronises.  The state block, the log and
+ * ftol / lambda_max / finalize are ehr_lm_update's.  In order:
+ *   1. Per camera, in camera order: S_c = sum_b info_c[b], s_c = sum_b grad_c[b], F_c = sum_b (double) loss_c[b],
+ *      n_c = sum_b count_c[b], each from 0.0 in view order (ehr_lm_update's sums).  H and g are cleared, then every camera is
+ *      embedded in camera order, each entry `+=`: local index i < 6 -> 6 c + i, local 6 + f -> 6 C + f.  A pose-pose and a
+ *      pose-offset block so has one term, the offset-offset block C terms in camera order, and the block between two different
+ *      cameras' poses stays 0.0.  F = F_0 + F_1 + ..., count = n_0 + n_1 + ... in camera order, from 0.0.  With C == 1 every
+ *      value is ehr_lm_update's, bit for bit.
+ *   2. A non-finite sum or loss or a count < 0 of ANY camera reports the call for the whole rig: every camera's accepted pose
+ *      and the accepted offsets are written back, `reported` is incremented, nothing else moves (ehr_rig_backward_adam's all or
+ *      nothing).
+ *   3-6. ehr_lm_update's, by the same device function over the rig's parameters: accept or reject, the damped scaled Cholesky
+ *      solve with the exclusion of H_kk <= 0 and the retries, pred, the stopping rule and the trial fl32(theta_acc + delta)
+ *      through every cams[c].dof and offset.  There are no intrinsics in a rig: no K is rewritten.
+ * Out of scope: per-camera intrinsics, more than EHR_LM_MAX_PARAMS parameters (C <= 5 with F <= 2, C <= 4 with F <= 8, ...).
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+typedef struct {            /* one camera of the rig's update; all pointers are device pointers */
+    const double *info, *grad;  const long long* count;  const float* loss;   /* ehr_mask_information's outputs for its views */
+    float* dof;                                                                 /* its 6 pose coordinates */
+    int B;
+} ehr_lm_rig_camera;
+int ehr_lm_update_rig(const ehr_lm_rig_camera* cams /* HOST array [C] */, int C, float* offset, const int32_t* free_list, int F,
+                      int J, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                      void* stream);
+
 /* Information-gain exploration: which candidate joint configuration to observe next.  A candidate is a group of S consecutive
  * views of info [Q,S,N,N] -- ehr_mask_information's matrices of the views the candidate WOULD give (the op's info does not depend
  * on the reference mask, so they exist before the candidate is observed); S > 1 averages over sampled poses or sums over cameras.
