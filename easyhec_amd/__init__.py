@@ -12,7 +12,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # the Levenberg-Marquardt solve (easyhec_amd/lm.py), looked up on first use: importing the package stays free of torch
-    if name in ("LevenbergMarquardt", "solve_lm", "LmResult"):
+    if name in ("LevenbergMarquardt", "solve_lm", "LmResult", "LmPrior", "make_prior"):
         from . import lm
         return getattr(lm, name)
     # its multi-start form (easyhec_amd/lm_multi.py), likewise

@@ -88,11 +88,16 @@ SIGNATURES = {
     "ehr_lm_linearize": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float] * 2 + [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 3),
     "ehr_lm_update": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 +
                       [c_void_p] * 2 + [c_int] * 2 + [ctypes.c_double] * 2 + [c_int] + [c_void_p] * 2 + [c_int, c_void_p]),
+    "ehr_lm_update_prior": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] + [c_int] * 2 +
+                            [c_void_p] * 2 + [c_int] * 2 + [ctypes.c_double] * 2 + [c_int] + [c_void_p] * 2 + [c_int] +
+                            [c_void_p] * 3),
     "ehr_lm_linearize_multi": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3),
     "ehr_lm_update_multi": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] + [ctypes.c_double] * 2 + [c_int] +
                             [c_void_p] * 2 + [c_int, c_void_p]),
     "ehr_lm_update_rig": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
                           [c_void_p] * 2 + [c_int, c_void_p]),
+    "ehr_lm_update_rig_prior": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
+                                [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
     "ehr_information_gain": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_double, ctypes.c_uint32, c_void_p, c_void_p]),
     "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
 }
@@ -171,6 +176,10 @@ def has_lm_rig():
     return has_symbols("ehr_lm_update_rig")
 
 
+def has_lm_prior():
+    return has_symbols("ehr_lm_update_prior", "ehr_lm_update_rig_prior")
+
+
 def has_information_gain():
     return has_symbols("ehr_information_gain", "ehr_information_pick")
 
@@ -180,7 +189,7 @@ IG_MAX_PARAMS = 32  # include/ehr.h: EHR_IG_MAX_PARAMS
 
 # the state block of ehr_lm_update (include/ehr.h: EHR_LM_*), in float64 words
 LM_STATE = {"lambda": 0, "nu": 1, "F_acc": 2, "pred": 3, "rho": 4, "F_trial": 5, "iterations": 6, "accepted": 7, "rejected": 8,
-            "reported": 9, "done": 10, "why": 11, "last": 12, "count": 13, "retries": 14}
+            "reported": 9, "done": 10, "why": 11, "last": 12, "count": 13, "retries": 14, "F_prior": 15}
 LM_THETA, LM_DELTA, LM_G, LM_H, LM_STATE_DOUBLES, LM_MAX_PARAMS = 16, 48, 80, 112, 1136, 32
 
 

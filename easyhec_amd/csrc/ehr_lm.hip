@@ -19,6 +19,10 @@
 //                  6 C + F parameters summed from the cameras' own (6 + F) matrices; its own gathering head, then the steps
 //                  every update shares (lm_update_rest) over the rig's parameter accessor.
 //
+//   lm_update<true>, lm_update_rig<true> : the two under a diagonal Gaussian prior sum_k p_k (theta_k - mu_k)^2 (section 6p): its
+//                  term joins the objective the accept test sees, p_k and 2 p_k (theta_acc_k - mu_k) the system that is solved;
+//                  the stored linearisation stays the data's.  The <false> forms are compiled without any of it.
+//
 // No kernel here allocates, synchronises or uses an atomic: results are bit-reproducible from run to run.
 #include "ehr_host.h"
 #include "ehr_pose_core.h"
@@ -299,6 +303,20 @@ struct LmShared {
     double F, cnt, lambda, nu;
     int accept, fail, small;
 };
+template <bool PRIOR>
+struct LmPriorArgs {  // the prior's two device arrays as a kernel argument; without a prior an empty one
+    const double *weight, *mean;
+};
+template <>
+struct LmPriorArgs<false> {};
+__device__ __forceinline__ const double* lm_prior_weight(const LmPriorArgs<true>& a) { return a.weight; }
+__device__ __forceinline__ const double* lm_prior_mean(const LmPriorArgs<true>& a) { return a.mean; }
+__device__ __forceinline__ const double* lm_prior_weight(const LmPriorArgs<false>&) { return nullptr; }
+__device__ __forceinline__ const double* lm_prior_mean(const LmPriorArgs<false>&) { return nullptr; }
+struct LmPriorShared {  // under a prior only: its weights p_k, its means mu_k and its term at the trial
+    double pw[EHR_LM_MAX_PARAMS], pm[EHR_LM_MAX_PARAMS];
+    double Fp;
+};
 
 // An update is three pieces, each called by all 64 threads of the one wave: lm_update_restore (finalize or done: only the
 // accepted parameters are written back), a gathering head (step 1: lm_update_gather for one problem's views, the rig's own
@@ -349,9 +367,17 @@ __device__ __forceinline__ int lm_update_gather(const double* __restrict__ info,
 }
 
 // Steps 2-6 on what a head left in sh (bad: the head's per-thread flag; it is joined here).
-template <class P>
+// prior_weight, prior_mean ([N] float64, both or neither): a Gaussian prior sum_k p_k (theta_k - mu_k)^2 beside the data's loss.
+// Its term at the trial joins F ahead of step 3 (EHR_LM_F and EHR_LM_F_TRIAL hold the total, EHR_LM_F_PRIOR the term at the
+// accepted point); H_acc, g_acc stay the data's own, and p_k, 2 p_k (theta_acc_k - mu_k) are added to the system that steps 4-6
+// solve, in both branches of step 3.  A parameter without data information but with p_k > 0 is therefore NOT left out: the prior
+// alone pulls it towards mu_k.  PRIOR is a template parameter: the kernels without a prior are compiled without any of it, so
+// not one operation of theirs differs from the kernel that had none (ps, prior_weight, prior_mean: unused, may be NULL).
+template <bool PRIOR, class P>
 __device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, const P& p, double ftol, double lambda_max,
-                                               double* __restrict__ st, double* __restrict__ log, int log_rows) {
+                                               double* __restrict__ st, double* __restrict__ log, int log_rows,
+                                               LmPriorShared* ps, const double* __restrict__ prior_weight,
+                                               const double* __restrict__ prior_mean) {
     auto &Hm = sh.Hm, &A = sh.A;  // (the names the steps below were written with)
     auto &gv = sh.gv, &sv = sh.sv, &yv = sh.yv, &rv = sh.rv, &hy = sh.hy, &dl = sh.dl;
     double &sh_F = sh.F, &sh_cnt = sh.cnt, &sh_lambda = sh.lambda, &sh_nu = sh.nu;
@@ -363,6 +389,33 @@ __device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, con
     const bool have = st[EHR_LM_ACCEPTED] > 0.0;  // a point has been accepted
     const int it = (int)st[EHR_LM_ITERATIONS];
     double* const row = (log && it < log_rows) ? log + (size_t)it * 4 : nullptr;  // (thread 0's)
+    constexpr bool prior = PRIOR;
+    // the prior's term at the trial (the parameters as the pointers hold them): Fp = sum_k (p_k d_k) d_k, d_k = theta_k - mu_k,
+    // k ascending from 0.0, p_k == 0 skipped; a bad weight, a bad mean under a weight or a non-finite Fp reports the call
+    if (prior) {
+        if (tid < N) {
+            const double w = prior_weight[tid], m = prior_mean[tid];
+            double t = 0.0;
+            if (!(w >= 0.0) || !lm_finite(w)) {
+                bad = 1;
+            } else if (w != 0.0) {
+                bad |= !lm_finite(m);
+                const double d = (double)lm_param_read(p, tid) - m;
+                t = (w * d) * d;
+            }
+            ps->pw[tid] = w;
+            ps->pm[tid] = m;
+            hy[tid] = t;  // (free until step 4)
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int k = 0; k < N; k++)
+                if (ps->pw[k] != 0.0) s += hy[k];
+            bad |= !lm_finite(s);
+            ps->Fp = s;
+        }
+    }
     bad = __syncthreads_or(bad);
     // 2. a reported call: the trial is discarded, nothing else moves
     if (bad) {
@@ -384,7 +437,7 @@ __device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, con
     }
     // 3. accept or reject
     if (tid == 0) {
-        const double F = sh_F, F_acc = st[EHR_LM_F];
+        const double F = prior ? sh_F + ps->Fp : sh_F, F_acc = st[EHR_LM_F];
         double lambda = st[EHR_LM_LAMBDA], nu = st[EHR_LM_NU], rho = 0.0;
         const int accept = !have || F < F_acc;
         if (accept) {
@@ -395,6 +448,7 @@ __device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, con
             }
             nu = 2.0;
             st[EHR_LM_F] = F;
+            if (prior) st[EHR_LM_F_PRIOR] = ps->Fp;  // (the data's loss at the accepted point: F_acc - F_prior)
             st[EHR_LM_COUNT] = sh_cnt;
             st[EHR_LM_RHO] = rho;
             st[EHR_LM_ACCEPTED] += 1.0;
@@ -433,6 +487,14 @@ __device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, con
         if (tid < N) gv[tid] = g_acc[tid];
     }
     __syncthreads();
+    // the prior joins the system that is solved, never the stored one: a rejected call rebuilds what the accepting call solved
+    if (prior) {
+        if (tid < N && ps->pw[tid] != 0.0) {
+            Hm[tid][tid] += ps->pw[tid];
+            gv[tid] += 2.0 * ps->pw[tid] * (th_acc[tid] - ps->pm[tid]);
+        }
+        __syncthreads();
+    }
     // 4. (H_acc + lambda D) delta = -g_acc / 2, D = diag H_acc, on the scaled system  (S H S + lambda I) y = -S g / 2,
     //    S = D^-1/2, delta = S y; a parameter whose diagonal entry is <= 0 is left out
     if (tid < N) {
@@ -542,14 +604,21 @@ __device__ __forceinline__ void lm_update_rest(LmShared& sh, int bad, int N, con
     lm_write_K(p, tid);
 }
 
+template <bool PRIOR>
 __global__ void __launch_bounds__(64) lm_update_kernel(const double* __restrict__ info, const double* __restrict__ grad,
                                                        const long long* __restrict__ count, const float* __restrict__ loss,
                                                        int B, int N, LmParams p, double ftol, double lambda_max, int finalize,
-                                                       double* __restrict__ st, double* __restrict__ log, int log_rows) {
+                                                       double* __restrict__ st, double* __restrict__ log, int log_rows,
+                                                       LmPriorArgs<PRIOR> prior) {
     __shared__ LmShared sh;
+    LmPriorShared* ps = nullptr;
+    if constexpr (PRIOR) {
+        __shared__ LmPriorShared prior_s;
+        ps = &prior_s;
+    }
     if (lm_update_restore(N, p, finalize, st)) return;
     const int bad = lm_update_gather(info, grad, count, loss, B, N, sh);
-    lm_update_rest(sh, bad, N, p, ftol, lambda_max, st, log, log_rows);
+    lm_update_rest<PRIOR>(sh, bad, N, p, ftol, lambda_max, st, log, log_rows, ps, lm_prior_weight(prior), lm_prior_mean(prior));
 }
 
 // P hypotheses, one workgroup each: hypothesis p owns views [p Bv, (p + 1) Bv), dof[p], state block p and log rows p.  Reported,
@@ -567,7 +636,7 @@ __global__ void __launch_bounds__(64) lm_update_multi_kernel(const double* __res
     log = log ? log + h * (size_t)log_rows * 4 : nullptr;
     if (lm_update_restore(N, p, finalize, st)) return;
     const int bad = lm_update_gather(info + v * N * N, grad + v * N, count + v, loss + v, Bv, N, sh);
-    lm_update_rest(sh, bad, N, p, ftol, lambda_max, st, log, log_rows);
+    lm_update_rest<false>(sh, bad, N, p, ftol, lambda_max, st, log, log_rows, nullptr, nullptr, nullptr);  // (pose only: no prior)
 }
 
 // ---- the rig: C cameras, one system of N = 6 C + F parameters (easyhec_amd/lm_rig.py) -------------------
@@ -603,11 +672,18 @@ __device__ __forceinline__ void lm_write_K(const LmRigParams&, int) {}  // (no i
 // loss and count, Nc = 6 + F, embedded in camera order into the cleared [N,N] system -- local i < 6 -> 6 c + i, local 6 + f ->
 // 6 C + f.  Camera c's local entry (r, col) is thread (r Nc + col) % 64's for every c, so the entries that several cameras add
 // to (the offsets' block) are added by ONE thread in camera order.  Any camera's bad sum reports the call for the whole rig.
+template <bool PRIOR>
 __global__ void __launch_bounds__(64) lm_update_rig_kernel(LmRigCameras cams, int C, float* __restrict__ offset,
                                                            const int* __restrict__ free_list, int F, int J, double ftol,
                                                            double lambda_max, int finalize, double* __restrict__ st,
-                                                           double* __restrict__ log, int log_rows) {
+                                                           double* __restrict__ log, int log_rows,
+                                                           LmPriorArgs<PRIOR> prior) {
     __shared__ LmShared sh;
+    LmPriorShared* ps = nullptr;
+    if constexpr (PRIOR) {
+        __shared__ LmPriorShared prior_s;
+        ps = &prior_s;
+    }
     __shared__ ehr_lm_rig_camera cam_s[EHR_LM_RIG_MAX_CAMERAS];
     const int tid = threadIdx.x;
     // the by-value array into LDS, every index a constant: a per-thread run-time index into it would put it in scratch
@@ -660,7 +736,7 @@ __global__ void __launch_bounds__(64) lm_update_rig_kernel(LmRigCameras cams, in
         sh.F = Fsum;
         sh.cnt = nsum;
     }
-    lm_update_rest(sh, bad, N, p, ftol, lambda_max, st, log, log_rows);
+    lm_update_rest<PRIOR>(sh, bad, N, p, ftol, lambda_max, st, log, log_rows, ps, lm_prior_weight(prior), lm_prior_mean(prior));
 }
 
 }  // namespace ehr
@@ -694,29 +770,63 @@ int ehr_lm_linearize(const float* dof, const float* K, const float* link_poses, 
     return EHR_OK;
 }
 
-int ehr_lm_update(const double* info, const double* grad, const long long* count, const float* loss, int B, int N, float* dof,
-                  float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask, int tie_focal,
-                  const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
-                  void* stream) {
-    if (!info || !grad || !count || !loss || !dof || !state) return fail(EHR_ERR_INVALID, "ehr_lm_update: NULL tensor");
+// what the two prior pointers must be, for both forms: both NULL (no prior) or both given
+static int lm_prior_check(const char* who, const double* prior_weight, const double* prior_mean) {
+    if ((prior_weight == nullptr) != (prior_mean == nullptr))
+        return fail(EHR_ERR_INVALID, "%s: prior_weight and prior_mean go together (both NULL: no prior); got %s NULL", who,
+                    prior_weight ? "prior_mean" : "prior_weight");
+    return EHR_OK;
+}
+
+static int lm_update_launch(const char* who, const double* info, const double* grad, const long long* count, const float* loss,
+                            int B, int N, float* dof, float* offset, const int32_t* free_list, int F, int J, float* theta,
+                            int free4_mask, int tie_focal, const float* K0, float* K, int H, int W, double ftol, double lambda_max,
+                            int finalize, double* state, double* log, int log_rows, const double* prior_weight,
+                            const double* prior_mean, void* stream) {
+    if (!info || !grad || !count || !loss || !dof || !state) return fail(EHR_ERR_INVALID, "%s: NULL tensor", who);
     if (F < 0 || (F > 0 && (!offset || !free_list || J < 1 || J > 32)))
-        return fail(EHR_ERR_INVALID, "ehr_lm_update: free joints need offset and the list (J %d <= 32)", J);
+        return fail(EHR_ERR_INVALID, "%s: free joints need offset and the list (J %d <= 32)", who, J);
     if (free4_mask < 0 || free4_mask > 15 || (tie_focal != 0 && (free4_mask & 3) != 3) ||
         (free4_mask != 0 && (!theta || !K0 || !K || H < 1 || W < 1)))
-        return fail(EHR_ERR_INVALID, "ehr_lm_update: bad free intrinsics (mask %d, tie_focal %d), or no theta / K0 / K", free4_mask,
+        return fail(EHR_ERR_INVALID, "%s: bad free intrinsics (mask %d, tie_focal %d), or no theta / K0 / K", who, free4_mask,
                     tie_focal);
     int Fi = 0;
     for (int i = 0; i < 4; i++) Fi += (free4_mask >> i) & 1;
     if (tie_focal != 0) Fi -= 1;
     // (N < 6 without free joints or intrinsics: the first N pose coordinates alone)
     if ((N != 6 + F + Fi && !(F == 0 && Fi == 0 && N >= 1 && N < 6)) || N > EHR_LM_MAX_PARAMS || B < 1)
-        return fail(EHR_ERR_INVALID, "ehr_lm_update: N %d is not 6 + %d free joints + %d free intrinsics, or exceeds %d (B %d)", N, F,
-                    Fi, EHR_LM_MAX_PARAMS, B);
+        return fail(EHR_ERR_INVALID, "%s: N %d is not 6 + %d free joints + %d free intrinsics, or exceeds %d (B %d)", who, N, F, Fi,
+                    EHR_LM_MAX_PARAMS, B);
+    if (int rc = lm_prior_check(who, prior_weight, prior_mean)) return rc;
     LmParams p = {dof, offset, free_list, F, J, theta, free4_mask, tie_focal, K0, K, H, W};
-    lm_update_kernel<<<1, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize, state,
-                                                       log && log_rows > 0 ? log : nullptr, log_rows);
+    double* const lg = log && log_rows > 0 ? log : nullptr;
+    if (prior_weight)
+        lm_update_kernel<true><<<1, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize,
+                                                                 state, lg, log_rows,
+                                                                 LmPriorArgs<true>{prior_weight, prior_mean});
+    else
+        lm_update_kernel<false><<<1, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, B, N, p, ftol, lambda_max, finalize,
+                                                                  state, lg, log_rows, LmPriorArgs<false>{});
     EHR_LAUNCH_CHECK();
     return EHR_OK;
+}
+
+int ehr_lm_update(const double* info, const double* grad, const long long* count, const float* loss, int B, int N, float* dof,
+                  float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask, int tie_focal,
+                  const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                  void* stream) {
+    return lm_update_launch("ehr_lm_update", info, grad, count, loss, B, N, dof, offset, free_list, F, J, theta, free4_mask,
+                            tie_focal, K0, K, H, W, ftol, lambda_max, finalize, state, log, log_rows, nullptr, nullptr, stream);
+}
+
+int ehr_lm_update_prior(const double* info, const double* grad, const long long* count, const float* loss, int B, int N,
+                        float* dof, float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask,
+                        int tie_focal, const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize,
+                        double* state, double* log, int log_rows, const double* prior_weight, const double* prior_mean,
+                        void* stream) {
+    return lm_update_launch("ehr_lm_update_prior", info, grad, count, loss, B, N, dof, offset, free_list, F, J, theta, free4_mask,
+                            tie_focal, K0, K, H, W, ftol, lambda_max, finalize, state, log, log_rows, prior_weight, prior_mean,
+                            stream);
 }
 
 int ehr_lm_linearize_multi(const float* dof, const float* K, const float* link_poses, int P, int Bv, int L, int H, int W,
@@ -745,26 +855,47 @@ int ehr_lm_update_multi(const double* info, const double* grad, const long long*
     return EHR_OK;
 }
 
-int ehr_lm_update_rig(const ehr_lm_rig_camera* cams, int C, float* offset, const int32_t* free_list, int F, int J, double ftol,
-                      double lambda_max, int finalize, double* state, double* log, int log_rows, void* stream) {
-    if (!cams || !state) return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: NULL cameras or state");
+static int lm_update_rig_launch(const char* who, const ehr_lm_rig_camera* cams, int C, float* offset, const int32_t* free_list,
+                                int F, int J, double ftol, double lambda_max, int finalize, double* state, double* log,
+                                int log_rows, const double* prior_weight, const double* prior_mean, void* stream) {
+    if (!cams || !state) return fail(EHR_ERR_INVALID, "%s: NULL cameras or state", who);
     if (F < 0 || (F > 0 && (!offset || !free_list || J < 1 || J > 32)))
-        return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: free joints need offset and the list (J %d <= 32)", J);
+        return fail(EHR_ERR_INVALID, "%s: free joints need offset and the list (J %d <= 32)", who, J);
     if (C < 1 || C > EHR_LM_RIG_MAX_CAMERAS || 6 * C + F > EHR_LM_MAX_PARAMS)
-        return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: %d cameras and %d free joints are N = %d parameters; 1 <= C and N <= %d",
-                    C, F, 6 * C + F, EHR_LM_MAX_PARAMS);
+        return fail(EHR_ERR_INVALID, "%s: %d cameras and %d free joints are N = %d parameters; 1 <= C and N <= %d", who, C, F,
+                    6 * C + F, EHR_LM_MAX_PARAMS);
     LmRigCameras by_value = {};
     for (int c = 0; c < C; c++) {  // (a HOST array: every field can be judged here)
         const ehr_lm_rig_camera& k = cams[c];
         if (!k.info || !k.grad || !k.count || !k.loss || !k.dof)
-            return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: camera %d has a NULL pointer", c);
-        if (k.B < 1) return fail(EHR_ERR_INVALID, "ehr_lm_update_rig: camera %d has B %d < 1", c, k.B);
+            return fail(EHR_ERR_INVALID, "%s: camera %d has a NULL pointer", who, c);
+        if (k.B < 1) return fail(EHR_ERR_INVALID, "%s: camera %d has B %d < 1", who, c, k.B);
         by_value.c[c] = k;
     }
-    lm_update_rig_kernel<<<1, 64, 0, (hipStream_t)stream>>>(by_value, C, offset, free_list, F, J, ftol, lambda_max, finalize, state,
-                                                           log && log_rows > 0 ? log : nullptr, log_rows);
+    if (int rc = lm_prior_check(who, prior_weight, prior_mean)) return rc;
+    double* const lg = log && log_rows > 0 ? log : nullptr;
+    if (prior_weight)
+        lm_update_rig_kernel<true><<<1, 64, 0, (hipStream_t)stream>>>(by_value, C, offset, free_list, F, J, ftol, lambda_max,
+                                                                     finalize, state, lg, log_rows,
+                                                                     LmPriorArgs<true>{prior_weight, prior_mean});
+    else
+        lm_update_rig_kernel<false><<<1, 64, 0, (hipStream_t)stream>>>(by_value, C, offset, free_list, F, J, ftol, lambda_max,
+                                                                      finalize, state, lg, log_rows, LmPriorArgs<false>{});
     EHR_LAUNCH_CHECK();
     return EHR_OK;
+}
+
+int ehr_lm_update_rig(const ehr_lm_rig_camera* cams, int C, float* offset, const int32_t* free_list, int F, int J, double ftol,
+                      double lambda_max, int finalize, double* state, double* log, int log_rows, void* stream) {
+    return lm_update_rig_launch("ehr_lm_update_rig", cams, C, offset, free_list, F, J, ftol, lambda_max, finalize, state, log,
+                                log_rows, nullptr, nullptr, stream);
+}
+
+int ehr_lm_update_rig_prior(const ehr_lm_rig_camera* cams, int C, float* offset, const int32_t* free_list, int F, int J,
+                            double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                            const double* prior_weight, const double* prior_mean, void* stream) {
+    return lm_update_rig_launch("ehr_lm_update_rig_prior", cams, C, offset, free_list, F, J, ftol, lambda_max, finalize, state,
+                                log, log_rows, prior_weight, prior_mean, stream);
 }
 
 }  // extern "C"

@@ -13,7 +13,9 @@ information matrix at the solution, so :func:`solve_lm` returns the :class:`easy
 accepted point without another call.
 
 It is a refinement BESIDE Adam, not a new default: it does not touch Adam's moments, step counters or ``history_ops``, has no
-weight decay (no prior towards the given intrinsics or zero offsets), and far from the optimum its quadratic model is poor
+weight decay unless asked for one -- a Gaussian prior towards the given intrinsics, zero offsets or any other mean
+(:func:`make_prior`, ``solve_lm(..., prior_sigma=...)``) -- and far from the optimum its quadratic model
+is poor
 (the squared error of binary silhouettes is linear in the displacement): the accept / reject rule, not the model, makes it
 safe.  It renders the float32 matrix ``ehr_pose_forward`` builds -- the loss it minimises is the loss the Adam solve reports,
 bit for bit -- where :func:`easyhec_amd.information.information_of` renders a float64-built one.  HIP only; no fallback.
@@ -32,7 +34,7 @@ import torch
 
 from . import _lib, fused, information
 
-__all__ = ["LevenbergMarquardt", "LmResult", "solve_lm", "WHY"]
+__all__ = ["LevenbergMarquardt", "LmResult", "LmPrior", "make_prior", "solve_lm", "WHY"]
 
 WHY = {0: "running", 1: "ftol: the predicted reduction is below ftol * loss", 2: "lambda_max: the damping reached its limit",
        3: "step: every parameter's step is below float32's spacing", 4: "factorisation: the damped matrix kept failing to factor"}
@@ -118,7 +120,44 @@ class _LmDriver:
     the rig has one per camera (:class:`easyhec_amd.lm_rig.RigLM`).  A subclass sets ``dev``, ``N`` (the parameters of a
     state block) and ``names``, calls :meth:`_init_driver`, and provides the ONE C call ``_update(stream, finalize=0)``.
     ``who`` names the owner in the guard's messages."""
-    who, label, _forward_kinematics = "solve_lm", "", None
+    who, label, _forward_kinematics, prior = "solve_lm", "", None, None
+
+    def set_prior(self, prior):
+        """Take an :class:`LmPrior` made for this driver's parameters (None: no prior, today's update).  Set before the first
+        iteration: ``F_acc`` of an accepted point carries the prior's term."""
+        if prior is not None:
+            if not isinstance(prior, LmPrior):
+                raise TypeError(f"{self.who}: prior is an LmPrior (make_prior), not {type(prior).__name__}")
+            if list(prior.names) != list(self.names):
+                raise ValueError(f"{self.who}: the prior was made for {list(prior.names)}, the solve optimises "
+                                 f"{list(self.names)}")
+            if not _lib.has_lm_prior():
+                raise RuntimeError("this libehr_hip.so has no prior form of the update (ehr_lm_update_prior): rebuild it")
+            if getattr(self, "calls", 0):
+                raise RuntimeError(f"{self.who}: the prior is set before the first iteration")
+        self.prior = prior
+        return self
+
+    def _prior_ptrs(self):
+        return _lib.ptr(self.prior.weight), _lib.ptr(self.prior.mean)
+
+    def evaluate(self):
+        """(summed loss, summed count) of ONE ``ehr_mask_information`` evaluation of every unit at the current parameters; the
+        state block is not touched.  Synchronises."""
+        self._guard()
+        with torch.cuda.device(self.dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for u in self.units:
+                if u._forward_kinematics is not None:
+                    u._forward_kinematics(stream)
+                u._linearize(stream)
+                o = u.out
+                information._launch(u.glctx, u.scene, u.mvp, u.dmvp, u.ref, o.info, o.grad, o.count, o.loss, None)
+        loss, count = 0.0, 0
+        for u in self.units:
+            loss += float(u.out.loss.double().sum().item())
+            count += int(u.out.count.sum().item())
+        return loss, count
 
     def _init_driver(self, P, lambda0, ftol, lambda_max, log_rows, units=None):
         N, dev = self.N, self.dev
@@ -181,7 +220,8 @@ class _LmDriver:
     def states(self):
         """The P state blocks as a list of namespaces (one copy of [P,EHR_LM_STATE_DOUBLES]; synchronises): lambda, nu,
         F_acc, pred, rho, F_trial, the counters iterations / accepted / rejected / reported / retries, done, why, last,
-        count, and theta [N], delta [N], g [N], H [N,N] of the accepted point."""
+        count, F_prior (the prior's term of F_acc; 0 without a prior) and theta [N], delta [N], g [N], H [N,N] of the accepted
+        point (H and g: the data's own, under a prior too)."""
         s = self._state.cpu().numpy()
         return [state_namespace(s[p], self.N) for p in range(self.P)]
 
@@ -194,7 +234,22 @@ class _LmDriver:
     def report(self, p, state=None):
         """The :class:`easyhec_amd.information.InformationReport` of hypothesis p's accepted point, from its state block."""
         s = self.states()[p] if state is None else state
-        return information.InformationReport(s.H[None], self.names, s.g[None], [s.count], [s.F_acc])
+        data_loss = s.F_acc - getattr(s, "F_prior", 0.0)
+        return information.InformationReport(s.H[None], self.names, s.g[None], [s.count], [data_loss])
+
+    def posterior(self, p=0, state=None):
+        """Under a prior: the :class:`easyhec_amd.information.InformationReport` over ``H_views = [H_data, diag(weight)]`` and
+        the matching gradients at the accepted point; its ``sigma2()`` is the prior's (the variance the weights were formed
+        with), so ``covariance()`` is the posterior's.  None without a prior."""
+        if self.prior is None:
+            return None
+        s = self.states()[p] if state is None else state
+        w, mu = self.prior.weight.cpu().numpy(), self.prior.mean.cpu().numpy()
+        gp = np.where(w != 0, 2.0 * w * (s.theta - np.where(w != 0, mu, 0.0)), 0.0)
+        rep = information.InformationReport(np.stack([s.H, np.diag(w)]), self.names, np.stack([s.g, gp]), [s.count], [s.F_acc])
+        sigma2 = self.prior.sigma2
+        rep.sigma2 = lambda: sigma2
+        return rep
 
 
 class LevenbergMarquardt(_LmDriver):
@@ -208,7 +263,7 @@ class LevenbergMarquardt(_LmDriver):
     offsets; a trial is in them between iterations).  ``state_block`` [EHR_LM_STATE_DOUBLES] and ``log`` [log_rows,4] are the
     one hypothesis's."""
 
-    def __init__(self, step, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256):
+    def __init__(self, step, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256, prior=None):
         _refuse(step)
         self.step, self.dev = step, step.dev
         self.glctx, self.scene, self.ref, self.weight = step.glctx, step.scene, step.ref, getattr(step, "weight", None)
@@ -219,6 +274,7 @@ class LevenbergMarquardt(_LmDriver):
         self.free_list = torch.tensor(lay.free, dtype=torch.int32, device=self.dev) if lay.free else None
         self._init_driver(1, lambda0, ftol, lambda_max, log_rows)
         self.state_block, self.log = self._state[0], self._log[0]  # (views: the same memory)
+        self.set_prior(prior)
 
     def _linearize(self, stream):
         st = self.step
@@ -228,12 +284,30 @@ class LevenbergMarquardt(_LmDriver):
     def _update(self, stream, finalize=0):
         st, o = self.step, self.out
         intr = self.free4_mask != 0
-        _lib.check(_lib.lib().ehr_lm_update(
-            _lib.ptr(o.info), _lib.ptr(o.grad), _lib.ptr(o.count), _lib.ptr(o.loss), st.B, self.N, _lib.ptr(st.model.dof.data),
-            _lib.ptr(st.offsets if self.F else None), _lib.ptr(self.free_list), self.F, self.J,
-            _lib.ptr(st.theta if intr else None), self.free4_mask, self.tie_focal, _lib.ptr(st.K0 if intr else None),
-            _lib.ptr(st.K if intr else None), st.H, st.W, ctypes.c_double(self.ftol), ctypes.c_double(self.lambda_max),
-            int(finalize), _lib.ptr(self.state_block), _lib.ptr(self.log), self.log_rows, stream), "ehr_lm_update")
+        args = (_lib.ptr(o.info), _lib.ptr(o.grad), _lib.ptr(o.count), _lib.ptr(o.loss), st.B, self.N,
+                _lib.ptr(st.model.dof.data), _lib.ptr(st.offsets if self.F else None), _lib.ptr(self.free_list), self.F, self.J,
+                _lib.ptr(st.theta if intr else None), self.free4_mask, self.tie_focal, _lib.ptr(st.K0 if intr else None),
+                _lib.ptr(st.K if intr else None), st.H, st.W, ctypes.c_double(self.ftol), ctypes.c_double(self.lambda_max),
+                int(finalize), _lib.ptr(self.state_block), _lib.ptr(self.log), self.log_rows)
+        if self.prior is None:
+            _lib.check(_lib.lib().ehr_lm_update(*args, stream), "ehr_lm_update")
+        else:
+            _lib.check(_lib.lib().ehr_lm_update_prior(*args, *self._prior_ptrs(), stream), "ehr_lm_update_prior")
+
+    def parameters(self):
+        """The N parameters as the step's tensors hold them, in ``names``' order (float32, host).  Synchronises."""
+        st = self.step
+        out = [st.model.dof.detach().cpu().numpy().reshape(-1)[:6]]
+        if self.F:
+            out.append(st.offsets.detach().cpu().numpy()[list(self.layout.free)])
+        if self.free4_mask:
+            th = st.theta.detach().cpu().numpy()
+            first = {"f": 0, "fx": 0, "fy": 1, "cx": 2, "cy": 3}
+            out.append(np.array([th[first[nm[6:-1]]] for nm in self.names[6 + self.F:]], dtype=np.float32))
+        return np.concatenate(out).astype(np.float32)
+
+    def joint_kinds(self):
+        return self.kin.jkind.cpu().numpy() if self.kin is not None else None
 
     def _forward_kinematics(self, stream):
         if self.kin is not None:
@@ -248,8 +322,120 @@ class LevenbergMarquardt(_LmDriver):
         return super().trajectory(0)
 
     def report(self, state=None):
-        """The :class:`easyhec_amd.information.InformationReport` of the accepted point, from the state block alone."""
+        """The :class:`easyhec_amd.information.InformationReport` of the accepted point, from the state block alone (the
+        data's report, under a prior too)."""
         return super().report(0, state)
+
+    def posterior(self, state=None):
+        """:meth:`_LmDriver.posterior` of the one hypothesis."""
+        return super().posterior(0, state)
+
+
+# ---- the prior ------------------------------------------------------------------------------------------------------------
+@dataclass
+class LmPrior:
+    """A diagonal Gaussian prior for a Levenberg-Marquardt solve: ``F = sum_views w (mask - ref)^2 + sum_k weight_k (theta_k -
+    mean_k)^2`` with ``weight_k = sigma2 / sigma_k^2`` (0 where there is no prior on parameter k)."""
+    weight: torch.Tensor        # [N] float64, device: p_k, in loss units per squared parameter unit
+    mean: torch.Tensor          # [N] float64, device: mu_k
+    sigma: np.ndarray           # [N] float64: one standard deviation per parameter, inf where there is none
+    sigma2: float               # the residual variance that puts prior and data in the same units; fixed for the solve
+    names: list
+
+
+def _prior_kinds(names, joint_kind):
+    """``info_explorer.parameter_kinds`` extended to the rig's ``camK.dof[i]`` names."""
+    from .info_explorer import parameter_kinds
+    return parameter_kinds([nm.split(".", 1)[1] if nm.startswith("cam") and "." in nm else nm for nm in names], joint_kind)
+
+
+def _no_prior_arguments(who, prior_sigma, sigma2, prior_mean, allowed=False):
+    if allowed:
+        if prior_sigma is None and (sigma2 is not None or prior_mean is not None):
+            raise ValueError(f"{who}: sigma2 and prior_mean belong to a prior: pass prior_sigma as well")
+        return
+    if prior_sigma is not None or sigma2 is not None or prior_mean is not None:
+        raise ValueError(f"{who}: no prior is available for the multi-start solve: it is pose-only, and the prior is for "
+                         "offsets and intrinsics (solve_lm and solve_lm_rig take one)")
+
+
+def make_prior(driver_or_step, prior_sigma, sigma2=None, prior_mean=None):
+    """The :class:`LmPrior` of a solve.  ``driver_or_step``: a :class:`LevenbergMarquardt` or
+    :class:`easyhec_amd.lm_rig.RigLM`, or the step object one would drive (a driver is then made for the call).
+
+    ``prior_sigma``: ``"default"`` -- ``info_explorer.PRIOR_SIGMA`` by kind for the offsets and the intrinsics, NO prior on a
+    pose coordinate; a dict by parameter name or by kind (what it does not mention gets none); a number (every parameter); or
+    a sequence of N (``inf`` or None: none).  ``prior_mean``: None, a dict by name, or a sequence of N; where it says nothing
+    an offset's mean is 0, an intrinsics parameter's 0 (the given K) and a pose coordinate's its value NOW.  ``sigma2``: a
+    positive number, or None for ``loss / max(count - N, 1)`` of ONE ``ehr_mask_information`` evaluation at the current
+    parameters (the explorer's formula, ``InformationReport.sigma2``'s): one synchronising read; it then stays fixed for the
+    solve and is recorded in the result.  That default is meant for a polish from near the optimum: far from it the loss is
+    large, so it OVERWEIGHTS the prior -- pass a value there.
+
+    ValueError, with the reason: a sigma <= 0 or NaN, a mean that is not finite under a finite sigma, a wrong length, unknown
+    names, ``sigma2 <= 0``."""
+    from .info_explorer import PRIOR_SIGMA
+    drv = driver_or_step
+    if not isinstance(drv, _LmDriver):
+        from .rig_calib import RigJointStep
+        if isinstance(drv, RigJointStep):
+            from .lm_rig import RigLM
+            drv = RigLM(drv)
+        else:
+            drv = LevenbergMarquardt(drv)
+    if drv.P != 1 or not hasattr(drv, "parameters"):
+        raise ValueError("make_prior: no prior is available for the multi-start solve (pose-only)")
+    names, N = list(drv.names), drv.N
+    kinds = _prior_kinds(names, drv.joint_kinds())
+    # sigma
+    if isinstance(prior_sigma, str):
+        if prior_sigma != "default":
+            raise ValueError(f"make_prior: prior_sigma {prior_sigma!r}: the one word is 'default'")
+        sig = [PRIOR_SIGMA[kd] if kd in ("revolute", "prismatic", "focal", "principal") else np.inf for kd in kinds]
+    elif isinstance(prior_sigma, dict):
+        unknown = [k for k in prior_sigma if k not in names and k not in PRIOR_SIGMA]
+        if unknown:
+            raise ValueError(f"make_prior: prior_sigma {unknown}: keys are parameter names {names} or kinds {list(PRIOR_SIGMA)}")
+        sig = [prior_sigma.get(nm, prior_sigma.get(kd, np.inf)) for nm, kd in zip(names, kinds)]
+    elif np.ndim(prior_sigma) == 0 and prior_sigma is not None:
+        sig = [prior_sigma] * N
+    else:
+        if prior_sigma is None or len(prior_sigma) != N:
+            raise ValueError(f"make_prior: prior_sigma is 'default', a dict, a number or a sequence of N = {N} ({names})")
+        sig = list(prior_sigma)
+    sig = np.array([np.inf if x is None else float(x) for x in sig], dtype=np.float64)
+    if np.isnan(sig).any() or (sig <= 0).any():
+        raise ValueError(f"make_prior: every sigma is > 0 (inf or None: no prior), got {dict(zip(names, sig.tolist()))}")
+    has = np.isfinite(sig)
+    # mean
+    now = drv.parameters().astype(np.float64)
+    mean = np.where([kd in ("translation", "rotation") for kd in kinds], now, 0.0)
+    if isinstance(prior_mean, dict):
+        unknown = [k for k in prior_mean if k not in names]
+        if unknown:
+            raise ValueError(f"make_prior: prior_mean {unknown}: keys are parameter names {names}")
+        for k, v in prior_mean.items():
+            mean[names.index(k)] = float(v)
+    elif prior_mean is not None:
+        if np.ndim(prior_mean) != 1 or len(prior_mean) != N:
+            raise ValueError(f"make_prior: prior_mean is None, a dict by name or a sequence of N = {N} ({names})")
+        mean = np.array([float(x) for x in prior_mean], dtype=np.float64)
+    if not np.isfinite(mean[has]).all():
+        raise ValueError(f"make_prior: the mean under a finite sigma is finite, got {dict(zip(names, mean.tolist()))}")
+    mean = np.where(has, mean, 0.0)
+    # sigma2
+    if sigma2 is None:
+        loss, count = drv.evaluate()
+        sigma2 = loss / max(count - N, 1)
+        if not (np.isfinite(sigma2) and sigma2 > 0):
+            raise ValueError(f"make_prior: the evaluation at the current parameters gives sigma2 = {sigma2} (loss {loss}, count "
+                             f"{count}): pass sigma2")
+    elif not (np.isfinite(sigma2) and sigma2 > 0):
+        raise ValueError(f"make_prior: sigma2 must be finite and > 0, got {sigma2}")
+    weight = np.where(has, float(sigma2) / np.where(has, sig, 1.0) ** 2, 0.0)
+    if not np.isfinite(weight).all():
+        raise ValueError(f"make_prior: sigma2 / sigma^2 overflows: {dict(zip(names, weight.tolist()))}")
+    return LmPrior(torch.from_numpy(weight).to(drv.dev), torch.from_numpy(mean).to(drv.dev), sig, float(sigma2), names)
 
 
 @dataclass
@@ -266,6 +452,10 @@ class LmResult:
     recoveries: list = field(default_factory=list)
     state: object = None        # the final state namespace
     lm: object = None           # the LevenbergMarquardt object
+    data_loss: float = None     # F_acc - F_prior: the summed per-view loss at the accepted point (== loss without a prior)
+    prior_loss: float = 0.0     # F_prior: sum_k p_k (theta_k - mu_k)^2 at the accepted point
+    prior: object = None        # the LmPrior the solve ran under (sigma2 included), or None
+    posterior: object = None    # under a prior: InformationReport over [H_data, diag(weight)]; covariance() is the posterior's
 
 
 def _run_to_convergence(driver, max_iters, check_every, recover, check_status, who):
@@ -296,12 +486,28 @@ def _run_to_convergence(driver, max_iters, check_every, recover, check_status, w
     return recoveries
 
 
-def solve_lm(step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6):
+def result_of(lm, recoveries):
+    """The :class:`LmResult` of a finished one-block solve (``solve_lm``, ``solve_lm_rig``)."""
+    s = lm.state()
+    why = WHY[s.why].split(":")[0] if s.done else "max_iters"
+    return LmResult(s.F_acc, s.iterations, s.accepted, s.rejected, s.reported, bool(s.done), why, lm.trajectory(),
+                    lm.report(s), recoveries, s, lm, s.F_acc - s.F_prior, s.F_prior, lm.prior, lm.posterior(s))
+
+
+def solve_lm(step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, prior_sigma=None, sigma2=None,
+             prior_mean=None):
     """Levenberg-Marquardt on ``step``'s parameters from where they are: at most ``max_iters`` EFFECTIVE iterations (a
     reported one -- the plan's job slots overflowed, the view needs the general-triangle pass -- is recovered from the way
     ``_ChainStep`` recovers a step, and taken again), ``done`` polled every ``check_every`` iterations.  Ends with the accepted
-    parameters in the step's tensors; a captured chain stays valid.  Returns an :class:`LmResult`."""
+    parameters in the step's tensors; a captured chain stays valid.  Returns an :class:`LmResult`.
+
+    ``prior_sigma`` (None: no prior, today's solve bit for bit), ``sigma2``, ``prior_mean``: :func:`make_prior`'s -- the solve
+    is then the MAP estimate: ``loss`` is the total objective, ``data_loss`` and ``prior_loss`` its two parts, ``report`` the
+    data's report and ``posterior`` the posterior's."""
     lm = LevenbergMarquardt(step, lambda0=lambda0, ftol=ftol, lambda_max=lambda_max, log_rows=max_iters + 4 * check_every + 8)
+    _no_prior_arguments("solve_lm", prior_sigma, sigma2, prior_mean, allowed=True)
+    if prior_sigma is not None:
+        lm.set_prior(make_prior(lm, prior_sigma, sigma2, prior_mean))
 
     def recover():
         what = step.recover_from_overflow() if hasattr(step, "recover_from_overflow") else False
@@ -310,7 +516,4 @@ def solve_lm(step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_
         return what
 
     recoveries = _run_to_convergence(lm, max_iters, check_every, recover, lambda: fused.check_status(step.glctx), "solve_lm")
-    s = lm.state()
-    why = WHY[s.why].split(":")[0] if s.done else "max_iters"
-    return LmResult(s.F_acc, s.iterations, s.accepted, s.rejected, s.reported, bool(s.done), why, lm.trajectory(),
-                    lm.report(s), recoveries, s, lm)
+    return result_of(lm, recoveries)

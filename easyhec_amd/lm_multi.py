@@ -25,7 +25,7 @@ import torch
 from . import _lib, dr, fused
 from .chain_step import _PlannedContext
 from .fast import _hip_device, _private_weight
-from .lm import WHY, _LmDriver, _run_to_convergence
+from .lm import WHY, _LmDriver, _no_prior_arguments, _run_to_convergence
 from .multistart import _starts_to_dof, rank_losses
 from .se3 import se3_exp_map
 
@@ -167,13 +167,15 @@ def _result(ms, recoveries):
 
 
 def solve_lm_multi(model, batch, starts, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, near=0.001,
-                   far=10.0, slack=None):
+                   far=10.0, slack=None, prior_sigma=None, sigma2=None, prior_mean=None):
     """:func:`easyhec_amd.lm.solve_lm` for P starts at once, with its loop: the hypotheses are polled every ``check_every``
     iterations; reported iterations are recovered from the way ``_ChainStep`` recovers a step (at most 4 rounds, then it
     raises) and taken again; it stops when every hypothesis is done, or when the hypotheses still running have taken
     ``max_iters`` EFFECTIVE iterations (the one that has taken fewest counts), and ends with the accepted poses in the
     object's ``dof``.  The hypotheses are ranked by ``F_acc``, an exact loss (float64 sum of the views' losses at the
-    accepted pose) -- no tail mean.  The model is NOT written.  Returns a :class:`MultiLmResult`."""
+    accepted pose) -- no tail mean.  The model is NOT written.  Returns a :class:`MultiLmResult`.  A prior argument
+    (``prior_sigma``, ``sigma2``, ``prior_mean``) is refused: the multi-start solve is pose-only."""
+    _no_prior_arguments("solve_lm_multi", prior_sigma, sigma2, prior_mean)
     ms = MultiStartLM(model, batch, starts, lambda0=lambda0, ftol=ftol, lambda_max=lambda_max,
                       log_rows=max_iters + 4 * check_every + 8, near=near, far=far, slack=slack)
     recoveries = _run_to_convergence(ms, max_iters, check_every, ms.recover_from_overflow,
@@ -182,13 +184,16 @@ def solve_lm_multi(model, batch, starts, max_iters=50, check_every=5, lambda0=1e
 
 
 def solve_global_lm(model, batch, Tc_init, Q, P, max_iters=50, check_every=5, trans_sigma_m=0.03, rot_sigma_deg=4.0, seed=0,
-                    extra=None, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, slack=None, score="xor", cap_px=None):
+                    extra=None, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, slack=None, score="xor", cap_px=None, prior_sigma=None,
+                    sigma2=None, prior_mean=None):
     """A global solve that needs no tuning: :func:`easyhec_amd.pose_search.search_starts` (Q candidates scored by mask
     overlap, the best P kept), then :func:`solve_lm_multi` from its starts -> ``(PoseSearchResult, MultiLmResult)``.  The
     winner's accepted dof is written into ``model.dof``; ``history_ops`` and any Adam state stay untouched, as for
     ``solve_lm``.  Hypothesis 0 is ``Tc_init``: it is the plain ``solve_lm`` from there bit for bit, so the winner's loss
     never exceeds it.  ``score`` and ``cap_px`` go to ``search_starts`` (``score="soft"``: the soft IoU, which still ranks
-    candidates that no longer overlap the observed masks, so the draw may be wide)."""
+    candidates that no longer overlap the observed masks, so the draw may be wide).  A prior argument is refused, as by
+    ``solve_lm_multi``."""
+    _no_prior_arguments("solve_global_lm", prior_sigma, sigma2, prior_mean)
     from .pose_search import search_starts
     search = search_starts(model, batch, Tc_init, Q, P, trans_sigma_m, rot_sigma_deg, seed, extra=extra, score=score, cap_px=cap_px)
     res = solve_lm_multi(model, batch, search.starts, max_iters=max_iters, check_every=check_every, lambda0=lambda0, ftol=ftol,

@@ -21,10 +21,11 @@ call.  The iteration and the solve loop are :mod:`easyhec_amd.lm`'s (``_LmDriver
 graph capture, more than 32 parameters, information-gain exploration for a rig."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
-from .lm import WHY, LmResult, _LmDriver, _run_to_convergence, launch_linearize, parameter_layout
+from .lm import _LmDriver, _run_to_convergence, launch_linearize, make_prior, parameter_layout, result_of
 
 __all__ = ["RigLM", "solve_lm_rig"]
 
@@ -80,7 +81,7 @@ class RigLM(_LmDriver):
     the one system's."""
     who = "solve_lm_rig"
 
-    def __init__(self, rig_step, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256):
+    def __init__(self, rig_step, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256, prior=None):
         _refuse(rig_step)
         self.rig, self.dev = rig_step, rig_step.dev
         self.C, self.J = rig_step.C, rig_step.J
@@ -92,6 +93,7 @@ class RigLM(_LmDriver):
         self.mvp, self.dmvp, self.out = [u.mvp for u in self.units], [u.dmvp for u in self.units], [u.out for u in self.units]
         self.state_block, self.log = self._state[0], self._log[0]  # (views: the same memory)
         self._cams, self._cams_key = None, None
+        self.set_prior(prior)
 
     def _camera_array(self):
         """The HOST array of ``ehr_lm_rig_camera``; built once, and again whenever a pointer in it has changed (a model's
@@ -103,10 +105,24 @@ class RigLM(_LmDriver):
         return self._cams
 
     def _update(self, stream, finalize=0):
-        _lib.check(_lib.lib().ehr_lm_update_rig(
-            self._camera_array(), self.C, _lib.ptr(self.rig.offsets if self.F else None), _lib.ptr(self.free_list), self.F, self.J,
-            ctypes.c_double(self.ftol), ctypes.c_double(self.lambda_max), int(finalize), _lib.ptr(self.state_block),
-            _lib.ptr(self.log), self.log_rows, stream), "ehr_lm_update_rig")
+        args = (self._camera_array(), self.C, _lib.ptr(self.rig.offsets if self.F else None), _lib.ptr(self.free_list), self.F,
+                self.J, ctypes.c_double(self.ftol), ctypes.c_double(self.lambda_max), int(finalize), _lib.ptr(self.state_block),
+                _lib.ptr(self.log), self.log_rows)
+        if self.prior is None:
+            _lib.check(_lib.lib().ehr_lm_update_rig(*args, stream), "ehr_lm_update_rig")
+        else:
+            _lib.check(_lib.lib().ehr_lm_update_rig_prior(*args, *self._prior_ptrs(), stream), "ehr_lm_update_rig_prior")
+
+    def parameters(self):
+        """The ``6 C + F`` parameters as the rig's tensors hold them, in ``names``' order (float32, host).  Synchronises."""
+        out = [cam.model.dof.detach().cpu().numpy().reshape(-1)[:6] for cam in self.rig.cameras]
+        if self.F:
+            out.append(self.rig.offsets.detach().cpu().numpy()[[int(j) for j in self.free_list.cpu().numpy()]])
+        return np.concatenate(out).astype(np.float32)
+
+    def joint_kinds(self):
+        kin = self.units[0].layout.kin
+        return kin.jkind.cpu().numpy() if kin is not None else None
 
     def state(self):
         """The state block as one namespace: :meth:`easyhec_amd.lm._LmDriver.states` of the one system."""
@@ -117,21 +133,31 @@ class RigLM(_LmDriver):
         return super().trajectory(0)
 
     def report(self, state=None):
-        """The :class:`easyhec_amd.information.InformationReport` of the ``6 C + F`` system at the accepted point."""
+        """The :class:`easyhec_amd.information.InformationReport` of the ``6 C + F`` system at the accepted point (the data's,
+        under a prior too)."""
         return super().report(0, state)
 
+    def posterior(self, state=None):
+        """:meth:`easyhec_amd.lm._LmDriver.posterior` of the one system."""
+        return super().posterior(0, state)
 
-def solve_lm_rig(rig_step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6):
+
+def solve_lm_rig(rig_step, max_iters=50, check_every=5, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, prior_sigma=None, sigma2=None,
+                 prior_mean=None):
     """:func:`easyhec_amd.lm.solve_lm` for a rig, with its loop: Levenberg-Marquardt on every camera's pose and the shared
     offsets from where they are, at most ``max_iters`` EFFECTIVE iterations (a reported one is rig-wide; every camera's
     context is recovered the way the rig's Adam solve recovers them -- ``recoveries`` reads "camera c: job slots" -- and the
     iteration is taken again), ``done`` polled every ``check_every`` iterations.  Ends with the accepted poses in every
     ``model.dof``, the accepted offsets in ``rig_step.offsets`` and the link poses at them.  Returns an
     :class:`easyhec_amd.lm.LmResult`: ``loss`` is the summed loss over all views of all cameras, ``report`` the
-    ``InformationReport`` of the ``6 C + F`` system with ``rig_information``'s names."""
+    ``InformationReport`` of the ``6 C + F`` system with ``rig_information``'s names.  ``prior_sigma`` (None: no prior),
+    ``sigma2``, ``prior_mean``: :func:`easyhec_amd.lm.make_prior`'s over the rig's names -- with ``"default"`` the shared offsets
+    are held near zero and no camera's pose is; the result's ``data_loss``, ``prior_loss``, ``prior`` and ``posterior`` as for
+    ``solve_lm``."""
     lm = RigLM(rig_step, lambda0=lambda0, ftol=ftol, lambda_max=lambda_max, log_rows=max_iters + 4 * check_every + 8)
+    if prior_sigma is None and (sigma2 is not None or prior_mean is not None):
+        raise ValueError("solve_lm_rig: sigma2 and prior_mean belong to a prior: pass prior_sigma as well")
+    if prior_sigma is not None:
+        lm.set_prior(make_prior(lm, prior_sigma, sigma2, prior_mean))
     notes = _run_to_convergence(lm, max_iters, check_every, rig_step._recover_and_note, rig_step._check_status, "solve_lm_rig")
-    s = lm.state()
-    why = WHY[s.why].split(":")[0] if s.done else "max_iters"
-    return LmResult(s.F_acc, s.iterations, s.accepted, s.rejected, s.reported, bool(s.done), why, lm.trajectory(), lm.report(s),
-                    [what for did in notes for what in did], s, lm)
+    return result_of(lm, [what for did in notes for what in did])

@@ -547,7 +547,8 @@ int ehr_intrinsics_backward_adam(const float* grad_mvp, const float* tc_jac, con
  *     [ehr_joint_forward, if joints are free] -> ehr_lm_linearize -> ehr_mask_information -> ehr_lm_update      on one stream,
  * with no host round trip: the state of the solve lives in a device block (below).  Both calls take device pointers only, never
  * allocate or synchronise and launch on `stream`.  Adam's moments, its step counters and the pose history are not touched, and
- * there is no weight decay: this is a refinement beside the Adam solves, not a replacement.
+ * there is no weight decay unless the caller asks for a Gaussian prior (ehr_lm_update_prior, below): this is a refinement beside
+ * the Adam solves, not a replacement.
  * The N <= EHR_LM_MAX_PARAMS parameters are ordered as easyhec_amd.information.information_of orders them: dof[0..5], then
  * offset[free_list[0..F)], then the free intrinsics in the order f (tie_focal: theta[0] and theta[1] as one) | fx, fy, then cx, cy;
  * free4_mask has bit i set where theta[i] is free (tie_focal needs bits 0 and 1), and N = 6 + F + Fi.
@@ -603,6 +604,7 @@ int ehr_intrinsics_backward_adam(const float* grad_mvp, const float* tc_jac, con
 #define EHR_LM_LAST 12       /* the last iteration: 1 accepted, 0 rejected, -1 reported */
 #define EHR_LM_COUNT 13      /* sum_b count[b] at the accepted point */
 #define EHR_LM_RETRIES 14    /* non-positive pivots met so far */
+#define EHR_LM_F_PRIOR 15    /* the prior's term of F_acc (ehr_lm_update_prior; never written without a prior) */
 #define EHR_LM_THETA 16      /* [32] the accepted parameters */
 #define EHR_LM_DELTA 48      /* [32] the last delta */
 #define EHR_LM_G 80          /* [32] g_acc */
@@ -616,6 +618,32 @@ int ehr_lm_update(const double* info, const double* grad, const long long* count
                   float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask, int tie_focal,
                   const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize, double* state,
                   double* log, int log_rows, void* stream);
+
+/* Levenberg-Marquardt with a Gaussian prior: the MAP estimate
+ *     F(theta) = sum_views w (mask - ref)^2 + sum_k p_k (theta_k - mu_k)^2,     p_k = sigma2 / sigma_k^2  (the caller's),
+ * for the solo update and the rig's.  prior_weight, prior_mean: [N] float64 device arrays in the parameter order of the state
+ * block (the rig's: N = 6 C + F); p_k == 0 puts no prior on parameter k.  Both NULL: the call IS ehr_lm_update /
+ * ehr_lm_update_rig, bit for bit (they are these entries called with NULL, NULL); one NULL and the other not: EHR_ERR_INVALID.
+ * Everything else is the update's, with these additions, in this order (float64, -ffp-contract=off: no fused multiply-add):
+ *   a. After step 1, at the trial (the parameters as the pointers hold them): d_k = (double) theta_k - mu_k,
+ *      Fp = sum_k (p_k * d_k) * d_k for k ascending from 0.0; terms with p_k == 0 are skipped, not added.  A non-finite Fp, a
+ *      non-finite mu_k where p_k != 0, or a p_k that is negative or not finite makes the call REPORTED (step 2; rig-wide).
+ *   b. Step 3 judges F = F_data + Fp (one addition): EHR_LM_F and EHR_LM_F_TRIAL hold this total, the log's first column too.
+ *      An accept stores Fp in EHR_LM_F_PRIOR: the data's loss at the accepted point is F_acc - F_prior.
+ *   c. The stored linearisation (EHR_LM_H, EHR_LM_G, EHR_LM_THETA) stays the DATA'S: sum w J J^T and the data's gradient.
+ *      Behind step 3, accepted or rejected, the system that is solved gets, for every k with p_k != 0,
+ *          H[k][k] += p_k        g[k] += 2.0 * p_k * (theta_acc_k - mu_k),
+ *      so a rejected call rebuilds exactly the system the accepting call solved.
+ *   d. Steps 4-6 run on that system: the scaling is the posterior diagonal's, and a parameter WITHOUT data information but
+ *      with p_k > 0 is no longer left out -- the prior alone pulls it towards mu_k (intended).  pred, ftol * F_acc,
+ *      lambda_max and the float32-spacing rule are unchanged; restore, finalize and done likewise.
+ * ehr_lm_update_multi has no such form (pose only).  Out of scope: full prior covariances, N > EHR_LM_MAX_PARAMS.
+ * ehr_version() is unchanged: the presence of these symbols is the capability check. */
+int ehr_lm_update_prior(const double* info, const double* grad, const long long* count, const float* loss, int B, int N,
+                        float* dof, float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask,
+                        int tie_focal, const float* K0, float* K, int H, int W, double ftol, double lambda_max, int finalize,
+                        double* state, double* log, int log_rows, const double* prior_weight, const double* prior_mean,
+                        void* stream);
 
 /* Multi-start Levenberg-Marquardt: the two calls above for P hypotheses of ONE problem, so that an iteration of all of them is
  *     ehr_lm_linearize_multi -> ehr_mask_information (P*Bv views) -> ehr_lm_update_multi                    on one stream,
@@ -677,6 +705,10 @@ typedef struct {            /* one camera of the rig's update; all pointers are 
 int ehr_lm_update_rig(const ehr_lm_rig_camera* cams /* HOST array [C] */, int C, float* offset, const int32_t* free_list, int F,
                       int J, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
                       void* stream);
+/* The rig's update under a Gaussian prior: see ehr_lm_update_prior; prior_weight, prior_mean [6 C + F] in the rig's order. */
+int ehr_lm_update_rig_prior(const ehr_lm_rig_camera* cams /* HOST array [C] */, int C, float* offset, const int32_t* free_list,
+                            int F, int J, double ftol, double lambda_max, int finalize, double* state, double* log,
+                            int log_rows, const double* prior_weight, const double* prior_mean, void* stream);
 
 /* Information-gain exploration: which candidate joint configuration to observe next.  A candidate is a group of S consecutive
  * views of info [Q,S,N,N] -- ehr_mask_information's matrices of the views the candidate WOULD give (the op's info does not depend
