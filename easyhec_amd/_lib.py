@@ -94,6 +94,12 @@ SIGNATURES = {
     "ehr_lm_linearize_multi": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 3),
     "ehr_lm_update_multi": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] + [ctypes.c_double] * 2 + [c_int] +
                             [c_void_p] * 2 + [c_int, c_void_p]),
+    "ehr_joint_forward_multi": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    "ehr_lm_linearize_multi_calib": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 4 + [c_int] * 5 +
+                                     [c_void_p] * 3),
+    "ehr_lm_update_multi_calib": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] +
+                                  [c_int] * 2 + [c_void_p] * 2 + [c_int] * 2 + [ctypes.c_double] * 2 + [c_int] +
+                                  [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
     "ehr_lm_update_rig": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
                           [c_void_p] * 2 + [c_int, c_void_p]),
     "ehr_lm_update_rig_prior": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
@@ -170,6 +176,10 @@ def has_lm():
 
 def has_lm_multi():
     return has_symbols("ehr_lm_linearize_multi", "ehr_lm_update_multi")
+
+
+def has_lm_multi_calib():
+    return has_symbols("ehr_joint_forward_multi", "ehr_lm_linearize_multi_calib", "ehr_lm_update_multi_calib")
 
 
 def has_lm_rig():

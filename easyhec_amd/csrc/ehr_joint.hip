@@ -4,6 +4,8 @@
 //   joint_forward      : qpos[b] + offset -> forward kinematics of the flat table (UrdfChain.joint_table), in float64 ->
 //                        link_poses [B,L,16] float32 (what ehr_solver_step reads) and joint_frames [B,J,6] float32 = the
 //                        world axis a and a world point p on the axis of every active joint.
+//   joint_forward_multi: the same for P hypotheses of one arm: virtual view p * Bv + j walks qpos[j] + offset[p] (the multi-start
+//                        Levenberg-Marquardt solve, easyhec_amd/lm_multi.py); the body is the solo kernel's device function.
 //   joint_backward_adam: grad_mvp [B,L,16] (written by the chain) -> d(sum_b loss_b) / d offset_j =
 //                        sum_{b,l: j upstream of l} <(PF @ Tc)^T grad_mvp[b,l], D_blj>, with
 //                            revolute  D = [[a]x R_l | a x (t_l - p); 0 0],   prismatic  D = [0 | a; 0 0]
@@ -30,24 +32,25 @@ namespace ehr {
 // F[i] = F[parent_i] @ OM[i] is serial in i and takes 16 lanes, one per entry.  Frames live in LDS (2 x 8 KB), never in a
 // per-thread array.  Malformed tables (a parent that does not precede its child, an index out of range) are the caller's
 // to refuse; here they only ever read inside the arrays and give NaN.
-__global__ void __launch_bounds__(64) joint_forward_kernel(const int* __restrict__ parent, const double* __restrict__ origin,
-                                                          const int* __restrict__ kind, const double* __restrict__ axis,
-                                                          const int* __restrict__ qidx, const int* __restrict__ use, int N,
-                                                          int J, int L, const double* __restrict__ qpos,
-                                                          const float* __restrict__ offset, float* __restrict__ link_poses,
-                                                          float* __restrict__ joint_frames) {
+// The body is joint_forward_view, for ONE view: qpos [J] and offset [J] are the rows it walks, link_poses [L,16] and
+// joint_frames [J,6] the view's own output; the solo and the multi-start kernel below both call it.
+__device__ __forceinline__ void joint_forward_view(const int* __restrict__ parent, const double* __restrict__ origin,
+                                                   const int* __restrict__ kind, const double* __restrict__ axis,
+                                                   const int* __restrict__ qidx, const int* __restrict__ use, int N, int J,
+                                                   int L, const double* __restrict__ qpos, const float* __restrict__ offset,
+                                                   float* __restrict__ link_poses, float* __restrict__ joint_frames) {
     __shared__ double OM[EHR_JOINT_MAX_LINKS][16];
     __shared__ double F[EHR_JOINT_MAX_LINKS][16];
     __shared__ double sc[EHR_JOINT_MAX_LINKS][3];  // sin, cos, q of the link's joint
     __shared__ int jlink[EHR_JOINT_MAX_JOINTS];    // the link active joint j moves
-    const int b = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     if (lane < EHR_JOINT_MAX_JOINTS) jlink[lane] = -1;
     __syncthreads();
     if (lane < N) {
         const int c = qidx[lane];
         double q = 0.0;
         if (c >= 0 && c < J) {
-            q = qpos[(size_t)b * J + c] + (double)offset[c];
+            q = qpos[c] + (double)offset[c];
             jlink[c] = lane;  // (one writer per joint: the host refuses a table in which two links share an active joint)
         }
         sc[lane][0] = sin(q);
@@ -103,8 +106,7 @@ __global__ void __launch_bounds__(64) joint_forward_kernel(const int* __restrict
     // one rounding, at the end
     for (int e = lane; e < L * 16; e += 64) {
         const int u = use[e >> 4];
-        link_poses[((size_t)b * L) * 16 + e] =
-            (u >= 0 && u < N) ? (float)F[u][e & 15] : __int_as_float(0x7fc00000);
+        link_poses[e] = (u >= 0 && u < N) ? (float)F[u][e & 15] : __int_as_float(0x7fc00000);
     }
     for (int e = lane; e < J * 6; e += 64) {
         const int j = e / 6, k = e - 6 * j;
@@ -116,8 +118,32 @@ __global__ void __launch_bounds__(64) joint_forward_kernel(const int* __restrict
             else        // p = the moved link's origin: on the axis of a revolute joint (unused for a prismatic one)
                 out = (float)F[i][4 * (k - 3) + 3];
         }
-        joint_frames[((size_t)b * J) * 6 + e] = out;
+        joint_frames[e] = out;
     }
+}
+
+__global__ void __launch_bounds__(64) joint_forward_kernel(const int* __restrict__ parent, const double* __restrict__ origin,
+                                                          const int* __restrict__ kind, const double* __restrict__ axis,
+                                                          const int* __restrict__ qidx, const int* __restrict__ use, int N,
+                                                          int J, int L, const double* __restrict__ qpos,
+                                                          const float* __restrict__ offset, float* __restrict__ link_poses,
+                                                          float* __restrict__ joint_frames) {
+    const size_t b = blockIdx.x;
+    joint_forward_view(parent, origin, kind, axis, qidx, use, N, J, L, qpos + b * J, offset, link_poses + b * L * 16,
+                       joint_frames + b * J * 6);
+}
+
+// P hypotheses of one arm (easyhec_amd/lm_multi.py): virtual view b = p * Bv + j walks qpos[j] + offset[p].
+__global__ void __launch_bounds__(64) joint_forward_multi_kernel(const int* __restrict__ parent, const double* __restrict__ origin,
+                                                                const int* __restrict__ kind, const double* __restrict__ axis,
+                                                                const int* __restrict__ qidx, const int* __restrict__ use,
+                                                                int N, int J, int L, const double* __restrict__ qpos,
+                                                                const float* __restrict__ offset, int Bv,
+                                                                float* __restrict__ link_poses,
+                                                                float* __restrict__ joint_frames) {
+    const size_t b = blockIdx.x, p = b / (size_t)Bv, j = b - p * (size_t)Bv;
+    joint_forward_view(parent, origin, kind, axis, qidx, use, N, J, L, qpos + j * J, offset + p * J, link_poses + b * L * 16,
+                       joint_frames + b * J * 6);
 }
 
 // The sum of one camera's offset gradient, shared by joint_backward_adam_kernel and rig_backward_adam_kernel; call with all
@@ -310,6 +336,21 @@ int ehr_joint_forward(const int32_t* parent, const double* origin, const int32_t
         return fail(EHR_ERR_INVALID, "ehr_joint_forward: bad sizes (N %d <= 64 links, J %d <= 32 joints, L %d, B %d)", N, J, L, B);
     joint_forward_kernel<<<B, 64, 0, (hipStream_t)stream>>>(parent, origin, kind, axis, qidx, use, N, J, L, qpos, offset,
                                                            link_poses, joint_frames);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_joint_forward_multi(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                            const int32_t* qidx, const int32_t* use, int N, int J, int L, const double* qpos,
+                            const float* offset, int P, int Bv, float* link_poses, float* joint_frames, void* stream) {
+    if (!parent || !origin || !kind || !axis || !qidx || !use || !qpos || !offset || !link_poses || !joint_frames)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward_multi: NULL tensor");
+    if (N < 1 || N > EHR_JOINT_MAX_LINKS || J < 1 || J > EHR_JOINT_MAX_JOINTS || L < 1 || P < 1 || Bv < 1 ||
+        (long long)P * Bv * L > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID,
+                    "ehr_joint_forward_multi: bad sizes (N %d <= 64 links, J %d <= 32 joints, L %d, P %d, Bv %d)", N, J, L, P, Bv);
+    joint_forward_multi_kernel<<<(unsigned)(P * Bv), 64, 0, (hipStream_t)stream>>>(parent, origin, kind, axis, qidx, use, N, J, L,
+                                                                                 qpos, offset, Bv, link_poses, joint_frames);
     EHR_LAUNCH_CHECK();
     return EHR_OK;
 }

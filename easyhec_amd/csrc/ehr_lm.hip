@@ -15,6 +15,9 @@
 //                  virtual view p * Bv + j takes dof[p] and link_poses[j]; one workgroup per hypothesis updates its own state
 //                  block.  Both call the device functions the solo kernels call, so hypothesis p has its solo solve's bits.
 //
+//   lm_linearize_multi_calib, lm_update_multi_calib<PRIOR> : P hypotheses that each own dof, offsets, theta, K, link poses, joint
+//                  frames and prior rows (section 6q): any layout of free joints and intrinsics, the same device functions again.
+//
 //   lm_update_rig : the update for C cameras that share the joint offsets (easyhec_amd/lm_rig.py, section 6o): ONE system of
 //                  6 C + F parameters summed from the cameras' own (6 + F) matrices; its own gathering head, then the steps
 //                  every update shares (lm_update_rest) over the rig's parameter accessor.
@@ -229,6 +232,24 @@ __global__ void __launch_bounds__(256) lm_linearize_multi_kernel(const float* __
     const int p = b / Bv, j = b - p * Bv;
     lm_linearize_matrix(dof + 6 * (size_t)p, K, link_poses + ((size_t)j * L + l) * 16, k, j, l, H, W, n, f, nullptr, nullptr,
                         nullptr, nullptr, 0, 0, 0, 0, k < 0 ? mvp + (size_t)i * 16 : dmvp + ((size_t)k * BL + i) * 16);
+}
+
+// P hypotheses with everything of their own (section 6q): virtual view b = p * Bv + j takes dof[p], K[p], ITS link pose and ITS
+// joint-frame rows (ehr_joint_forward_multi's layout); any layout of free joints and intrinsics.
+__global__ void __launch_bounds__(256) lm_linearize_multi_calib_kernel(
+    const float* __restrict__ dof, const float* __restrict__ K, const float* __restrict__ link_poses, int P, int Bv, int L, int H,
+    int W, float n, float f, const float* __restrict__ joint_frames, const unsigned* __restrict__ upstream,
+    const int* __restrict__ joint_kind, const int* __restrict__ free_list, int F, int J, int free4_mask, int tie_focal, int N,
+    float* __restrict__ mvp, float* __restrict__ dmvp) {
+    const int BL = P * Bv * L;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)(N + 1) * BL) return;
+    const int k = (int)(idx / BL) - 1, i = (int)(idx % BL);
+    const int b = i / L, l = i - b * L;
+    const int p = b / Bv;
+    lm_linearize_matrix(dof + 6 * (size_t)p, K + 9 * (size_t)p, link_poses + (size_t)i * 16, k, b, l, H, W, n, f, joint_frames,
+                        upstream, joint_kind, free_list, F, J, free4_mask, tie_focal,
+                        k < 0 ? mvp + (size_t)i * 16 : dmvp + ((size_t)k * BL + i) * 16);
 }
 
 // ---- the update ---------------------------------------------------------------------------------------------------------------
@@ -639,6 +660,45 @@ __global__ void __launch_bounds__(64) lm_update_multi_kernel(const double* __res
     lm_update_rest<false>(sh, bad, N, p, ftol, lambda_max, st, log, log_rows, nullptr, nullptr, nullptr);  // (pose only: no prior)
 }
 
+// P hypotheses that each own a full parameter set (section 6q), one workgroup each: `all` holds the [P,...] arrays' bases, and
+// workgroup h builds its LmParams on the slices dof + 6 h, offset + J h, theta + 4 h, K + 9 h (K0 and free_list are shared),
+// its state block, its log rows and, under a prior, rows h of prior_weight / prior_mean [P,N].  Then the solo kernel's pieces.
+template <bool PRIOR>
+__global__ void __launch_bounds__(64) lm_update_multi_calib_kernel(const double* __restrict__ info, const double* __restrict__ grad,
+                                                                   const long long* __restrict__ count,
+                                                                   const float* __restrict__ loss, int Bv, int N, LmParams all,
+                                                                   double ftol, double lambda_max, int finalize,
+                                                                   double* __restrict__ st, double* __restrict__ log,
+                                                                   int log_rows, LmPriorArgs<PRIOR> prior) {
+    __shared__ LmShared sh;
+    LmPriorShared* ps = nullptr;
+    if constexpr (PRIOR) {
+        __shared__ LmPriorShared prior_s;
+        ps = &prior_s;
+    }
+    const size_t h = blockIdx.x, v = h * (size_t)Bv;
+    const LmParams p = {all.dof + 6 * h,
+                        all.offset ? all.offset + (size_t)all.J * h : nullptr,
+                        all.free_list,
+                        all.F,
+                        all.J,
+                        all.theta ? all.theta + 4 * h : nullptr,
+                        all.free4_mask,
+                        all.tie_focal,
+                        all.K0,
+                        all.K ? all.K + 9 * h : nullptr,
+                        all.H,
+                        all.W};
+    st += h * EHR_LM_STATE_DOUBLES;
+    log = log ? log + h * (size_t)log_rows * 4 : nullptr;
+    if (lm_update_restore(N, p, finalize, st)) return;
+    const int bad = lm_update_gather(info + v * N * N, grad + v * N, count + v, loss + v, Bv, N, sh);
+    const double* pw = lm_prior_weight(prior);
+    const double* pm = lm_prior_mean(prior);
+    lm_update_rest<PRIOR>(sh, bad, N, p, ftol, lambda_max, st, log, log_rows, ps, pw ? pw + h * (size_t)N : nullptr,
+                          pm ? pm + h * (size_t)N : nullptr);
+}
+
 // ---- the rig: C cameras, one system of N = 6 C + F parameters (easyhec_amd/lm_rig.py) -------------------
 #define EHR_LM_RIG_MAX_CAMERAS (EHR_LM_MAX_PARAMS / 6)
 
@@ -851,6 +911,70 @@ int ehr_lm_update_multi(const double* info, const double* grad, const long long*
     lm_update_multi_kernel<<<(unsigned)P, 64, 0, (hipStream_t)stream>>>(info, grad, count, loss, Bv, N, dof, ftol, lambda_max,
                                                                        finalize, state, log && log_rows > 0 ? log : nullptr,
                                                                        log_rows);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+// free intrinsics of a mask (tied focal: one parameter for both), or -1 for a mask / tying that is not one
+static int lm_free_intrinsics(int free4_mask, int tie_focal) {
+    if (free4_mask < 0 || free4_mask > 15 || (tie_focal != 0 && (free4_mask & 3) != 3)) return -1;
+    int Fi = 0;
+    for (int i = 0; i < 4; i++) Fi += (free4_mask >> i) & 1;
+    return tie_focal != 0 ? Fi - 1 : Fi;
+}
+
+int ehr_lm_linearize_multi_calib(const float* dof, const float* K, const float* link_poses, int P, int Bv, int L, int H, int W,
+                                 float near_plane, float far_plane, const float* joint_frames, const uint32_t* upstream,
+                                 const int32_t* joint_kind, const int32_t* free_list, int F, int J, int free4_mask,
+                                 int tie_focal, int N, float* mvp, float* dmvp, void* stream) {
+    const char* who = "ehr_lm_linearize_multi_calib";
+    if (!dof || !K || !link_poses || !mvp || !dmvp) return fail(EHR_ERR_INVALID, "%s: NULL tensor", who);
+    if (F < 0 || (F > 0 && (!joint_frames || !upstream || !joint_kind || !free_list || J < 1 || J > 32)))
+        return fail(EHR_ERR_INVALID, "%s: free joints need joint_frames, upstream, joint_kind and the list (J %d <= 32)", who, J);
+    const int Fi = lm_free_intrinsics(free4_mask, tie_focal);
+    if (Fi < 0) return fail(EHR_ERR_INVALID, "%s: bad free intrinsics (mask %d, tie_focal %d)", who, free4_mask, tie_focal);
+    if (N != 6 + F + Fi || N > EHR_LM_MAX_PARAMS)
+        return fail(EHR_ERR_INVALID, "%s: N %d is not 6 + %d free joints + %d free intrinsics, or exceeds %d", who, N, F, Fi,
+                    EHR_LM_MAX_PARAMS);
+    if (P < 1 || Bv < 1 || L < 1 || H < 1 || W < 1 || (long long)P * Bv * L * (N + 1) > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID, "%s: bad sizes (P %d, Bv %d, L %d, H %d, W %d)", who, P, Bv, L, H, W);
+    const long long total = (long long)P * Bv * L * (N + 1);
+    lm_linearize_multi_calib_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+        dof, K, link_poses, P, Bv, L, H, W, near_plane, far_plane, joint_frames, upstream, joint_kind, free_list, F, J,
+        free4_mask, tie_focal, N, mvp, dmvp);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_lm_update_multi_calib(const double* info, const double* grad, const long long* count, const float* loss, int P, int Bv,
+                              int N, float* dof, float* offset, const int32_t* free_list, int F, int J, float* theta,
+                              int free4_mask, int tie_focal, const float* K0, float* K, int H, int W, double ftol,
+                              double lambda_max, int finalize, double* state, double* log, int log_rows,
+                              const double* prior_weight, const double* prior_mean, void* stream) {
+    const char* who = "ehr_lm_update_multi_calib";
+    if (!info || !grad || !count || !loss || !dof || !state) return fail(EHR_ERR_INVALID, "%s: NULL tensor", who);
+    if (F < 0 || (F > 0 && (!offset || !free_list || J < 1 || J > 32)))
+        return fail(EHR_ERR_INVALID, "%s: free joints need offset and the list (J %d <= 32)", who, J);
+    const int Fi = lm_free_intrinsics(free4_mask, tie_focal);
+    if (Fi < 0 || (free4_mask != 0 && (!theta || !K0 || !K || H < 1 || W < 1)))
+        return fail(EHR_ERR_INVALID, "%s: bad free intrinsics (mask %d, tie_focal %d), or no theta / K0 / K", who, free4_mask,
+                    tie_focal);
+    // (N < 6 without free joints or intrinsics: the first N pose coordinates alone, as for ehr_lm_update)
+    if ((N != 6 + F + Fi && !(F == 0 && Fi == 0 && N >= 1 && N < 6)) || N > EHR_LM_MAX_PARAMS)
+        return fail(EHR_ERR_INVALID, "%s: N %d is not 6 + %d free joints + %d free intrinsics, or exceeds %d", who, N, F, Fi,
+                    EHR_LM_MAX_PARAMS);
+    if (P < 1 || Bv < 1 || (long long)P * Bv > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID, "%s: bad sizes (P %d, Bv %d)", who, P, Bv);
+    if (int rc = lm_prior_check(who, prior_weight, prior_mean)) return rc;
+    LmParams all = {dof, offset, free_list, F, J, theta, free4_mask, tie_focal, K0, K, H, W};
+    double* const lg = log && log_rows > 0 ? log : nullptr;
+    if (prior_weight)
+        lm_update_multi_calib_kernel<true><<<(unsigned)P, 64, 0, (hipStream_t)stream>>>(
+            info, grad, count, loss, Bv, N, all, ftol, lambda_max, finalize, state, lg, log_rows,
+            LmPriorArgs<true>{prior_weight, prior_mean});
+    else
+        lm_update_multi_calib_kernel<false><<<(unsigned)P, 64, 0, (hipStream_t)stream>>>(
+            info, grad, count, loss, Bv, N, all, ftol, lambda_max, finalize, state, lg, log_rows, LmPriorArgs<false>{});
     EHR_LAUNCH_CHECK();
     return EHR_OK;
 }

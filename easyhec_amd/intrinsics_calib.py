@@ -25,7 +25,8 @@ reported step (NaN loss) ``theta``, its Adam state and ``K`` stay untouched like
 again and recovers as it always does.  :class:`JointIntrinsicsPoseStep` composes this with the joint-offset solve.
 
 Out of scope: the camera rig (per-camera intrinsics inside ``ehr_rig_backward_adam``'s all-or-nothing step), data-parallel
-and multi-start solves, lens distortion, skew, per-view intrinsics, and the autograd (``use_fused=True``) path."""
+solves and the ADAM multi-start step (the multi-start Levenberg-Marquardt solve fits a ``K`` per hypothesis:
+:mod:`easyhec_amd.lm_multi`), lens distortion, skew, per-view intrinsics, and the autograd (``use_fused=True``) path."""
 from dataclasses import dataclass, field
 
 import numpy as np

@@ -14,7 +14,8 @@ not change (csrc/ehr_joint.hip, include/ehr.h):
 Stepping, graph capture, the look at the loss every 16 steps and the recovery from a reported step are ``_ChainStep``'s: on a
 reported step (NaN loss) the offsets and their Adam state stay untouched like the pose's, the next forward launch writes the
 same ``link_poses`` again, and the chain recovers as it always does.  Not available for a data-parallel job (the offset
-gradient would need an exchange of its own) nor for the multi-start step (its hypotheses share one ``link_poses``)."""
+gradient would need an exchange of its own) nor for the Adam multi-start step (``MultiStartPoseStep``: its hypotheses share
+one ``link_poses``; the multi-start Levenberg-Marquardt solve, :mod:`easyhec_amd.lm_multi`, gives every hypothesis its own)."""
 import ctypes
 from dataclasses import dataclass, field
 
@@ -59,6 +60,49 @@ def _check_table(t, J):
     for k in ("origin", "kind", "axis", "qidx"):
         if np.asarray(t[k]).shape[0] != N:
             raise ValueError(f"joint offsets: table entry {k!r} has the wrong length")
+
+
+def arm_table(robot, qpos, batch, who):
+    """What every solve with free joints reads of the arm (``who``: its name in the messages): ``robot.joint_table()`` checked,
+    the articulation's dof J, and the recorded joint vectors (``qpos``, default ``batch["qpos"]``) as [B,J] float64,
+    zero-padded to J like the dataset does -> ``(table, J, qp)``."""
+    if qpos is None:
+        if "qpos" not in batch:
+            raise ValueError(f"{who} needs the recorded joint vectors: pass qpos= or batch['qpos']")
+        qpos = batch["qpos"]
+    table = robot.joint_table()
+    J = int(robot.chain.dof)
+    _check_table(table, J)
+    q = np.asarray(qpos.detach().cpu() if torch.is_tensor(qpos) else qpos, dtype=np.float64)
+    q = np.atleast_2d(q)
+    qp = np.zeros((q.shape[0], J))
+    qp[:, :min(J, q.shape[1])] = q[:, :J]
+    return table, J, qp
+
+
+def with_recorded_link_poses(robot, qp, batch, who):
+    """A copy of ``batch`` whose ``link_poses`` are the forward kinematics of the recorded ``qp``.  batch["link_poses"] is
+    optional for a solve with free joints and never rendered from: the forward kernel writes the solve's own buffer from qpos +
+    offsets.  One that is given must be the kinematics of the recorded qpos (what the dataset computes) -- a batch whose link
+    poses and joint vectors belong to different frames is refused, not silently overruled."""
+    batch = dict(batch)
+    fk0 = robot.link_poses_batch(qp)
+    if "link_poses" in batch:
+        given = batch["link_poses"].detach().cpu().double().numpy()
+        if given.shape != fk0.shape or np.abs(given - fk0).max() > 1e-5:
+            raise ValueError(f"{who}: batch['link_poses'] is not the forward kinematics of qpos (to 1e-5): the "
+                             "joint vectors and the link poses must describe the same views")
+    else:
+        batch["link_poses"] = torch.from_numpy(fk0).float()
+    return batch
+
+
+def free_joint_list(table, J, free):
+    """The free joints of a solve, sorted: ``free`` (default :func:`default_free_joints`), every one an active joint."""
+    free = default_free_joints(table) if free is None else [int(j) for j in free]
+    if any(j < 0 or j >= J for j in free):
+        raise ValueError(f"free joints {free}: active joints are 0..{J - 1}")
+    return sorted(set(free))
 
 
 class _JointForward:
@@ -152,39 +196,15 @@ class JointPoseStep(FusedPoseStep):
     def _init_joint(self, model, batch, robot, qpos, free, offsets, finish, kw):
         """offsets: the offsets' group -- this step's own, or the one a rig's cameras share; finish: whether the
         step finishes with ``ehr_joint_backward_adam`` (a rig's camera does not: the rig's one finish launch follows)."""
-        if qpos is None:
-            if "qpos" not in batch:
-                raise ValueError("JointPoseStep needs the recorded joint vectors: pass qpos= or batch['qpos']")
-            qpos = batch["qpos"]
-        table = robot.joint_table()
-        J = int(robot.chain.dof)
-        _check_table(table, J)
-        q = np.asarray(qpos.detach().cpu() if torch.is_tensor(qpos) else qpos, dtype=np.float64)
-        q = np.atleast_2d(q)
-        qp = np.zeros((q.shape[0], J))
-        qp[:, :min(J, q.shape[1])] = q[:, :J]
-        batch = dict(batch)
-        # batch["link_poses"] is optional here and never rendered from: the forward kernel writes this object's own buffer
-        # from qpos + offsets.  One that is given must be the kinematics of the recorded qpos (what the dataset computes) --
-        # a batch whose link poses and joint vectors belong to different frames is refused, not silently overruled.
-        fk0 = robot.link_poses_batch(qp)
-        if "link_poses" in batch:
-            given = batch["link_poses"].detach().cpu().double().numpy()
-            if given.shape != fk0.shape or np.abs(given - fk0).max() > 1e-5:
-                raise ValueError("JointPoseStep: batch['link_poses'] is not the forward kinematics of qpos (to 1e-5): the "
-                                 "joint vectors and the link poses must describe the same views")
-        else:
-            batch["link_poses"] = torch.from_numpy(fk0).float()
+        table, J, qp = arm_table(robot, qpos, batch, "JointPoseStep")
+        batch = with_recorded_link_poses(robot, qp, batch, "JointPoseStep")
         FusedPoseStep.__init__(self, model, batch, **kw)
         dev = self.dev
         if qp.shape[0] != self.B or len(table["use"]) != self.L:
             raise ValueError(f"JointPoseStep: qpos {qp.shape} / {len(table['use'])} rendered links do not match the batch's "
                              f"{self.B} views of {self.L} links")
         self.robot, self.table, self.J = robot, table, J
-        free = default_free_joints(table) if free is None else [int(j) for j in free]
-        if any(j < 0 or j >= J for j in free):
-            raise ValueError(f"free joints {free}: active joints are 0..{J - 1}")
-        self.free_joints = sorted(set(free))
+        self.free_joints = free_joint_list(table, J, free)
         self.offsets_group = g = offsets
         self.offset_lr, self.offset_wd = g.lr, g.wd
         self.offsets, self.offset_grad = g.param, g.grad

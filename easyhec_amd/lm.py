@@ -245,6 +245,8 @@ class _LmDriver:
             return None
         s = self.states()[p] if state is None else state
         w, mu = self.prior.weight.cpu().numpy(), self.prior.mean.cpu().numpy()
+        if w.ndim == 2:  # (a P-block driver's prior: one row per hypothesis)
+            w, mu = w[p], mu[p]
         gp = np.where(w != 0, 2.0 * w * (s.theta - np.where(w != 0, mu, 0.0)), 0.0)
         rep = information.InformationReport(np.stack([s.H, np.diag(w)]), self.names, np.stack([s.g, gp]), [s.count], [s.F_acc])
         sigma2 = self.prior.sigma2
@@ -338,6 +340,7 @@ class LmPrior:
     mean_k)^2`` with ``weight_k = sigma2 / sigma_k^2`` (0 where there is no prior on parameter k)."""
     weight: torch.Tensor        # [N] float64, device: p_k, in loss units per squared parameter unit
     mean: torch.Tensor          # [N] float64, device: mu_k
+    # (for the P hypotheses of a MultiStartLM both are [P,N]: every row of ``weight`` the same, ``mean`` a row per hypothesis)
     sigma: np.ndarray           # [N] float64: one standard deviation per parameter, inf where there is none
     sigma2: float               # the residual variance that puts prior and data in the same units; fixed for the solve
     names: list
@@ -350,6 +353,8 @@ def _prior_kinds(names, joint_kind):
 
 
 def _no_prior_arguments(who, prior_sigma, sigma2, prior_mean, allowed=False):
+    """``allowed``: the solve takes a prior (then ``sigma2`` / ``prior_mean`` need ``prior_sigma``); otherwise it is the multi-start
+    solve in its pose-only form, which refuses all three."""
     if allowed:
         if prior_sigma is None and (sigma2 is not None or prior_mean is not None):
             raise ValueError(f"{who}: sigma2 and prior_mean belong to a prior: pass prior_sigma as well")
@@ -361,7 +366,8 @@ def _no_prior_arguments(who, prior_sigma, sigma2, prior_mean, allowed=False):
 
 def make_prior(driver_or_step, prior_sigma, sigma2=None, prior_mean=None):
     """The :class:`LmPrior` of a solve.  ``driver_or_step``: a :class:`LevenbergMarquardt` or
-    :class:`easyhec_amd.lm_rig.RigLM`, or the step object one would drive (a driver is then made for the call).
+    :class:`easyhec_amd.lm_rig.RigLM`, or the step object one would drive (a driver is then made for the call), or a
+    :class:`easyhec_amd.lm_multi.MultiStartLM` with free offsets or intrinsics (below).
 
     ``prior_sigma``: ``"default"`` -- ``info_explorer.PRIOR_SIGMA`` by kind for the offsets and the intrinsics, NO prior on a
     pose coordinate; a dict by parameter name or by kind (what it does not mention gets none); a number (every parameter); or
@@ -371,6 +377,12 @@ def make_prior(driver_or_step, prior_sigma, sigma2=None, prior_mean=None):
     parameters (the explorer's formula, ``InformationReport.sigma2``'s): one synchronising read; it then stays fixed for the
     solve and is recorded in the result.  That default is meant for a polish from near the optimum: far from it the loss is
     large, so it OVERWEIGHTS the prior -- pass a value there.
+
+    For the P hypotheses of a ``MultiStartLM``: ``mean`` is [P,N] -- a pose coordinate's default is ITS hypothesis's value now,
+    what ``prior_mean`` names holds for every hypothesis -- and ``weight`` [P,N] has every row equal:
+    ONE ``sigma2`` for all hypotheses, or their objectives could not be ranked against each other.  With ``sigma2=None`` it is
+    the MINIMUM over the hypotheses of ``loss_p / max(count_p - N, 1)`` from one evaluation of all of them: a far start's loss
+    overweights the prior (above), and the best start's residual variance is the least overweighting one available.
 
     ValueError, with the reason: a sigma <= 0 or NaN, a mean that is not finite under a finite sigma, a wrong length, unknown
     names, ``sigma2 <= 0``."""
@@ -383,7 +395,9 @@ def make_prior(driver_or_step, prior_sigma, sigma2=None, prior_mean=None):
             drv = RigLM(drv)
         else:
             drv = LevenbergMarquardt(drv)
-    if drv.P != 1 or not hasattr(drv, "parameters"):
+    # hypothesis_priors: True for a P-block driver whose update takes [P,N] prior rows, False for one in its pose-only form
+    blocks = getattr(drv, "hypothesis_priors", None)
+    if blocks is False or (drv.P != 1 and not blocks) or not hasattr(drv, "parameters"):
         raise ValueError("make_prior: no prior is available for the multi-start solve (pose-only)")
     names, N = list(drv.names), drv.N
     kinds = _prior_kinds(names, drv.joint_kinds())
@@ -408,25 +422,31 @@ def make_prior(driver_or_step, prior_sigma, sigma2=None, prior_mean=None):
         raise ValueError(f"make_prior: every sigma is > 0 (inf or None: no prior), got {dict(zip(names, sig.tolist()))}")
     has = np.isfinite(sig)
     # mean
-    now = drv.parameters().astype(np.float64)
+    now = drv.parameters().astype(np.float64)  # [N], or [P,N] for the blocks: everything below works on the last axis
     mean = np.where([kd in ("translation", "rotation") for kd in kinds], now, 0.0)
     if isinstance(prior_mean, dict):
         unknown = [k for k in prior_mean if k not in names]
         if unknown:
             raise ValueError(f"make_prior: prior_mean {unknown}: keys are parameter names {names}")
         for k, v in prior_mean.items():
-            mean[names.index(k)] = float(v)
+            mean[..., names.index(k)] = float(v)
     elif prior_mean is not None:
         if np.ndim(prior_mean) != 1 or len(prior_mean) != N:
             raise ValueError(f"make_prior: prior_mean is None, a dict by name or a sequence of N = {N} ({names})")
-        mean = np.array([float(x) for x in prior_mean], dtype=np.float64)
-    if not np.isfinite(mean[has]).all():
-        raise ValueError(f"make_prior: the mean under a finite sigma is finite, got {dict(zip(names, mean.tolist()))}")
+        mean = np.broadcast_to(np.array([float(x) for x in prior_mean], dtype=np.float64), now.shape).copy()
+    if not np.isfinite(mean[..., has]).all():
+        raise ValueError(f"make_prior: the mean under a finite sigma is finite, got {dict(zip(names, mean.T.tolist()))}")
     mean = np.where(has, mean, 0.0)
     # sigma2
     if sigma2 is None:
-        loss, count = drv.evaluate()
-        sigma2 = loss / max(count - N, 1)
+        if blocks:
+            pairs = drv.evaluate_each()
+            loss, count = [ls for ls, _ in pairs], [ct for _, ct in pairs]
+            each = [ls / max(ct - N, 1) for ls, ct in pairs]
+            sigma2 = min(each) if np.isfinite(each).all() else float("nan")
+        else:
+            loss, count = drv.evaluate()
+            sigma2 = loss / max(count - N, 1)
         if not (np.isfinite(sigma2) and sigma2 > 0):
             raise ValueError(f"make_prior: the evaluation at the current parameters gives sigma2 = {sigma2} (loss {loss}, count "
                              f"{count}): pass sigma2")
@@ -435,6 +455,7 @@ def make_prior(driver_or_step, prior_sigma, sigma2=None, prior_mean=None):
     weight = np.where(has, float(sigma2) / np.where(has, sig, 1.0) ** 2, 0.0)
     if not np.isfinite(weight).all():
         raise ValueError(f"make_prior: sigma2 / sigma^2 overflows: {dict(zip(names, weight.tolist()))}")
+    weight = np.broadcast_to(weight, now.shape).copy()  # (the blocks: every row the same)
     return LmPrior(torch.from_numpy(weight).to(drv.dev), torch.from_numpy(mean).to(drv.dev), sig, float(sigma2), names)
 
 

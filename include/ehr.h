@@ -466,7 +466,7 @@ int ehr_mask_cost(ehr_ctx* ctx, const float* verts, const int32_t* tris, const i
  *                       writes identical link_poses, so the chain's own recovery (the same history row again, the
  *                       general-triangle pass, a new plan) works unchanged.  A single workgroup.
  * Out of scope: a data-parallel job (the offset gradient would need an exchange of its own) and ehr_solver_step_multi (the
- * hypotheses share ONE link_poses).  ehr_version() is unchanged: the presence of these symbols is the capability check. */
+ * hypotheses share ONE link_poses; the multi-start Levenberg-Marquardt solve has ehr_joint_forward_multi, below).  ehr_version() is unchanged: the presence of these symbols is the capability check. */
 int ehr_joint_forward(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
                       const int32_t* qidx, const int32_t* use, int N, int J, int L, const double* qpos, const float* offset,
                       int B, float* link_poses, float* joint_frames, void* stream);
@@ -637,7 +637,7 @@ int ehr_lm_update(const double* info, const double* grad, const long long* count
  *   d. Steps 4-6 run on that system: the scaling is the posterior diagonal's, and a parameter WITHOUT data information but
  *      with p_k > 0 is no longer left out -- the prior alone pulls it towards mu_k (intended).  pred, ftol * F_acc,
  *      lambda_max and the float32-spacing rule are unchanged; restore, finalize and done likewise.
- * ehr_lm_update_multi has no such form (pose only).  Out of scope: full prior covariances, N > EHR_LM_MAX_PARAMS.
+ * ehr_lm_update_multi has no such form (pose only; ehr_lm_update_multi_calib below takes [P,N] rows).  Out of scope: full prior covariances, N > EHR_LM_MAX_PARAMS.
  * ehr_version() is unchanged: the presence of these symbols is the capability check. */
 int ehr_lm_update_prior(const double* info, const double* grad, const long long* count, const float* loss, int B, int N,
                         float* dof, float* offset, const int32_t* free_list, int F, int J, float* theta, int free4_mask,
@@ -663,14 +663,54 @@ int ehr_lm_update_prior(const double* info, const double* grad, const long long*
  *                            finalize != 0 restores all P accepted poses and changes nothing else.  The caller prepares every
  *                            state block as for ehr_lm_update.
  * Both refuse (EHR_ERR_INVALID) NULL tensors, P < 1, Bv < 1 and sizes whose matrix count overflows 32 bits; the update also N
- * outside 1..6.  Out of scope: free joints or intrinsics per hypothesis, a shared-reference form of ehr_mask_information (the
- * caller tiles the reference), retiring finished hypotheses from the render.
+ * outside 1..6.  Free joints or intrinsics per hypothesis: the _multi_calib entries below.  Out of scope: a shared-reference
+ * form of ehr_mask_information (the caller tiles the reference), retiring finished hypotheses from the render.
  * ehr_version() is unchanged: the presence of these symbols is the capability check. */
 int ehr_lm_linearize_multi(const float* dof, const float* K, const float* link_poses, int P, int Bv, int L, int H, int W,
                            float near_plane, float far_plane, float* mvp, float* dmvp, void* stream);
 int ehr_lm_update_multi(const double* info, const double* grad, const long long* count, const float* loss, int P, int Bv, int N,
                         float* dof, double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
                         void* stream);
+
+/* Multi-start Levenberg-Marquardt with joint offsets, intrinsics and priors per hypothesis: P hypotheses
+ * of ONE problem that each own a FULL parameter set, so that an iteration of all of them is
+ *     [ehr_joint_forward_multi, if joints are free] -> ehr_lm_linearize_multi_calib -> ehr_mask_information (P*Bv views)
+ *                                                   -> ehr_lm_update_multi_calib                                on one stream.
+ * Everything that can differ between hypotheses is a per-hypothesis array -- dof [P,6], offset [P,J], theta [P,4], K [P,9],
+ * link_poses [P*Bv,L,16], joint_frames [P*Bv,J,6], prior_weight / prior_mean [P,N] -- one layout, no "shared or not" flags; the
+ * joint table, free_list and K0 describe the problem and are shared.  The parameters' order, F, J, free4_mask, tie_focal and N
+ * are ehr_lm_linearize's.  Device pointers only; no call allocates, synchronises or uses an atomic.  The contract: hypothesis p
+ * is, bit for bit, its solo solve -- every kernel calls the device functions of its solo kernel.
+ *   ehr_joint_forward_multi      : a grid of P*Bv workgroups of one wave; virtual view b = p * Bv + j walks qpos[j] + offset[p]
+ *                                  (qpos [Bv,J] float64, offset [P,J] float32).  Block p of link_poses / joint_frames holds the
+ *                                  bytes ehr_joint_forward(..., qpos, offset + p J, B = Bv) writes.
+ *   ehr_lm_linearize_multi_calib : one thread per (k, b, l) matrix, k in [-1, N); view b of hypothesis p = b / Bv takes dof + 6 p,
+ *                                  K + 9 p, link_poses[b] and joint_frames[b] (NULL where F == 0).  mvp [P*Bv,L,16], dmvp
+ *                                  [N,P*Bv,L,16]; views [p Bv, (p+1) Bv) of both hold the bits ehr_lm_linearize writes for
+ *                                  hypothesis p's rows with B = Bv.
+ *   ehr_lm_update_multi_calib    : a grid of P workgroups of one wave.  Workgroup p runs ehr_lm_update -- or, with prior_weight
+ *                                  and prior_mean given, ehr_lm_update_prior on rows p of them -- on its own slices: views
+ *                                  [p Bv, (p+1) Bv), dof + 6 p, offset + J p, theta + 4 p, K + 9 p (offset / theta, K0, K: NULL
+ *                                  where F == 0 / free4_mask == 0), state + p * EHR_LM_STATE_DOUBLES, log + p * log_rows * 4.
+ *                                  Reported, done and finalize apply to ONE hypothesis, as for ehr_lm_update_multi; with F == 0
+ *                                  and free4_mask == 0 and no prior it writes ehr_lm_update_multi's bytes.
+ * All refuse (EHR_ERR_INVALID) NULL tensors, P < 1, Bv < 1, an N that is not 6 + F + the free intrinsics (the update also takes
+ * N in 1..5 where nothing but the pose is free), N > EHR_LM_MAX_PARAMS and sizes whose matrix count overflows 32 bits; the update
+ * refuses prior_weight and prior_mean given singly.  Out of scope: rigs, retiring finished hypotheses from the render, a
+ * shared-reference form of ehr_mask_information.
+ * ehr_version() is unchanged: the presence of these symbols is the capability check. */
+int ehr_joint_forward_multi(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                            const int32_t* qidx, const int32_t* use, int N, int J, int L, const double* qpos,
+                            const float* offset, int P, int Bv, float* link_poses, float* joint_frames, void* stream);
+int ehr_lm_linearize_multi_calib(const float* dof, const float* K, const float* link_poses, int P, int Bv, int L, int H, int W,
+                                 float near_plane, float far_plane, const float* joint_frames, const uint32_t* upstream,
+                                 const int32_t* joint_kind, const int32_t* free_list, int F, int J, int free4_mask,
+                                 int tie_focal, int N, float* mvp, float* dmvp, void* stream);
+int ehr_lm_update_multi_calib(const double* info, const double* grad, const long long* count, const float* loss, int P, int Bv,
+                              int N, float* dof, float* offset, const int32_t* free_list, int F, int J, float* theta,
+                              int free4_mask, int tie_focal, const float* K0, float* K, int H, int W, double ftol,
+                              double lambda_max, int finalize, double* state, double* log, int log_rows,
+                              const double* prior_weight, const double* prior_mean, void* stream);
 
 /* Levenberg-Marquardt over a camera rig: C fixed cameras watch one arm and share its joint offsets (ehr_rig_backward_adam's
  * setting), solved as ONE system of N = 6 C + F <= EHR_LM_MAX_PARAMS parameters in the order of
