@@ -104,6 +104,8 @@ SIGNATURES = {
                           [c_void_p] * 2 + [c_int, c_void_p]),
     "ehr_lm_update_rig_prior": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
                                 [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
+    "ehr_lm_update_rig_arrow": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [ctypes.c_double] * 2 + [c_int] +
+                                [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
     "ehr_information_gain": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_double, ctypes.c_uint32, c_void_p, c_void_p]),
     "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
 }
@@ -186,6 +188,10 @@ def has_lm_rig():
     return has_symbols("ehr_lm_update_rig")
 
 
+def has_lm_rig_arrow():
+    return has_symbols("ehr_lm_update_rig_arrow")
+
+
 def has_lm_prior():
     return has_symbols("ehr_lm_update_prior", "ehr_lm_update_rig_prior")
 
@@ -203,6 +209,15 @@ LM_STATE = {"lambda": 0, "nu": 1, "F_acc": 2, "pred": 3, "rho": 4, "F_trial": 5,
 LM_THETA, LM_DELTA, LM_G, LM_H, LM_STATE_DOUBLES, LM_MAX_PARAMS = 16, 48, 80, 112, 1136, 32
 
 
+# the state block of ehr_lm_update_rig_arrow (include/ehr.h: EHR_LM_ARROW_*): words 0..15 as LM_STATE, then theta, delta, g with
+# a capacity of LM_ARROW_MAX_PARAMS, then H_acc packed: per camera a panel [10][36] and the border's other half [26][10], then
+# the corner [26][26]
+LM_ARROW_MAX_CAMERAS, LM_ARROW_MAX_BLOCK, LM_ARROW_MAX_SHARED, LM_ARROW_MAX_PARAMS = 16, 10, 26, 192
+LM_ARROW_THETA, LM_ARROW_DELTA, LM_ARROW_G, LM_ARROW_H = 16, 208, 400, 592
+LM_ARROW_PANEL_STRIDE, LM_ARROW_BORDER_T, LM_ARROW_CAMERA_STRIDE = 36, 360, 620
+LM_ARROW_CORNER, LM_ARROW_STATE_DOUBLES = 10512, 11188
+
+
 class RigCamera(ctypes.Structure):
     """``ehr_rig_camera`` of include/ehr.h, field for field."""
     _fields_ = [(k, c_void_p) for k in ("grad_mvp", "tc_jac", "K", "link_poses", "joint_frames", "red", "dof", "adam_m",
@@ -213,6 +228,12 @@ class RigCamera(ctypes.Structure):
 class LmRigCamera(ctypes.Structure):
     """``ehr_lm_rig_camera`` of include/ehr.h, field for field."""
     _fields_ = [(k, c_void_p) for k in ("info", "grad", "count", "loss", "dof")] + [("B", c_int)]
+
+
+class LmRigArrowCamera(ctypes.Structure):
+    """``ehr_lm_rig_arrow_camera`` of include/ehr.h, field for field."""
+    _fields_ = [(k, c_void_p) for k in ("info", "grad", "count", "loss", "dof", "theta", "K0", "K")] + \
+               [(k, c_int) for k in ("B", "H", "W", "free4_mask", "tie_focal")]
 
 
 EHR_ERR_OVERFLOW = -3  # include/ehr.h

@@ -22,6 +22,11 @@
 //                  6 C + F parameters summed from the cameras' own (6 + F) matrices; its own gathering head, then the steps
 //                  every update shares (lm_update_rest) over the rig's parameter accessor.
 //
+//   lm_update_rig_arrow<PRIOR> : the rig's update on its BLOCK-ARROW system (section 6r): every camera may free its own intrinsics,
+//                  which ride in that camera's diagonal block, and N goes up to 182.  One workgroup of 256 threads eliminates
+//                  the camera blocks side by side and factors the Schur complement of the shared offsets: the dense
+//                  factorisation's arithmetic in the dense order with the structurally zero blocks skipped.
+//
 //   lm_update<true>, lm_update_rig<true> : the two under a diagonal Gaussian prior sum_k p_k (theta_k - mu_k)^2 (section 6p): its
 //                  term joins the objective the accept test sees, p_k and 2 p_k (theta_acc_k - mu_k) the system that is solved;
 //                  the stored linearisation stays the data's.  The <false> forms are compiled without any of it.
@@ -799,6 +804,494 @@ __global__ void __launch_bounds__(64) lm_update_rig_kernel(LmRigCameras cams, in
     lm_update_rest<PRIOR>(sh, bad, N, p, ftol, lambda_max, st, log, log_rows, ps, lm_prior_weight(prior), lm_prior_mean(prior));
 }
 
+// ---- the rig on its block-arrow system: per-camera intrinsics, N up to 182 (easyhec_amd/lm_rig.py) -------
+// The rig's matrix is block-arrow: one diagonal block per camera (pose + its free intrinsics, P_c <= 10), one border per camera
+// (its coupling to the F shared offsets) and one shared corner; the block between two cameras is exactly 0.0.  Eliminating the
+// camera blocks one by one IS the dense right-looking Cholesky in the system's order with the structurally zero updates left
+// out.  One workgroup of 256 threads: 16 lanes per camera factor the camera panels side by side, every sum in the dense
+// kernel's order.  Steps 2-3 and 5-6 are lm_update_rest's restated: that function is bound to the dense [32][32] LmShared and
+// to one wave, and sharing it would have changed the existing kernels' code.
+#define LM_ARROW_THREADS 256
+#define LM_ARROW_PB EHR_LM_ARROW_MAX_BLOCK
+#define LM_ARROW_FS EHR_LM_ARROW_MAX_SHARED
+#define LM_ARROW_ROWS (LM_ARROW_PB + LM_ARROW_FS)
+
+struct LmArrowCameras {  // the host's array, by value in the kernel's arguments (unused entries zeroed)
+    ehr_lm_rig_arrow_camera c[EHR_LM_ARROW_MAX_CAMERAS];
+};
+
+struct LmArrowShared {
+    // per camera: rows i < P_c its scaled damped block -> L_c; rows 10 + f the border's row of offset f -> (W_c^T)[f]
+    double T[EHR_LM_ARROW_MAX_CAMERAS][LM_ARROW_ROWS][LM_ARROW_PB];
+    double Cn[LM_ARROW_FS][LM_ARROW_FS];  // the scaled damped corner -> its Schur complement -> L_s
+    double gv[EHR_LM_ARROW_MAX_PARAMS];   // the call's g, then g_acc (+ the prior's); after the solve: delta
+    double sv[EHR_LM_ARROW_MAX_PARAMS], yv[EHR_LM_ARROW_MAX_PARAMS];
+    double rv[EHR_LM_ARROW_MAX_PARAMS];   // the right-hand side; before step 4 the prior's terms, after the solve (S H S) y
+    double dg[EHR_LM_ARROW_MAX_PARAMS];   // the diagonal of the system that is solved: H_acc's (+ the prior's weights)
+    double F, cnt, lambda, nu, Fp;
+    int accept, fail, why;
+    int base[EHR_LM_ARROW_MAX_CAMERAS + 1], P[EHR_LM_ARROW_MAX_CAMERAS];
+    ehr_lm_rig_arrow_camera cam[EHR_LM_ARROW_MAX_CAMERAS];
+};
+
+struct LmArrowParams {  // cam0.dof, cam0.theta[...], cam1.dof, ..., then the free joints' SHARED offsets; cams, base: in LDS
+    const ehr_lm_rig_arrow_camera* cams;
+    const int* base;  // [C + 1]: where camera c's block starts; base[C] = S0
+    int C;
+    float* offset;
+    const int* free_list;
+    int F, J;
+};
+// camera c's own parameters as the solo accessor sees them (dof, no joints, its intrinsics): local index i of its block
+__device__ __forceinline__ LmParams lm_arrow_camera(const LmArrowParams& p, int c) {
+    const ehr_lm_rig_arrow_camera& k = p.cams[c];
+    return LmParams{k.dof, nullptr, nullptr, 0, 0, k.theta, k.free4_mask, k.tie_focal, k.K0, k.K, k.H, k.W};
+}
+__device__ __forceinline__ int lm_arrow_owner(const LmArrowParams& p, int k) {
+    int c = 0;
+    while (c + 1 < p.C && k >= p.base[c + 1]) c++;
+    return c;
+}
+__device__ __forceinline__ float lm_param_read(const LmArrowParams& p, int k) {
+    if (k < p.base[p.C]) {
+        const int c = lm_arrow_owner(p, k);
+        return lm_param_read(lm_arrow_camera(p, c), k - p.base[c]);
+    }
+    const int j = p.free_list[k - p.base[p.C]];
+    return (j >= 0 && j < p.J) ? p.offset[j] : 0.f;
+}
+__device__ __forceinline__ void lm_param_write(const LmArrowParams& p, int k, float x) {
+    if (k < p.base[p.C]) {
+        const int c = lm_arrow_owner(p, k);
+        lm_param_write(lm_arrow_camera(p, c), k - p.base[c], x);
+    } else {
+        const int j = p.free_list[k - p.base[p.C]];
+        if (j >= 0 && j < p.J) p.offset[j] = x;
+    }
+}
+// every camera's K from its theta (9 threads per camera; a camera without free intrinsics: untouched)
+__device__ __forceinline__ void lm_write_K(const LmArrowParams& p, int tid) {
+    const int c = tid / 9;
+    if (c < p.C) lm_write_K(lm_arrow_camera(p, c), tid - 9 * c);
+}
+
+// the packed H_acc of the arrow state block: camera c's panel (block + border), its border's transpose, the corner
+__device__ __forceinline__ double* lm_arrow_panel(double* st, int c) { return st + EHR_LM_ARROW_H + c * EHR_LM_ARROW_CAMERA_STRIDE; }
+__device__ __forceinline__ double* lm_arrow_border_t(double* st, int c) { return lm_arrow_panel(st, c) + EHR_LM_ARROW_BORDER_T; }
+__device__ __forceinline__ double* lm_arrow_corner(double* st) { return st + EHR_LM_ARROW_CORNER; }
+// camera-local index of ehr_lm_linearize's order (dof, offsets, intrinsics) -> index in the camera's block, or -1 - f for offset f
+__device__ __forceinline__ int lm_arrow_local(int r, int F) { return r < 6 ? r : (r < 6 + F ? -1 - (r - 6) : r - F); }
+
+template <bool PRIOR>
+__global__ void __launch_bounds__(LM_ARROW_THREADS) lm_update_rig_arrow_kernel(LmArrowCameras cams, int C, float* __restrict__ offset,
+                                                                              const int* __restrict__ free_list, int F, int J,
+                                                                              double ftol, double lambda_max, int finalize,
+                                                                              double* st, double* __restrict__ log, int log_rows,
+                                                                              LmPriorArgs<PRIOR> prior) {
+    __shared__ LmArrowShared sh;
+    constexpr int NT = LM_ARROW_THREADS, PB = LM_ARROW_PB, ST = EHR_LM_ARROW_PANEL_STRIDE;
+    const int tid = threadIdx.x;
+    // the by-value array into LDS, every index a constant: a per-thread run-time index into it would put it in scratch
+    if (tid == 0) {
+#pragma unroll
+        for (int c = 0; c < EHR_LM_ARROW_MAX_CAMERAS; c++) sh.cam[c] = cams.c[c];
+        int b = 0;
+        for (int c = 0; c < C; c++) {
+            const int m = sh.cam[c].free4_mask;
+            const int Pc = 6 + (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1) - (sh.cam[c].tie_focal != 0 ? 1 : 0);
+            sh.base[c] = b;
+            sh.P[c] = Pc;
+            b += Pc;
+        }
+        sh.base[C] = b;
+    }
+    __syncthreads();
+    const int S0 = sh.base[C], N = S0 + F;
+    const LmArrowParams p = {sh.cam, sh.base, C, offset, free_list, F, J};
+    if (lm_update_restore(N, p, finalize, st)) return;
+    const double* const prior_weight = lm_prior_weight(prior);
+    const double* const prior_mean = lm_prior_mean(prior);
+    double* const th_acc = st + EHR_LM_ARROW_THETA;
+    double* const g_acc = st + EHR_LM_ARROW_G;
+    const bool have = st[EHR_LM_ACCEPTED] > 0.0;  // a point has been accepted
+    const int it = (int)st[EHR_LM_ITERATIONS];
+    double* const row = (log && it < log_rows) ? log + (size_t)it * 4 : nullptr;  // (thread 0's)
+    // where this thread's parameter (tid < N) lives: camera mc and index mi of its block, or mc = -1 and offset mi
+    int mc = -1, mi = tid - S0;
+    if (tid < S0) {
+        mc = lm_arrow_owner(p, tid);
+        mi = tid - sh.base[mc];
+    }
+    // 1. the head: every camera's sums in view order; g embedded with += in camera order; H is summed again where it is stored
+    if (tid < N) sh.gv[tid] = 0.0;
+    __syncthreads();
+    int bad = 0;
+    double Fsum = 0.0, nsum = 0.0;  // (thread 0's)
+    for (int c = 0; c < C; c++) {
+        const double* __restrict__ info = sh.cam[c].info;
+        const double* __restrict__ grad = sh.cam[c].grad;
+        const int B = sh.cam[c].B, Nc = sh.P[c] + F;
+        for (int e = tid; e < Nc * Nc; e += NT) {
+            double s = 0.0;
+            for (int b = 0; b < B; b++) s += info[(size_t)b * Nc * Nc + e];
+            bad |= !lm_finite(s);
+        }
+        if (tid < Nc) {  // local index tid is this thread's for every camera: an offset's C terms are added by ONE thread
+            double s = 0.0;
+            for (int b = 0; b < B; b++) s += grad[(size_t)b * Nc + tid];
+            bad |= !lm_finite(s);
+            const int l = lm_arrow_local(tid, F);
+            sh.gv[l >= 0 ? sh.base[c] + l : S0 + (-1 - l)] += s;
+        }
+        if (tid == 0) {
+            const long long* __restrict__ count = sh.cam[c].count;
+            const float* __restrict__ loss = sh.cam[c].loss;
+            double s = 0.0, n = 0.0;
+            for (int b = 0; b < B; b++) {
+                s += (double)loss[b];
+                bad |= count[b] < 0;
+                n += (double)count[b];
+            }
+            bad |= !lm_finite(s);
+            Fsum += s;
+            nsum += n;
+        }
+    }
+    if (tid == 0) {
+        bad |= !lm_finite(Fsum);
+        sh.F = Fsum;
+        sh.cnt = nsum;
+    }
+    // the prior's term at the trial: lm_update_rest's
+    if (PRIOR) {
+        if (tid < N) {
+            const double w = prior_weight[tid], m = prior_mean[tid];
+            double t = 0.0;
+            if (!(w >= 0.0) || !lm_finite(w)) {
+                bad = 1;
+            } else if (w != 0.0) {
+                bad |= !lm_finite(m);
+                const double d = (double)lm_param_read(p, tid) - m;
+                t = (w * d) * d;
+            }
+            sh.rv[tid] = t;  // (free until step 4)
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int k = 0; k < N; k++)
+                if (prior_weight[k] != 0.0) s += sh.rv[k];
+            bad |= !lm_finite(s);
+            sh.Fp = s;
+        }
+    }
+    bad = __syncthreads_or(bad);
+    // 2. a reported call: the trial is discarded, nothing else moves
+    if (bad) {
+        if (have && tid < N) lm_param_write(p, tid, (float)th_acc[tid]);
+        if (tid == 0) {
+            st[EHR_LM_REPORTED] += 1.0;
+            st[EHR_LM_ITERATIONS] = (double)(it + 1);
+            st[EHR_LM_LAST] = -1.0;
+            if (row) {
+                row[0] = __longlong_as_double(0x7ff8000000000000ll);
+                row[1] = -1.0;
+                row[2] = st[EHR_LM_LAMBDA];
+                row[3] = __longlong_as_double(0x7ff8000000000000ll);
+            }
+        }
+        __syncthreads();
+        if (have) lm_write_K(p, tid);
+        return;
+    }
+    // 3. accept or reject
+    if (tid == 0) {
+        const double Fv = PRIOR ? sh.F + sh.Fp : sh.F, F_acc = st[EHR_LM_F];
+        double lambda = st[EHR_LM_LAMBDA], nu = st[EHR_LM_NU], rho = 0.0;
+        const int accept = !have || Fv < F_acc;
+        if (accept) {
+            if (have) {
+                rho = (F_acc - Fv) / st[EHR_LM_PRED];
+                const double t = 2.0 * rho - 1.0;
+                lambda *= fmax(1.0 / 3.0, 1.0 - t * t * t);
+            }
+            nu = 2.0;
+            st[EHR_LM_F] = Fv;
+            if (PRIOR) st[EHR_LM_F_PRIOR] = sh.Fp;
+            st[EHR_LM_COUNT] = sh.cnt;
+            st[EHR_LM_RHO] = rho;
+            st[EHR_LM_ACCEPTED] += 1.0;
+        } else {
+            lambda *= nu;
+            nu *= 2.0;
+            st[EHR_LM_REJECTED] += 1.0;
+        }
+        st[EHR_LM_ITERATIONS] = (double)(it + 1);
+        st[EHR_LM_LAST] = accept ? 1.0 : 0.0;
+        st[EHR_LM_F_TRIAL] = Fv;
+        sh.accept = accept;
+        sh.lambda = lambda;
+        sh.nu = nu;
+        if (row) {
+            row[0] = Fv;
+            row[1] = accept ? 1.0 : 0.0;
+            row[3] = accept ? rho : __longlong_as_double(0x7ff8000000000000ll);
+        }
+    }
+    __syncthreads();
+    if (sh.accept) {
+        // the call's H into the packed H_acc: the same sums again (the same bits), every entry by one owner
+        for (int c = 0; c < C; c++) {
+            const double* __restrict__ info = sh.cam[c].info;
+            const int B = sh.cam[c].B, Nc = sh.P[c] + F;
+            double* const panel = lm_arrow_panel(st, c);
+            double* const bt = lm_arrow_border_t(st, c);
+            for (int e = tid; e < Nc * Nc; e += NT) {
+                const int r = lm_arrow_local(e / Nc, F), col = lm_arrow_local(e % Nc, F);
+                if (r < 0 && col < 0) continue;  // (the corner: below)
+                double s = 0.0;
+                for (int b = 0; b < B; b++) s += info[(size_t)b * Nc * Nc + e];
+                if (r >= 0)
+                    panel[r * ST + (col >= 0 ? col : PB + (-1 - col))] = s;
+                else
+                    bt[(-1 - r) * PB + col] = s;
+            }
+        }
+        for (int e = tid; e < F * F; e += NT) {  // the shared corner: its C terms one camera at a time
+            const int f = e / F, g = e - f * F;
+            double acc = 0.0;
+            for (int c = 0; c < C; c++) {
+                const double* __restrict__ info = sh.cam[c].info;
+                const int B = sh.cam[c].B, Nc = sh.P[c] + F;
+                double s = 0.0;
+                for (int b = 0; b < B; b++) s += info[((size_t)b * Nc + 6 + f) * Nc + 6 + g];
+                acc += s;
+            }
+            lm_arrow_corner(st)[f * LM_ARROW_FS + g] = acc;
+        }
+        if (tid < N) {
+            g_acc[tid] = sh.gv[tid];
+            th_acc[tid] = (double)lm_param_read(p, tid);
+        }
+    } else if (tid < N) {  // the stored linearisation: the inputs of this call are not read again
+        sh.gv[tid] = g_acc[tid];
+    }
+    __syncthreads();
+    // the diagonal of the system that is solved; the prior joins it and g, never the stored ones
+    if (tid < N) {
+        double d = mc >= 0 ? lm_arrow_panel(st, mc)[mi * ST + mi] : lm_arrow_corner(st)[mi * LM_ARROW_FS + mi];
+        if (PRIOR) {
+            const double w = prior_weight[tid];
+            if (w != 0.0) {
+                d += w;
+                sh.gv[tid] += 2.0 * w * (th_acc[tid] - prior_mean[tid]);
+            }
+        }
+        sh.dg[tid] = d;
+        sh.sv[tid] = d > 0.0 ? 1.0 / sqrt(d) : 0.0;
+    }
+    __syncthreads();
+    // 4. (S H S + lambda I) y = -S g / 2 by block elimination in the system's order
+    const int gc = tid >> 4, gl = tid & 15;  // this thread's camera panel and its lane there
+    const int gP = gc < C ? sh.P[gc] : 0, gb = gc < C ? sh.base[gc] : 0;
+    double(*const T)[PB] = sh.T[gc];
+    int retries = 0;
+    for (;;) {
+        const double lambda = sh.lambda;
+        for (int e = tid; e < C * LM_ARROW_ROWS * PB; e += NT) {
+            const int c = e / (LM_ARROW_ROWS * PB), rem = e - c * (LM_ARROW_ROWS * PB), r = rem / PB, j = rem - r * PB;
+            const int Pc = sh.P[c], b = sh.base[c];
+            double a = 0.0;
+            if (j < Pc) {
+                if (r < PB) {
+                    if (r < Pc) {
+                        a = (r == j ? sh.dg[b + r] : lm_arrow_panel(st, c)[r * ST + j]) * sh.sv[b + r] * sh.sv[b + j];
+                        if (r == j) a = sh.sv[b + r] > 0.0 ? a + lambda : 1.0;
+                    }
+                } else if (r - PB < F) {
+                    a = lm_arrow_border_t(st, c)[(r - PB) * PB + j] * sh.sv[S0 + r - PB] * sh.sv[b + j];
+                }
+            }
+            sh.T[c][r][j] = a;
+        }
+        for (int e = tid; e < F * F; e += NT) {
+            const int f = e / F, g = e - f * F;
+            double a = (f == g ? sh.dg[S0 + f] : lm_arrow_corner(st)[f * LM_ARROW_FS + g]) * sh.sv[S0 + f] * sh.sv[S0 + g];
+            if (f == g) a = sh.sv[S0 + f] > 0.0 ? a + lambda : 1.0;
+            sh.Cn[f][g] = a;
+        }
+        if (tid < N) sh.rv[tid] = -0.5 * sh.gv[tid] * sh.sv[tid];
+        if (tid == 0) sh.fail = 0;
+        __syncthreads();
+        // the camera panels side by side: A_c = L_c L_c^T right-looking, W_c^T = B_c^T L_c^-T, z_c = L_c^-1 r_c
+        for (int j = 0; j < PB; j++) {
+            const bool on = j < gP;
+            if (on && gl == 0) {
+                double piv = T[j][j];
+                if (!(piv > 0.0) || !lm_finite(piv)) {
+                    sh.fail = 1;
+                    piv = 1.0;
+                }
+                T[j][j] = sqrt(piv);
+            }
+            __syncthreads();
+            if (on) {
+                const double d = T[j][j];
+                for (int r = gl; r < LM_ARROW_ROWS; r += 16)
+                    if (r < PB ? (r > j && r < gP) : (r - PB < F)) T[r][j] = T[r][j] / d;
+                if (gl == 0) sh.yv[gb + j] = sh.rv[gb + j] / d;
+            }
+            __syncthreads();
+            if (on) {
+                for (int r = gl; r < LM_ARROW_ROWS; r += 16) {
+                    if (r < PB) {
+                        if (r > j && r < gP) {
+                            for (int k = j + 1; k <= r; k++) T[r][k] -= T[r][j] * T[k][j];
+                            sh.rv[gb + r] -= T[r][j] * sh.yv[gb + j];
+                        }
+                    } else if (r - PB < F) {
+                        for (int k = j + 1; k < gP; k++) T[r][k] -= T[r][j] * T[k][j];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        // the corner and its right-hand side lose W_c^T W_c and W_c^T z_c: camera order, then row order k, one owner per entry
+        for (int e = tid; e < F * F; e += NT) {
+            const int f = e / F, g = e - f * F;
+            if (g > f) continue;
+            double acc = sh.Cn[f][g];
+            for (int c = 0; c < C; c++)
+                for (int k = 0; k < sh.P[c]; k++) acc -= sh.T[c][PB + f][k] * sh.T[c][PB + g][k];
+            sh.Cn[f][g] = acc;
+        }
+        if (tid < F) {
+            double acc = sh.rv[S0 + tid];
+            for (int c = 0; c < C; c++)
+                for (int k = 0; k < sh.P[c]; k++) acc -= sh.T[c][PB + tid][k] * sh.yv[sh.base[c] + k];
+            sh.rv[S0 + tid] = acc;
+        }
+        __syncthreads();
+        for (int j = 0; j < F; j++) {  // the Schur complement's Cholesky: the dense kernel's
+            if (tid == 0) {
+                double piv = sh.Cn[j][j];
+                if (!(piv > 0.0) || !lm_finite(piv)) {
+                    sh.fail = 1;
+                    piv = 1.0;
+                }
+                sh.Cn[j][j] = sqrt(piv);
+            }
+            __syncthreads();
+            if (tid > j && tid < F) sh.Cn[tid][j] = sh.Cn[tid][j] / sh.Cn[j][j];
+            __syncthreads();
+            if (tid > j && tid < F)
+                for (int k = j + 1; k <= tid; k++) sh.Cn[tid][k] -= sh.Cn[tid][j] * sh.Cn[k][j];
+            __syncthreads();
+        }
+        if (!sh.fail || retries >= EHR_LM_MAX_RETRIES) break;
+        retries++;
+        __syncthreads();
+        if (tid == 0) {  // a non-positive pivot: raise lambda like a rejection and factor again
+            sh.lambda *= sh.nu;
+            sh.nu *= 2.0;
+        }
+        __syncthreads();
+    }
+    if (sh.fail) {  // the factorisation keeps failing: stop on the accepted point
+        if (tid < N) lm_param_write(p, tid, (float)th_acc[tid]);
+        if (tid == 0) {
+            st[EHR_LM_LAMBDA] = sh.lambda;
+            st[EHR_LM_NU] = sh.nu;
+            st[EHR_LM_RETRIES] += (double)retries;
+            st[EHR_LM_DONE] = 1.0;
+            st[EHR_LM_WHY] = 4.0;
+            if (row) row[2] = sh.lambda;
+        }
+        __syncthreads();
+        lm_write_K(p, tid);
+        return;
+    }
+    for (int j = 0; j < F; j++) {  // L_s z_s = r_s
+        if (tid == 0) sh.yv[S0 + j] = sh.rv[S0 + j] / sh.Cn[j][j];
+        __syncthreads();
+        if (tid > j && tid < F) sh.rv[S0 + tid] -= sh.Cn[tid][j] * sh.yv[S0 + j];
+        __syncthreads();
+    }
+    for (int j = F - 1; j >= 0; j--) {  // L_s^T y_s = z_s
+        if (tid == 0) sh.yv[S0 + j] = sh.yv[S0 + j] / sh.Cn[j][j];
+        __syncthreads();
+        if (tid < j) sh.yv[S0 + tid] -= sh.Cn[j][tid] * sh.yv[S0 + j];
+        __syncthreads();
+    }
+    // y_c = L_c^-T (z_c - W_c y_s): the offsets' terms last to first, then the camera's own rows, as the dense back-substitution
+    if (gl < gP) {
+        double acc = sh.yv[gb + gl];
+        for (int f = F - 1; f >= 0; f--) acc -= T[PB + f][gl] * sh.yv[S0 + f];
+        sh.yv[gb + gl] = acc;
+    }
+    __syncthreads();
+    for (int j = PB - 1; j >= 0; j--) {
+        const bool on = j < gP;
+        if (on && gl == 0) sh.yv[gb + j] = sh.yv[gb + j] / T[j][j];
+        __syncthreads();
+        if (on && gl < j) sh.yv[gb + gl] -= T[j][gl] * sh.yv[gb + j];
+        __syncthreads();
+    }
+    // hy = (S H S) y per row over its structurally non-zero columns, ascending; H_acc is read back from the state block
+    if (tid < N) {
+        const double sk = sh.sv[tid];
+        double s = 0.0;
+        if (mc >= 0) {
+            const double* const panel = lm_arrow_panel(st, mc);
+            const int b = sh.base[mc], Pc = sh.P[mc];
+            for (int j = 0; j < Pc; j++) s += ((j == mi ? sh.dg[tid] : panel[mi * ST + j]) * sk * sh.sv[b + j]) * sh.yv[b + j];
+            for (int f = 0; f < F; f++) s += (panel[mi * ST + PB + f] * sk * sh.sv[S0 + f]) * sh.yv[S0 + f];
+        } else {
+            for (int c = 0; c < C; c++) {
+                const double* const bt = lm_arrow_border_t(st, c);
+                const int b = sh.base[c], Pc = sh.P[c];
+                for (int j = 0; j < Pc; j++) s += (bt[mi * PB + j] * sk * sh.sv[b + j]) * sh.yv[b + j];
+            }
+            const double* const corner = lm_arrow_corner(st);
+            for (int f = 0; f < F; f++)
+                s += ((f == mi ? sh.dg[tid] : corner[mi * LM_ARROW_FS + f]) * sk * sh.sv[S0 + f]) * sh.yv[S0 + f];
+        }
+        sh.rv[tid] = s;                   // (S H S) y
+        sh.gv[tid] = sh.yv[tid] * sk;     // delta
+        st[EHR_LM_ARROW_DELTA + tid] = sh.gv[tid];
+    }
+    __syncthreads();
+    // 5, 6. the predicted reduction, the stopping rule, the next trial
+    if (tid == 0) {
+        const double lambda = sh.lambda;
+        double pred = 0.0;
+        for (int k = 0; k < N; k++) pred += sh.yv[k] * sh.rv[k] + 2.0 * lambda * (sh.yv[k] * sh.yv[k]);
+        int small = 1;
+        for (int k = 0; k < N; k++) small = small && (sh.gv[k] == 0.0 || fabs(sh.gv[k]) < lm_spacing_f32((float)th_acc[k]));
+        int why = 0;
+        if (pred <= ftol * st[EHR_LM_F])
+            why = 1;
+        else if (lambda >= lambda_max)
+            why = 2;
+        else if (small)
+            why = 3;
+        st[EHR_LM_LAMBDA] = lambda;
+        st[EHR_LM_NU] = sh.nu;
+        st[EHR_LM_PRED] = pred;
+        st[EHR_LM_RETRIES] += (double)retries;
+        if (why) {
+            st[EHR_LM_DONE] = 1.0;
+            st[EHR_LM_WHY] = (double)why;
+        }
+        if (row) row[2] = lambda;
+        sh.why = why;
+    }
+    __syncthreads();
+    if (tid < N) lm_param_write(p, tid, sh.why ? (float)th_acc[tid] : (float)(th_acc[tid] + sh.gv[tid]));
+    __syncthreads();
+    lm_write_K(p, tid);
+}
+
 }  // namespace ehr
 
 using namespace ehr;
@@ -1020,6 +1513,46 @@ int ehr_lm_update_rig_prior(const ehr_lm_rig_camera* cams, int C, float* offset,
                             const double* prior_weight, const double* prior_mean, void* stream) {
     return lm_update_rig_launch("ehr_lm_update_rig_prior", cams, C, offset, free_list, F, J, ftol, lambda_max, finalize, state,
                                 log, log_rows, prior_weight, prior_mean, stream);
+}
+
+int ehr_lm_update_rig_arrow(const ehr_lm_rig_arrow_camera* cams, int C, float* offset, const int32_t* free_list, int F, int J,
+                            double ftol, double lambda_max, int finalize, double* state, double* log, int log_rows,
+                            const double* prior_weight, const double* prior_mean, void* stream) {
+    const char* who = "ehr_lm_update_rig_arrow";
+    if (!cams || !state) return fail(EHR_ERR_INVALID, "%s: NULL cameras or state", who);
+    if (F < 0 || (F > 0 && (!offset || !free_list || J < 1 || J > 32)))
+        return fail(EHR_ERR_INVALID, "%s: free joints need offset and the list (J %d <= 32)", who, J);
+    if (C < 1 || C > EHR_LM_ARROW_MAX_CAMERAS)
+        return fail(EHR_ERR_INVALID, "%s: %d cameras; 1 <= C <= %d", who, C, EHR_LM_ARROW_MAX_CAMERAS);
+    LmArrowCameras by_value = {};
+    for (int c = 0; c < C; c++) {  // (a HOST array: every field can be judged here)
+        const ehr_lm_rig_arrow_camera& k = cams[c];
+        if (!k.info || !k.grad || !k.count || !k.loss || !k.dof)
+            return fail(EHR_ERR_INVALID, "%s: camera %d has a NULL pointer", who, c);
+        if (k.B < 1) return fail(EHR_ERR_INVALID, "%s: camera %d has B %d < 1", who, c, k.B);
+        const int Fi = lm_free_intrinsics(k.free4_mask, k.tie_focal);
+        if (Fi < 0)
+            return fail(EHR_ERR_INVALID, "%s: camera %d has bad free intrinsics (mask %d, tie_focal %d)", who, c, k.free4_mask,
+                        k.tie_focal);
+        if (k.free4_mask != 0 && (!k.theta || !k.K0 || !k.K || k.H < 1 || k.W < 1))
+            return fail(EHR_ERR_INVALID, "%s: camera %d has free intrinsics (mask %d) but no theta / K0 / K (H %d, W %d)", who, c,
+                        k.free4_mask, k.H, k.W);
+        if (F + Fi > EHR_LM_ARROW_MAX_SHARED)
+            return fail(EHR_ERR_INVALID, "%s: camera %d has %d free joints + %d free intrinsics; F + I_c <= %d", who, c, F, Fi,
+                        EHR_LM_ARROW_MAX_SHARED);
+        by_value.c[c] = k;
+    }
+    if (int rc = lm_prior_check(who, prior_weight, prior_mean)) return rc;
+    double* const lg = log && log_rows > 0 ? log : nullptr;
+    if (prior_weight)
+        lm_update_rig_arrow_kernel<true><<<1, LM_ARROW_THREADS, 0, (hipStream_t)stream>>>(
+            by_value, C, offset, free_list, F, J, ftol, lambda_max, finalize, state, lg, log_rows,
+            LmPriorArgs<true>{prior_weight, prior_mean});
+    else
+        lm_update_rig_arrow_kernel<false><<<1, LM_ARROW_THREADS, 0, (hipStream_t)stream>>>(
+            by_value, C, offset, free_list, F, J, ftol, lambda_max, finalize, state, lg, log_rows, LmPriorArgs<false>{});
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
 }
 
 }  // extern "C"

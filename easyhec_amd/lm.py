@@ -121,6 +121,14 @@ class _LmDriver:
     state block) and ``names``, calls :meth:`_init_driver`, and provides the ONE C call ``_update(stream, finalize=0)``.
     ``who`` names the owner in the guard's messages."""
     who, label, _forward_kinematics, prior = "solve_lm", "", None, None
+    # the state block's size, the parameters it has room for and its reading are the driver's: None is ehr_lm_update's
+    # (_lib.LM_STATE_DOUBLES, _lib.LM_MAX_PARAMS, read when the buffers are made); the rig's block-arrow update has a larger
+    # block of its own (easyhec_amd.lm_rig)
+    state_doubles = max_params = None
+
+    def _namespace(self, s):
+        """One state block (``s``: its float64 words on the host) as the namespace :meth:`states` documents."""
+        return state_namespace(s, self.N)
 
     def set_prior(self, prior):
         """Take an :class:`LmPrior` made for this driver's parameters (None: no prior, today's update).  Set before the first
@@ -161,8 +169,9 @@ class _LmDriver:
 
     def _init_driver(self, P, lambda0, ftol, lambda_max, log_rows, units=None):
         N, dev = self.N, self.dev
-        if N > _lib.LM_MAX_PARAMS:
-            raise ValueError(f"{self.who}: the step optimises {N} parameters; the kernels take {_lib.LM_MAX_PARAMS}")
+        max_params = _lib.LM_MAX_PARAMS if self.max_params is None else self.max_params
+        if N > max_params:
+            raise ValueError(f"{self.who}: the step optimises {N} parameters; the kernels take {max_params}")
         self.P = P
         self.ftol, self.lambda_max, self.lambda0 = float(ftol), float(lambda_max), float(lambda0)
         self.units = [self] if units is None else list(units)
@@ -170,7 +179,7 @@ class _LmDriver:
             u.mvp = torch.empty((u.B, u.L, 4, 4), device=dev)
             u.dmvp = torch.empty((u.N, u.B, u.L, 4, 4), device=dev)
             u.out = information._outputs(u.N, u.B, u.L, dev, True, False)
-        st = np.zeros((P, _lib.LM_STATE_DOUBLES))
+        st = np.zeros((P, _lib.LM_STATE_DOUBLES if self.state_doubles is None else self.state_doubles))
         st[:, _lib.LM_STATE["lambda"]], st[:, _lib.LM_STATE["nu"]] = self.lambda0, 2.0
         self.state_block = self._state = torch.from_numpy(st).to(dev)  # (a subclass may publish views of the two)
         self.log_rows = int(log_rows)
@@ -223,7 +232,7 @@ class _LmDriver:
         count, F_prior (the prior's term of F_acc; 0 without a prior) and theta [N], delta [N], g [N], H [N,N] of the accepted
         point (H and g: the data's own, under a prior too)."""
         s = self._state.cpu().numpy()
-        return [state_namespace(s[p], self.N) for p in range(self.P)]
+        return [self._namespace(s[p]) for p in range(self.P)]
 
     def trajectory(self, p):
         """Hypothesis p's [iterations, 4] float64 (CPU): per iteration the trial's loss (NaN: reported), 1 accepted / 0

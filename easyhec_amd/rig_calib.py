@@ -88,6 +88,8 @@ class RigJointStep(_ReportedStepProtocol):
         self.loss = torch.zeros((C,), device=self.dev)
         self.cameras = [_RigCameraStep(models[c], batches[c], robot, qpos[c], free, g, self.loss[c:c + 1],
                                        **dict(kw, **{k: v[c] for k, v in per.items()})) for c in range(C)]
+        for cam, batch in zip(self.cameras, batches):
+            cam.batch_K = batch["K"]  # as given, every view's: read only (solve_lm_rig judges it where intrinsics are freed)
         first = self.cameras[0]
         if any(cam.L != first.L for cam in self.cameras):
             raise ValueError(f"RigJointStep: the cameras render {[cam.L for cam in self.cameras]} links: one robot, one link count")

@@ -735,7 +735,8 @@ int ehr_lm_update_multi_calib(const double* info, const double* grad, const long
  *   3-6. ehr_lm_update's, by the same device function over the rig's parameters: accept or reject, the damped scaled Cholesky
  *      solve with the exclusion of H_kk <= 0 and the retries, pred, the stopping rule and the trial fl32(theta_acc + delta)
  *      through every cams[c].dof and offset.  There are no intrinsics in a rig: no K is rewritten.
- * Out of scope: per-camera intrinsics, more than EHR_LM_MAX_PARAMS parameters (C <= 5 with F <= 2, C <= 4 with F <= 8, ...).
+ * Out of scope here: per-camera intrinsics, more than EHR_LM_MAX_PARAMS parameters (C <= 5 with F <= 2, C <= 4 with F <= 8, ...);
+ * ehr_lm_update_rig_arrow below takes both.
  * ehr_version() is unchanged: the presence of this symbol is the capability check. */
 typedef struct {            /* one camera of the rig's update; all pointers are device pointers */
     const double *info, *grad;  const long long* count;  const float* loss;   /* ehr_mask_information's outputs for its views */
@@ -750,7 +751,68 @@ int ehr_lm_update_rig_prior(const ehr_lm_rig_camera* cams /* HOST array [C] */, 
                             int F, int J, double ftol, double lambda_max, int finalize, double* state, double* log,
                             int log_rows, const double* prior_weight, const double* prior_mean, void* stream);
 
-/* Information-gain exploration: which candidate joint configuration to observe next.  A candidate is a group of S consecutive
+/* The rig's Levenberg-Marquardt update on its BLOCK-ARROW system: per-camera intrinsics, and no limit of 32 parameters.
+ * Camera c frees I_c in 0..4 intrinsics (free4_mask / tie_focal as for ehr_lm_linearize; the set may differ per camera and may
+ * be empty), P_c = 6 + I_c, base_c = P_0 + ... + P_{c-1}, S0 = base_C, N = S0 + F, in the order
+ *     cam0.dof[0..5], cam0.theta[...], cam1.dof[0..5], cam1.theta[...], ..., offset[free_list[0..F)]
+ * with theta[...] in ehr_lm_linearize's order (f | fx, fy, then cx, cy).  Without intrinsics it is ehr_lm_update_rig's order.
+ * The per-camera calls are unchanged: ehr_joint_forward, ehr_lm_linearize and ehr_mask_information with the camera's own
+ * free4_mask, tie_focal and N_c = 6 + F + I_c; camera c's local index (dof, offsets, intrinsics) embeds as
+ *     i < 6 -> base_c + i,     6 + f -> S0 + f,     6 + F + q -> base_c + 6 + q.
+ * Limits: 1 <= C <= EHR_LM_ARROW_MAX_CAMERAS, F + I_c <= EHR_LM_ARROW_MAX_SHARED (N_c <= 32), hence N <= 182.
+ * `cams` is a HOST array, judged here before anything is launched (EHR_ERR_INVALID, the message names the camera: C outside
+ * 1..16, a NULL pointer, B_c < 1, F + I_c > 26, free4_mask outside 0..15, tie_focal without bits 0 and 1, a free mask with NULL
+ * theta / K0 / K, one prior pointer NULL and the other not) and travels to the kernel by value.  One workgroup of 256 threads,
+ * float64, every sum in a fixed order, no atomics, every loop bounded; never allocates or synchronises.
+ *   1. ehr_lm_update_rig's head: per camera, in camera order, S_c, s_c, F_c, n_c from 0.0 in view order; the system is cleared
+ *      and every camera embedded with `+=` in camera order (the shared corner gets its C terms one camera at a time, by one owner
+ *      per entry); F and count from 0.0 in camera order.  The matrices need not be symmetric to the last bit: both halves of
+ *      every block are stored as given.
+ *   2, 3. ehr_lm_update's: a bad sum of ANY camera reports the call rig-wide (every accepted pose, every accepted theta with its
+ *      K rewritten, and the accepted offsets are written back, `reported` is incremented, nothing else moves); accept / reject
+ *      and Nielsen's schedule.  prior_weight, prior_mean [N] (both or neither): ehr_lm_update_prior's rule -- the term joins F,
+ *      p_k and 2 p_k (theta_acc_k - mu_k) the system that is solved, the stored H, g stay the data's.
+ *   4. (S H S + lambda I) y = -S g / 2, parameters with H_kk <= 0 left out, by block elimination in the system's order: for
+ *      c = 0 .. C-1, A_c = L_c L_c^T (right-looking, column by column), W_c = L_c^-1 B_c, z_c = L_c^-1 r_c; the corner and its
+ *      right-hand side lose W_c^T W_c and W_c^T z_c, the terms in camera order and within a camera in row order k = 0 .. P_c-1;
+ *      S^ = L_s L_s^T, y_s by two triangular solves, y_c = L_c^-T (z_c - W_c y_s).  This is the dense right-looking Cholesky of
+ *      ehr_lm_update in the system's order with the updates by structurally zero blocks left out.  A non-positive or non-finite
+ *      pivot anywhere raises lambda like a rejection and factors again, 8 times at the most, then why = 4.  (S H S) y per row
+ *      over that row's structurally non-zero columns, ascending; pred, the stopping rule and `small` for k ascending over N.
+ *   6. The trial fl32(theta_acc + delta) through every cams[c].dof, every free theta element (under tie_focal theta[1] follows
+ *      theta[0]) and offset; every camera with free intrinsics gets its K rewritten from K0 and theta by
+ *      ehr_intrinsics_backward_adam's "writing K" rule; a camera without has its K left untouched.
+ * The state block has EHR_LM_ARROW_STATE_DOUBLES float64; the caller clears it and sets EHR_LM_LAMBDA and EHR_LM_NU.  Words
+ * 0..15 are EHR_LM_LAMBDA .. EHR_LM_F_PRIOR; then theta, delta, g with a capacity of EHR_LM_ARROW_MAX_PARAMS each; then H_acc
+ * packed, every offset a constant: per camera c at EHR_LM_ARROW_H + c * EHR_LM_ARROW_CAMERA_STRIDE a panel [10][10 + 26] (row i
+ * of its block: columns 0..P_c-1 the block, columns 10 + f its coupling to offset f) followed at EHR_LM_ARROW_BORDER_T by the
+ * border's other half [26][10] (row f, column i: H[S0 + f][base_c + i]); then the corner [26][26] at EHR_LM_ARROW_CORNER.
+ * ehr_version() is unchanged: the presence of this symbol is the capability check. */
+#define EHR_LM_ARROW_MAX_CAMERAS 16
+#define EHR_LM_ARROW_MAX_BLOCK 10      /* P_c <= 6 + 4 */
+#define EHR_LM_ARROW_MAX_SHARED 26     /* F + I_c <= 26 */
+#define EHR_LM_ARROW_MAX_PARAMS 192    /* capacity of theta, delta, g (N <= 182) */
+#define EHR_LM_ARROW_THETA 16
+#define EHR_LM_ARROW_DELTA 208
+#define EHR_LM_ARROW_G 400
+#define EHR_LM_ARROW_H 592
+#define EHR_LM_ARROW_PANEL_STRIDE 36   /* row stride of a camera's panel */
+#define EHR_LM_ARROW_BORDER_T 360      /* within a camera's part: the border's other half, row stride 10 */
+#define EHR_LM_ARROW_CAMERA_STRIDE 620
+#define EHR_LM_ARROW_CORNER 10512      /* [26][26], row stride 26 */
+#define EHR_LM_ARROW_STATE_DOUBLES 11188
+typedef struct {            /* one camera of the arrow update; all pointers are device pointers */
+    const double *info, *grad;  const long long* count;  const float* loss;   /* ehr_mask_information's outputs, N_c = 6 + F + I_c */
+    float* dof;                                                                 /* its 6 pose coordinates */
+    float* theta;  const float* K0;  float* K;                                  /* NULL where free4_mask == 0 */
+    int B, H, W, free4_mask, tie_focal;
+} ehr_lm_rig_arrow_camera;
+int ehr_lm_update_rig_arrow(const ehr_lm_rig_arrow_camera* cams /* HOST array [C] */, int C, float* offset,
+                            const int32_t* free_list, int F, int J, double ftol, double lambda_max, int finalize, double* state,
+                            double* log, int log_rows, const double* prior_weight, const double* prior_mean /* [N] */,
+                            void* stream);
+
+/* Information-gain exploration: which candidate joint configuration to observe next. A candidate is a group of S consecutive
  * views of info [Q,S,N,N] -- ehr_mask_information's matrices of the views the candidate WOULD give (the op's info does not depend
  * on the reference mask, so they exist before the candidate is observed); S > 1 averages over sampled poses or sums over cameras.
  * Both calls take device pointers only, never allocate or synchronise and launch on `stream`; k rounds of gain + pick are 2k
