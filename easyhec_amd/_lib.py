@@ -108,6 +108,8 @@ SIGNATURES = {
                                 [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
     "ehr_information_gain": (c_int, [c_void_p] * 4 + [c_int] * 3 + [ctypes.c_double, ctypes.c_uint32, c_void_p, c_void_p]),
     "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
+    "ehr_config_clearance": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, ctypes.c_double] +
+                             [c_int] * 2 + [c_void_p] * 5),
 }
 
 
@@ -200,7 +202,12 @@ def has_information_gain():
     return has_symbols("ehr_information_gain", "ehr_information_pick")
 
 
+def has_feasibility():
+    return has_symbols("ehr_config_clearance")
+
+
 IG_MAX_PARAMS = 32  # include/ehr.h: EHR_IG_MAX_PARAMS
+FEAS_MAX_LINKS, FEAS_MAX_SPHERES, FEAS_MAX_PLANES, FEAS_MAX_OBSTACLES = 32, 4096, 16, 1024  # include/ehr.h: EHR_FEAS_*
 
 
 # the state block of ehr_lm_update (include/ehr.h: EHR_LM_*), in float64 words

@@ -1,0 +1,424 @@
+"""Feasibility of candidate joint configurations, on the device (``ehr_config_clearance`` in include/ehr.h,
+csrc/ehr_feasible.hip).
+
+The explorers score thousands of candidate joint configurations and the arm moves to the best one; whether it CAN go there
+the reference decides with three filters in front of its scoring (space_explorer.py:105-137 of the reference: self-collision,
+a maximum-distance constraint over the links, a workspace-boundary point cloud).  This module is their stand-in:
+
+    link_spheres      a link's mesh -> proxy spheres (a median-split tree over the triangles; every triangle of a leaf lies
+                      inside the leaf's sphere, so clear spheres mean clear meshes: the filter is conservative)
+    config_clearance  one ``ehr_config_clearance`` launch on device tensors
+    FeasibilityFilter the robot's proxies, the link pairs worth checking, the environment (half-spaces, obstacle spheres, a
+                      ball of allowed reach) and ``check``: candidates (and the straight joint-space segment from the current
+                      configuration to each) -> ``valid`` and the clearances, device tensors, with no host synchronisation
+
+What it is NOT: a mesh-exact collision test, or a planner -- the straight segment is sampled at ``path_steps`` configurations,
+nothing is searched or timed.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
+not covered.  HIP only; no fallback."""
+import ctypes
+import types
+
+import numpy as np
+import torch
+
+from . import _lib, dr
+
+__all__ = ["link_spheres", "link_bound", "box_planes", "robot_proxies", "enabled_pairs", "config_clearance",
+           "FeasibilityFilter", "REFERENCE_WORKSPACE"]
+
+REFERENCE_WORKSPACE = ((-0.2, -0.5, -0.5), (1.0, 0.5, 1.0))  # the reference's workspace box (workspace_boundary.py:9)
+
+
+def _missing():
+    raise RuntimeError("this libehr_hip.so has no feasibility kernel (ehr_config_clearance): rebuild it")
+
+
+# ---- proxy geometry (host, once per robot) --------------------------------------------------------------------------------
+def _enclosing(points):
+    """(centre, radius): the midpoint of the points' bounding box and the largest computed distance to them, moved up by one
+    ``np.nextafter``."""
+    c = 0.5 * (points.min(axis=0) + points.max(axis=0))
+    d = points - c
+    r = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).max()
+    return c, np.nextafter(r, np.inf)
+
+
+def link_spheres(vertices, faces, leaf_triangles=64, return_leaves=False):
+    """[S,4] float64 (centre, radius) proxy spheres of one link's mesh.  The triangles are split recursively at the median
+    of their centroids along the axis on which the centroids extend furthest (stable argsort, ``n // 2`` to the first half)
+    until a leaf holds ``<= leaf_triangles``; a leaf's sphere is :func:`_enclosing` of its triangles' vertices.  Deterministic;
+    every triangle of a leaf lies inside its sphere.  A link without triangles has no spheres.  ``return_leaves``: also the list of
+    every leaf's triangle indices, in the spheres' order."""
+    leaf_triangles = int(leaf_triangles)
+    if leaf_triangles < 1:
+        raise ValueError("leaf_triangles must be >= 1")
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if f.shape[0] == 0:
+        return (np.zeros((0, 4), dtype=np.float64), []) if return_leaves else np.zeros((0, 4), dtype=np.float64)
+    if f.min() < 0 or f.max() >= v.shape[0]:
+        raise ValueError("link_spheres: a face indexes past the vertices")
+    tri = v[f]                                            # [T,3,3]
+    cent = ((tri[:, 0] + tri[:, 1]) + tri[:, 2]) / 3.0
+    out, leaves, stack = [], [], [np.arange(f.shape[0])]
+    while stack:                                          # depth first, the first half first
+        idx = stack.pop()
+        n = idx.shape[0]
+        if n <= leaf_triangles:
+            c, r = _enclosing(tri[idx].reshape(-1, 3))
+            out.append([c[0], c[1], c[2], r])
+            leaves.append(idx)
+            continue
+        ci = cent[idx]
+        axis = int(np.argmax(ci.max(axis=0) - ci.min(axis=0)))
+        order = np.argsort(ci[:, axis], kind="stable")
+        stack.append(idx[order[n // 2:]])
+        stack.append(idx[order[:n // 2]])
+    out = np.asarray(out, dtype=np.float64)
+    return (out, leaves) if return_leaves else out
+
+
+def link_bound(vertices, spheres):
+    """[4] float64: the link's one bounding sphere, which the kernel culls with.  Its centre is the midpoint of the bounding box
+    of ALL the link's vertices, as a leaf's; its radius reaches every vertex AND every proxy sphere (a leaf's sphere may stick
+    out of the sphere around the vertices, and a bound that culls must contain what it stands for), moved up by one
+    ``np.nextafter``."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    s = np.asarray(spheres, dtype=np.float64).reshape(-1, 4)
+    if v.shape[0] == 0 and s.shape[0] == 0:
+        return np.zeros(4, dtype=np.float64)
+    pts = v if v.shape[0] else s[:, :3]
+    c, r = _enclosing(pts)
+    if s.shape[0]:
+        d = s[:, :3] - c
+        r = max(r, np.nextafter((np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]) + s[:, 3]).max(), np.inf))
+    return np.array([c[0], c[1], c[2], r], dtype=np.float64)
+
+
+def box_planes(lo, hi):
+    """[6,4] float64: the six inward half-spaces (n, d), ``n.x + d >= 0`` inside, of the box lo..hi."""
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise ValueError(f"box_planes: need finite lo < hi, got {lo.tolist()} .. {hi.tolist()}")
+    out = np.zeros((6, 4), dtype=np.float64)
+    for k in range(3):
+        out[2 * k, k], out[2 * k, 3] = 1.0, -lo[k]
+        out[2 * k + 1, k], out[2 * k + 1, 3] = -1.0, hi[k]
+    return out
+
+
+def robot_proxies(robot, leaf_triangles=64):
+    """(spheres [S,4], sphere_offsets [L+1] int32, link_bounds [L,4]) of the robot's rendered links, concatenated."""
+    per_link = [link_spheres(v, f, leaf_triangles) for v, f in robot.meshes]
+    offsets = np.zeros(len(per_link) + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum([s.shape[0] for s in per_link])
+    spheres = np.concatenate(per_link) if per_link else np.zeros((0, 4))
+    bounds = np.stack([link_bound(v, s) for (v, _), s in zip(robot.meshes, per_link)])
+    return np.ascontiguousarray(spheres, dtype=np.float64), offsets, bounds
+
+
+def _world_spheres(link_poses, spheres, offsets):
+    """[n,S,4] float64: the spheres in the base frame at link_poses [n,L,4,4] (float32 values), by the kernel's expression."""
+    T = np.asarray(link_poses, dtype=np.float32).astype(np.float64)
+    link = np.repeat(np.arange(len(offsets) - 1), np.diff(offsets))
+    R = T[:, link]                                                       # [n,S,4,4]
+    x, y, z = spheres[None, :, 0], spheres[None, :, 1], spheres[None, :, 2]
+    out = np.empty((T.shape[0], spheres.shape[0], 4), dtype=np.float64)
+    for k in range(3):
+        out[..., k] = ((R[..., k, 0] * x + R[..., k, 1] * y) + R[..., k, 2] * z) + R[..., k, 3]
+    out[..., 3] = spheres[None, :, 3]
+    return out
+
+
+def pair_clearances(link_poses, spheres, offsets):
+    """{(i, j): proxy clearance of link pair i < j, the minimum over the configurations of link_poses [n,L,4,4]} on the host
+    (numpy): what the automatic pair list is decided on, once per robot.  Pairs with a link that has no spheres: +inf."""
+    W = _world_spheres(link_poses, spheres, offsets)
+    L = len(offsets) - 1
+    out = {}
+    for i in range(L):
+        for j in range(i + 1, L):
+            A, B = W[:, offsets[i]:offsets[i + 1]], W[:, offsets[j]:offsets[j + 1]]
+            if A.shape[1] == 0 or B.shape[1] == 0:
+                out[(i, j)] = np.inf
+                continue
+            d = A[:, :, None, :3] - B[:, None, :, :3]
+            gap = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) - \
+                (A[:, :, None, 3] + B[:, None, :, 3])
+            out[(i, j)] = float(gap.min())
+    return out
+
+
+def _tree_relations(table):
+    """(adjacent, rigid): sets of rendered-link pairs (i < j).  adjacent: one is the other's nearest rendered ancestor; rigid:
+    no active joint lies on the tree path between them."""
+    parent, qidx, use = np.asarray(table["parent"]), np.asarray(table["qidx"]), np.asarray(table["use"])
+    link_of = {int(n): l for l, n in enumerate(use)}
+    chains = []
+    for n in use:
+        chain, i = [], int(n)
+        while i >= 0:
+            chain.append(i)
+            i = int(parent[i])
+        chains.append(chain)
+    adjacent, rigid = set(), set()
+    for l, chain in enumerate(chains):
+        for n in chain[1:]:
+            if n in link_of:
+                if link_of[n] != l:
+                    adjacent.add((min(l, link_of[n]), max(l, link_of[n])))
+                break
+    L = len(use)
+    for i in range(L):
+        for j in range(i + 1, L):
+            a, b = chains[i], chains[j]
+            common = set(a) & set(b)
+            between = [n for n in a if n not in common] + [n for n in b if n not in common]
+            if all(qidx[n] < 0 for n in between):
+                rigid.add((i, j))
+    return adjacent, rigid
+
+
+def enabled_pairs(robot, spheres, offsets, margin=0.01, ignore_pairs="auto", settle_qpos=None):
+    """(pairs, ignored) of the robot's rendered links.  Every pair i < j is enabled but: a link and its nearest rendered
+    ancestor ("adjacent"); pairs with only fixed joints between them ("rigid"); and, with ``ignore_pairs="auto"``, pairs whose
+    proxy clearance at ``settle_qpos`` (default: the zero configuration; may be several) is ``<= margin`` ("settle": proxies
+    that touch where the arm is known to be free tell nothing) -- or, with a list of pairs, exactly those ("listed").
+    ``ignored``: a list of ``{"pair", "reason", "clearance"}`` with the settle clearance of each."""
+    table = robot.joint_table()
+    L = len(offsets) - 1
+    adjacent, rigid = _tree_relations(table)
+    q0 = np.zeros((1, robot.chain.dof)) if settle_qpos is None else np.atleast_2d(np.asarray(settle_qpos, dtype=np.float64))
+    settle = pair_clearances(robot.link_poses_batch(q0).astype(np.float32), spheres, offsets)
+    listed = None
+    if not (isinstance(ignore_pairs, str) and ignore_pairs == "auto"):
+        listed = {(min(int(a), int(b)), max(int(a), int(b))) for a, b in ignore_pairs}
+        if any(a == b or a < 0 or b >= L for a, b in listed):
+            raise ValueError(f"ignore_pairs {sorted(listed)}: pairs of two different links out of 0..{L - 1}")
+    pairs, ignored = [], []
+    for i in range(L):
+        for j in range(i + 1, L):
+            p, c = (i, j), settle[(i, j)]
+            if p in adjacent:
+                why = "adjacent"
+            elif p in rigid:
+                why = "rigid"
+            elif listed is not None:
+                why = "listed" if p in listed else None
+            else:
+                why = "settle" if c <= margin else None
+            if why is None:
+                pairs.append(p)
+            else:
+                ignored.append({"pair": p, "reason": why, "clearance": c})
+    return pairs, ignored
+
+
+def pair_words(pairs, L):
+    """[L] uint32: bit j of word i (j > i) = pair (i, j) is checked."""
+    w = np.zeros(L, dtype=np.uint32)
+    for i, j in pairs:
+        i, j = (int(i), int(j)) if i < j else (int(j), int(i))
+        if not 0 <= i < j < L:
+            raise ValueError(f"pair ({i}, {j}): two different links out of 0..{L - 1}")
+        w[i] |= np.uint32(1) << np.uint32(j)
+    return w
+
+
+# ---- the kernel -------------------------------------------------------------------------------------------------------------
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def config_clearance(link_poses, spheres, sphere_offsets, link_bounds, pair_enable, planes=None, obstacles=None, env_links=0,
+                     reach=None, cutoff=0.25):
+    """One ``ehr_config_clearance`` launch (include/ehr.h).  Device tensors: link_poses [n,L,4,4] float32, spheres [S,4],
+    link_bounds [L,4], planes [Np,4], obstacles [No,4], reach [4] float64, pair_enable [L] int32 (the uint32 words' bits);
+    ``sphere_offsets`` [L+1]: a HOST array.  Returns a namespace of device tensors [n]: ``self_clear``, ``env_clear``,
+    ``reach_clear`` float64 and ``self_pair`` int32.  Never synchronises; the sizes' limits are the library's to refuse."""
+    if not _lib.has_feasibility():
+        _missing()
+    dr._check_dev("link_poses", link_poses, torch.float32)
+    dev = link_poses.device
+    dr._require(link_poses.dim() == 4 and tuple(link_poses.shape[2:]) == (4, 4), "link_poses must have shape [n, L, 4, 4]")
+    n, L = int(link_poses.shape[0]), int(link_poses.shape[1])
+    off = np.ascontiguousarray(np.asarray(sphere_offsets), dtype=np.int32)
+    dr._require(off.shape == (L + 1,), "sphere_offsets must be a host array of L + 1 entries")
+
+    def f64(name, t, rows):
+        if t is None:
+            return None
+        dr._check_dev(name, t, torch.float64)
+        dr._require(t.device == dev and t.dim() == 2 and t.shape[1] == 4 and t.shape[0] >= rows, f"{name} must have shape [{rows}, 4]")
+        return t.contiguous()
+
+    spheres = f64("spheres", spheres, max(int(off[-1]), 0))
+    link_bounds = f64("link_bounds", link_bounds, L)
+    planes, obstacles = f64("planes", planes, 0), f64("obstacles", obstacles, 0)
+    if reach is not None:
+        dr._check_dev("reach", reach, torch.float64)
+        dr._require(reach.device == dev and reach.numel() == 4, "reach must have 4 entries")
+        reach = reach.contiguous()
+    dr._check_dev("pair_enable", pair_enable, torch.int32)
+    dr._require(pair_enable.device == dev and pair_enable.shape == (L,), "pair_enable must have shape [L]")
+    out = types.SimpleNamespace(self_clear=torch.empty((n,), dtype=torch.float64, device=dev),
+                                self_pair=torch.empty((n,), dtype=torch.int32, device=dev),
+                                env_clear=torch.empty((n,), dtype=torch.float64, device=dev),
+                                reach_clear=torch.empty((n,), dtype=torch.float64, device=dev))
+    Np = 0 if planes is None else int(planes.shape[0])
+    No = 0 if obstacles is None else int(obstacles.shape[0])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ehr_config_clearance(
+            _lib.ptr(link_poses.contiguous()), _lib.ptr(spheres), off.ctypes.data_as(ctypes.c_void_p), _lib.ptr(link_bounds),
+            _lib.ptr(pair_enable.contiguous()), _lib.ptr(planes) if Np else None, Np, _lib.ptr(obstacles) if No else None, No,
+            int(env_links) & 0xffffffff, _lib.ptr(reach), float(cutoff), n, L, _lib.ptr(out.self_clear), _lib.ptr(out.self_pair),
+            _lib.ptr(out.env_clear), _lib.ptr(out.reach_clear), _stream()), "ehr_config_clearance")
+    return out
+
+
+# ---- the filter -------------------------------------------------------------------------------------------------------------
+def _rows4(a, name, limit):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, 4))
+    if a.shape[0] > limit or not np.isfinite(a).all():
+        raise ValueError(f"{name}: at most {limit} finite rows of 4, got {a.shape[0]}")
+    return a if a.shape[0] else None
+
+
+class FeasibilityFilter:
+    """Which candidate joint configurations the arm can take: sphere proxies of the rendered links against each other, against
+    half-spaces and obstacle spheres, and inside a ball of allowed reach.
+
+    robot: :class:`easyhec_amd.robot.Robot`.  leaf_triangles: see :func:`link_spheres`.  margin: the clearance [m] a valid
+    configuration keeps to itself and to the environment.  ignore_pairs / settle_qpos: see :func:`enabled_pairs`.  planes
+    [Np,4] (n, d), ``n.x + d >= 0`` inside (normalised here to unit n; :func:`box_planes` makes a workspace box); obstacles
+    [No,4] spheres in the base frame; env_links: the rendered links tested against both (default: every link an active joint
+    moves -- the base stands on the table).  reach: (centre, radius) of the ball every proxy must stay inside, or None.
+    cutoff: clearances are reported up to this value [m].  offsets: joint zero offsets [J] for the kinematics -- None (zeros),
+    an array, or a solve step's current offsets tensor (read on every call).  path_steps: what an online loop passes to
+    :meth:`check` (None: 1).
+
+    ``pairs``: the enabled link pairs; ``ignored``: the others with reason and settle clearance."""
+
+    def __init__(self, robot, leaf_triangles=64, margin=0.01, ignore_pairs="auto", settle_qpos=None, planes=None,
+                 obstacles=None, env_links=None, reach=None, cutoff=0.25, offsets=None, device="cuda:0", path_steps=None):
+        from .joint_calib import _check_table
+        if not _lib.has_feasibility():
+            _missing()
+        if not (np.isfinite(cutoff) and cutoff > 0 and np.isfinite(margin) and 0 <= margin < cutoff):
+            raise ValueError(f"FeasibilityFilter: need 0 <= margin < cutoff, finite (margin {margin}, cutoff {cutoff})")
+        self.robot, self.margin, self.cutoff = robot, float(margin), float(cutoff)
+        self.path_steps = None if path_steps is None else int(path_steps)
+        self.dev = dev = torch.device(device)
+        table = robot.joint_table()
+        self.J, self.L = int(robot.chain.dof), int(robot.num_links)
+        _check_table(table, self.J)
+        if not 1 <= self.L <= _lib.FEAS_MAX_LINKS:
+            raise ValueError(f"FeasibilityFilter: {self.L} rendered links; the kernel takes 1..{_lib.FEAS_MAX_LINKS}")
+        self.spheres, self.sphere_offsets, self.link_bounds = robot_proxies(robot, leaf_triangles)
+        if self.spheres.shape[0] > _lib.FEAS_MAX_SPHERES:
+            raise ValueError(f"FeasibilityFilter: {self.spheres.shape[0]} proxy spheres; the kernel takes {_lib.FEAS_MAX_SPHERES} "
+                             "(raise leaf_triangles)")
+        self.pairs, self.ignored = enabled_pairs(robot, self.spheres, self.sphere_offsets, self.margin, ignore_pairs, settle_qpos)
+        moved = [l for l in range(self.L) if int(table["upstream"][l]) != 0]
+        self.env_links = moved if env_links is None else sorted({int(l) for l in env_links})
+        if any(l < 0 or l >= self.L for l in self.env_links):
+            raise ValueError(f"env_links {self.env_links}: rendered links are 0..{self.L - 1}")
+        self.env_mask = sum(1 << l for l in self.env_links)
+        planes = _rows4(planes, "planes", _lib.FEAS_MAX_PLANES)
+        if planes is not None:
+            norm = np.sqrt((planes[:, :3] ** 2).sum(axis=1))
+            if not (norm > 0).all():
+                raise ValueError("planes: a normal of length 0")
+            planes = planes / norm[:, None]
+        self.planes, self.obstacles = planes, _rows4(obstacles, "obstacles", _lib.FEAS_MAX_OBSTACLES)
+        if reach is not None:
+            reach = np.asarray(reach, dtype=np.float64).reshape(-1)
+            if reach.shape != (4,) or not np.isfinite(reach).all() or reach[3] <= 0:
+                raise ValueError("reach: (cx, cy, cz, radius > 0)")
+        self.reach = reach
+        up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=dt)).to(dev)
+        self._t = [up(table[k], dt) for k, dt in (("parent", np.int32), ("origin", np.float64), ("kind", np.int32),
+                                                  ("axis", np.float64), ("qidx", np.int32), ("use", np.int32))]
+        self._N = int(table["parent"].shape[0])
+        self._spheres, self._bounds = up(self.spheres, np.float64), up(self.link_bounds, np.float64)
+        self._pair_enable = up(pair_words(self.pairs, self.L).view(np.int32), np.int32)
+        self._planes, self._obstacles, self._reach = up(self.planes, np.float64), up(self.obstacles, np.float64), up(reach, np.float64)
+        if offsets is None:
+            self.offsets = torch.zeros((self.J,), dtype=torch.float32, device=dev)
+        elif torch.is_tensor(offsets) and offsets.device == dev and offsets.dtype == torch.float32:
+            self.offsets = offsets                      # a step's own tensor: its current values on every call
+        else:
+            self.offsets = torch.as_tensor(np.asarray(offsets.detach().cpu() if torch.is_tensor(offsets) else offsets,
+                                                      dtype=np.float32)).to(dev)
+        if tuple(self.offsets.shape) != (self.J,) or not self.offsets.is_contiguous():
+            raise ValueError(f"offsets must be a contiguous [{self.J}] tensor")
+
+    # -- the parts ----------------------------------------------------------------------------------------------------------
+    def path_table(self, qposes, current_qpos=None, path_steps=1):
+        """[Q * path_steps, J] float64 (host): per candidate the configurations ``current + (s + 1) / path_steps * (candidate -
+        current)``, s = 0..path_steps - 1 -- the last is the candidate itself; without ``current_qpos``, the candidates."""
+        q = np.atleast_2d(np.asarray(qposes.detach().cpu() if torch.is_tensor(qposes) else qposes, dtype=np.float64))
+        qp = np.zeros((q.shape[0], self.J))
+        qp[:, :min(self.J, q.shape[1])] = q[:, :self.J]
+        path_steps = int(path_steps)
+        if current_qpos is None:
+            if path_steps != 1:
+                raise ValueError("check: path_steps > 1 needs current_qpos")
+            return qp, 1
+        if path_steps < 1:
+            raise ValueError("check: path_steps must be >= 1")
+        c = np.asarray(current_qpos, dtype=np.float64).reshape(-1)
+        cur = np.zeros(self.J)
+        cur[:min(self.J, c.shape[0])] = c[:self.J]
+        frac = (np.arange(path_steps, dtype=np.float64) + 1.0) / path_steps
+        tab = cur[None, None, :] + frac[None, :, None] * (qp[:, None, :] - cur[None, None, :])
+        tab[:, -1] = qp                                  # (the candidate itself, not current + 1.0 * difference)
+        return np.ascontiguousarray(tab.reshape(-1, self.J)), path_steps
+
+    def kinematics(self, qpos_table):
+        """link_poses [n,L,4,4] float32 on the device of a host table [n,J]: one ``ehr_joint_forward`` at ``offsets``."""
+        dev, n = self.dev, int(qpos_table.shape[0])
+        qd = torch.from_numpy(np.ascontiguousarray(qpos_table, dtype=np.float64)).to(dev)
+        lp = torch.empty((n, self.L, 4, 4), device=dev)
+        jf = torch.empty((n, self.J, 6), device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ehr_joint_forward(*[_lib.ptr(t) for t in self._t], self._N, self.J, self.L, _lib.ptr(qd),
+                                                    _lib.ptr(self.offsets), n, _lib.ptr(lp), _lib.ptr(jf), _stream()),
+                       "ehr_joint_forward")
+        return lp
+
+    def clearance(self, link_poses):
+        """The kernel on link poses [n,L,4,4]: a namespace of ``self_clear``, ``self_pair``, ``env_clear``, ``reach_clear`` [n]."""
+        return config_clearance(link_poses, self._spheres, self.sphere_offsets, self._bounds, self._pair_enable, self._planes,
+                                self._obstacles, self.env_mask, self._reach, self.cutoff)
+
+    def check(self, qposes, current_qpos=None, path_steps=1):
+        """Judges candidates [Q, <= dof]; with ``current_qpos`` each at the ``path_steps`` configurations of the straight
+        joint-space segment towards it (:meth:`path_table`).  Kinematics, one clearance launch and a reduction over the steps
+        with torch on the device: nothing synchronises.  Returns a namespace of device tensors [Q]:
+
+        ``valid`` bool: ``self_clear > margin``, ``env_clear > margin`` and ``reach_clear >= 0`` at EVERY step (a NaN -- a
+        configuration the kernel could not judge -- is not valid); ``self_ok`` / ``env_ok`` / ``reach_ok``: the three parts;
+        ``self_clear`` / ``env_clear`` / ``reach_clear`` float64: the minimum over the steps (NaN if any step's is);
+        ``self_pair`` int32: the pair at the first step that attains ``self_clear`` (-1: none below cutoff, or NaN);
+        ``worst_step`` int64: the first step with the least slack ``min(self_clear - margin, env_clear - margin, reach_clear)``,
+        a NaN counting as the least."""
+        table, steps = self.path_table(qposes, current_qpos, path_steps)
+        Q = table.shape[0] // steps
+        raw = self.clearance(self.kinematics(table))
+        sc, ec, rc = (t.view(Q, steps) for t in (raw.self_clear, raw.env_clear, raw.reach_clear))
+        self_ok, env_ok, reach_ok = (sc > self.margin).all(dim=1), (ec > self.margin).all(dim=1), (rc >= 0).all(dim=1)
+        ar = torch.arange(steps, device=self.dev)[None].expand(Q, steps)
+
+        def first_min(x):                                # NaN counts as the least; the lowest step among equals
+            x = torch.where(torch.isnan(x), torch.full_like(x, -float("inf")), x)
+            return torch.where(x == x.amin(dim=1, keepdim=True), ar, steps).amin(dim=1)
+
+        slack = torch.minimum(torch.minimum(sc - self.margin, ec - self.margin), rc)   # (torch.minimum hands a NaN on)
+        at = first_min(sc)
+        pair = raw.self_pair.view(Q, steps).gather(1, at[:, None])[:, 0]
+        return types.SimpleNamespace(valid=self_ok & env_ok & reach_ok, self_ok=self_ok, env_ok=env_ok, reach_ok=reach_ok,
+                                     self_clear=sc.amin(dim=1), env_clear=ec.amin(dim=1), reach_clear=rc.amin(dim=1),
+                                     self_pair=pair, worst_step=first_min(slack))

@@ -24,16 +24,21 @@ __all__ = ["OnlineCalibration"]
 
 class OnlineCalibration:
     def __init__(self, robot, K, H, W, init_Tc_c2b, capture, candidates, device="cuda:0", num_epochs=1000,
-                 explore_iters=5, sample=10, start=200, lr=0.003, seed=0, explore="variance"):
+                 explore_iters=5, sample=10, start=200, lr=0.003, seed=0, explore="variance", feasible=None):
         """capture(qpos) -> bool/float mask [H,W] of the robot as the camera sees it at that joint configuration;
         candidates(round) -> (qposes [Q,dof], valid [Q] bool or None): the joint configurations the planner would
         accept this round (space_explorer.py:98-150 decides that with pymp / SAPIEN in the reference).
         explore: "variance" (the reference's mask-variance score, ``SpaceExplorer``) or "information" (the log-det information
         gain of :class:`easyhec_amd.info_explorer.InformationExplorer`, built each round on that round's solve; it needs no
-        optimisation history, so ``sample`` and ``start`` are not used)."""
+        optimisation history, so ``sample`` and ``start`` are not used).
+        feasible: a :class:`easyhec_amd.feasibility.FeasibilityFilter`, or None.  With a filter, the callback's ``valid`` is
+        AND-ed with the filter's verdict on the candidates and on the straight joint-space segment from the last captured
+        configuration to each (``feasible.path_steps`` configurations, 1 by default), and the round's log record gains
+        ``rejected_self`` / ``rejected_env`` / ``rejected_reach``, the candidates each test turned down.  When it turns all of
+        them down, the explorers' "no valid qpos found" error is what the caller sees."""
         if explore not in ("variance", "information"):
             raise ValueError(f"explore={explore!r}: 'variance' or 'information'")
-        self.explore = explore
+        self.explore, self.feasible = explore, feasible
         self.robot, self.K, self.H, self.W = robot, np.asarray(K, dtype=np.float64), int(H), int(W)
         self.init_Tc_c2b = np.asarray(init_Tc_c2b, dtype=np.float64)
         self.capture, self.candidates = capture, candidates
@@ -76,6 +81,12 @@ class OnlineCalibration:
             rec = {"round": it, "frames": len(self.qposes), "mask_loss": float(loss), "solve_s": t1 - t0}
             if it + 1 < self.explore_iters:                               # explore_next_state (rbsolve_iter.py:263-275)
                 cand, valid = self.candidates(it)
+                rejected = {}
+                if self.feasible is not None:
+                    fc = self.feasible.check(cand, current_qpos=qpos, path_steps=self.feasible.path_steps or 1)
+                    ok = fc.valid.cpu().numpy()
+                    valid = ok if valid is None else (np.asarray(valid.cpu() if torch.is_tensor(valid) else valid) != 0) & ok
+                    rejected = {f"rejected_{k}": int((~getattr(fc, f"{k}_ok")).sum()) for k in ("self", "env", "reach")}
                 if self.explore == "information":
                     out = InformationExplorer(trainer.fast, robot=self.robot).forward(cand, valid=valid)
                     scores = {"info_gain": float(out["gain"]), "gain_mean": float(out["gain_mean"])}
@@ -85,6 +96,6 @@ class OnlineCalibration:
                     scores = {"variance": float(out["variance"]), "var_mean": float(out["var_mean"])}
                 torch.cuda.synchronize(self.device)
                 qpos = np.asarray(out["qpos"], dtype=np.float64)
-                rec.update(explore_s=time.perf_counter() - t1, **scores, candidates=int(len(cand)))
+                rec.update(explore_s=time.perf_counter() - t1, **scores, candidates=int(len(cand)), **rejected)
             self.log.append(rec)
         return self.model.Tc_c2b().detach().cpu().numpy()

@@ -9,7 +9,8 @@ here it is one call of ``ehr_mask_variance`` (include/ehr.h), which returns the 
 
 Motion planning, self-collision and workspace checks of the reference (pymp / SAPIEN, space_explorer.py:104-150) are
 out of scope: pass their outcome as ``valid`` and rejected candidates score 0 exactly as the reference's
-``variances.append(0)`` does."""
+``variances.append(0)`` does.  (A conservative stand-in for the collision and workspace checks, on sphere proxies:
+``easyhec_amd.feasibility.FeasibilityFilter.check(...).valid``.)"""
 import ctypes
 
 import numpy as np

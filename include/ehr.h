@@ -841,6 +841,44 @@ int ehr_information_gain(const double* A, const double* info, const int32_t* val
 int ehr_information_pick(const double* gain, const double* info, int Q, int S, int N, double scale, int round, double* A,
                          int32_t* taken, int32_t* picked, double* picked_gain, void* stream);
 
+/* Feasibility of candidate joint configurations on sphere proxies (easyhec_amd/feasibility.py, csrc/ehr_feasible.hip): the
+ * clearance of every configuration against itself, against planes and obstacle spheres, and inside a ball of allowed reach.
+ * Static and conservative: where the proxy spheres cover the meshes, clear spheres mean clear meshes.  Device pointers but for
+ * sphere_offsets, a HOST array that travels in the kernel's arguments (it sizes the launch's LDS and is checked here, with no
+ * read-back); never allocates or synchronises, no atomics; one launch on `stream`.
+ *   link_poses [n,L,16] float32 as ehr_joint_forward writes them; spheres [S,4] float64 = link-frame centre and radius, the
+ *   links concatenated, link l's being sphere_offsets[l] .. sphere_offsets[l+1] ([L+1] int32 on the HOST, ascending from 0 to S);
+ *   link_bounds [L,4] float64 = one link-frame sphere per link that CONTAINS every sphere of the link (used for culling only);
+ *   pair_enable [L] uint32: bit j of word i (j > i) = link pair (i,j) is checked; planes [Np,4] float64 (n, d): n.x + d >= 0 is
+ *   inside, n of unit length (a longer one would let a link's bound cull what it should not), Np <= EHR_FEAS_MAX_PLANES (may be NULL when 0); obstacles [No,4] float64 spheres in the base frame, No <=
+ *   EHR_FEAS_MAX_OBSTACLES (may be NULL when 0); env_links: bit l = link l is tested against planes and obstacles; reach [4]
+ *   float64 = centre o and radius R of the allowed ball, or NULL.
+ * Arithmetic: float64 throughout, every operation rounded on its own (no contraction), the pose entries widened to double:
+ *   world centre     c_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k          (k = 0..2; the sphere keeps its radius)
+ *   sphere / sphere  sqrt((dx dx + dy dy) + dz dz) - (r_a + r_b)       (also sphere / obstacle; d = c_a - c_b)
+ *   plane            (((n_x c_x + n_y c_y) + n_z c_z) + d) - r
+ *   reach            R - (sqrt((dx dx + dy dy) + dz dz) + r)           (d = c - o)
+ * Outputs, [n] each: self_clear = min(cutoff, min over the sphere pairs of every enabled link pair); env_clear = min(cutoff,
+ * min over planes and obstacles for the spheres of the links in env_links); reach_clear = min(cutoff, min over all spheres),
+ * cutoff where reach is NULL; self_pair = 32 i + j of the lowest-numbered enabled pair that attains self_clear, -1 where nothing
+ * lies below cutoff.  No pairs, no planes and obstacles, or no spheres: cutoff.  min is exact in any order: the results do not
+ * depend on the reduction's shape.  A configuration with a pose entry that is not finite gets NaN in all three clearances and
+ * self_pair -1 (a filter that cannot judge must not pass), and leaves its neighbours untouched.  A link pair, or a link against
+ * a plane or an obstacle, is skipped through link_bounds only where the bound exceeds cutoff + 1e-6: rounding in the bound
+ * never changes an output.  Refused (EHR_ERR_INVALID): L outside 1..EHR_FEAS_MAX_LINKS, S > EHR_FEAS_MAX_SPHERES, n < 1, n_planes
+ * or n_obstacles out of range, offsets that do not ascend from 0, cutoff not finite or <= 0, and a device whose LDS cannot hold
+ * the S spheres (32 bytes each).  The spheres, bounds, planes and obstacles are device memory: finite values are the caller's
+ * to ensure (a NaN among them is ignored by the minimum, not reported).
+ * ehr_version() is unchanged: the presence of the symbol is the capability check. */
+#define EHR_FEAS_MAX_LINKS 32
+#define EHR_FEAS_MAX_SPHERES 4096
+#define EHR_FEAS_MAX_PLANES 16
+#define EHR_FEAS_MAX_OBSTACLES 1024
+int ehr_config_clearance(const float* link_poses, const double* spheres, const int32_t* sphere_offsets, const double* link_bounds,
+                         const uint32_t* pair_enable, const double* planes, int n_planes, const double* obstacles,
+                         int n_obstacles, uint32_t env_links, const double* reach, double cutoff, int n, int L,
+                         double* self_clear, int32_t* self_pair, double* env_clear, double* reach_clear, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
