@@ -28,7 +28,7 @@ def __getattr__(name):
         from . import info_explorer
         return getattr(info_explorer, name)
     # the feasibility filter in front of the explorers' scoring (easyhec_amd/feasibility.py), likewise
-    if name in ("FeasibilityFilter", "link_spheres", "box_planes", "config_clearance"):
+    if name in ("FeasibilityFilter", "link_spheres", "box_planes", "config_clearance", "robot_triangles", "mesh_clearance"):
         from . import feasibility
         return getattr(feasibility, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -110,6 +110,8 @@ SIGNATURES = {
     "ehr_information_pick": (c_int, [c_void_p] * 2 + [c_int] * 3 + [ctypes.c_double, c_int] + [c_void_p] * 5),
     "ehr_config_clearance": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, ctypes.c_double] +
                              [c_int] * 2 + [c_void_p] * 5),
+    "ehr_mesh_clearance": (c_int, [c_void_p] * 6 + [c_int, c_void_p, c_int, ctypes.c_uint32, ctypes.c_double] + [c_int] * 2 +
+                           [c_void_p] * 2 + [c_int] + [c_void_p] * 5),
 }
 
 
@@ -206,8 +208,13 @@ def has_feasibility():
     return has_symbols("ehr_config_clearance")
 
 
+def has_mesh_clearance():
+    return has_symbols("ehr_mesh_clearance")
+
+
 IG_MAX_PARAMS = 32  # include/ehr.h: EHR_IG_MAX_PARAMS
 FEAS_MAX_LINKS, FEAS_MAX_SPHERES, FEAS_MAX_PLANES, FEAS_MAX_OBSTACLES = 32, 4096, 16, 1024  # include/ehr.h: EHR_FEAS_*
+MESH_MAX_TRIANGLES = 1048576  # include/ehr.h: EHR_MESH_MAX_TRIANGLES
 
 
 # the state block of ehr_lm_update (include/ehr.h: EHR_LM_*), in float64 words

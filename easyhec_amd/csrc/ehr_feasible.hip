@@ -11,18 +11,11 @@
 // -ffp-contract=off, so a product is rounded before it is added, as numpy evaluates tests/feasibility_reference.py).  A minimum
 // is exact in any order: the result does not depend on how the pairs are dealt to the threads.  No atomics, no allocation, no
 // synchronisation with the host.
-#include <math.h>
-
-#include "ehr_host.h"
+#include "ehr_feas_core.h"  // FeasOffsets, FEAS_CULL_SLACK and the expressions shared with ehr_mesh_clearance.hip (feas_*)
 
 #define FEAS_THREADS 256
-#define FEAS_CULL_SLACK 1e-6  // a bound must exceed cutoff by this much before it culls: its own rounding never decides
 
 namespace ehr {
-
-struct FeasOffsets {  // sphere_offsets, by value in the kernel's arguments
-    int v[EHR_FEAS_MAX_LINKS + 1];
-};
 
 // LDS of one workgroup, all of it in the dynamic region and every part a multiple of 16 bytes: x | y | z | r of the Sp = S
 // rounded up to even spheres, then the fixed tail below
@@ -32,22 +25,6 @@ struct FeasOffsets {  // sphere_offsets, by value in the kernel's arguments
 #define FEAS_TAIL_BYTES ((FEAS_TAIL_BOUNDS + FEAS_TAIL_RED) * 8 + FEAS_TAIL_INTS * 4 + EHR_FEAS_MAX_OBSTACLES)
 static inline size_t feas_lds_bytes(int Sp) { return (size_t)Sp * 32 + FEAS_TAIL_BYTES; }
 
-__device__ __forceinline__ bool feas_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }  // (NaN: false)
-__device__ __forceinline__ double feas_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// ---- the contract's expressions ---------------------------------------------------------------------------------------------
-// row k of a pose applied to a link-frame point: ((R_k0 x + R_k1 y) + R_k2 z) + t_k
-__device__ __forceinline__ double feas_world(const float* __restrict__ row, double x, double y, double z) {
-    return (((double)row[0] * x + (double)row[1] * y) + (double)row[2] * z) + (double)row[3];
-}
-__device__ __forceinline__ double feas_norm2(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
-// sphere against sphere or obstacle
-__device__ __forceinline__ double feas_gap(double dx, double dy, double dz, double ra, double rb) {
-    return sqrt(feas_norm2(dx, dy, dz)) - (ra + rb);
-}
-__device__ __forceinline__ double feas_plane(double nx, double ny, double nz, double d, double cx, double cy, double cz, double r) {
-    return (((nx * cx + ny * cy) + nz * cz) + d) - r;
-}
 __device__ __forceinline__ double feas_reach(double R, double dx, double dy, double dz, double r) {
     return R - (sqrt(feas_norm2(dx, dy, dz)) + r);
 }

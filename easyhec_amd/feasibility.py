@@ -11,9 +11,13 @@ a maximum-distance constraint over the links, a workspace-boundary point cloud).
     FeasibilityFilter the robot's proxies, the link pairs worth checking, the environment (half-spaces, obstacle spheres, a
                       ball of allowed reach) and ``check``: candidates (and the straight joint-space segment from the current
                       configuration to each) -> ``valid`` and the clearances, device tensors, with no host synchronisation
+    robot_triangles   the triangles every proxy sphere stands for, in the spheres' order
+    mesh_clearance    one ``ehr_mesh_clearance`` launch (csrc/ehr_mesh_clearance.hip; DESIGN.md section 6t, INTEGRATION.md
+                      4a-14): the exact distance between the meshes behind the proxies, and of the meshes to planes and
+                      obstacles.  ``FeasibilityFilter(exact=True)`` judges self and environment clearance with it.
 
-What it is NOT: a mesh-exact collision test, or a planner -- the straight segment is sampled at ``path_steps`` configurations,
-nothing is searched or timed.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
+What it is NOT: a planner -- the straight segment is sampled at ``path_steps`` configurations, nothing is searched or timed; and,
+without ``exact=True``, a mesh-exact collision test.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
 not covered.  HIP only; no fallback."""
 import ctypes
 import types
@@ -24,13 +28,17 @@ import torch
 from . import _lib, dr
 
 __all__ = ["link_spheres", "link_bound", "box_planes", "robot_proxies", "enabled_pairs", "config_clearance",
-           "FeasibilityFilter", "REFERENCE_WORKSPACE"]
+           "leaf_mesh", "robot_triangles", "mesh_clearance", "FeasibilityFilter", "REFERENCE_WORKSPACE"]
 
 REFERENCE_WORKSPACE = ((-0.2, -0.5, -0.5), (1.0, 0.5, 1.0))  # the reference's workspace box (workspace_boundary.py:9)
 
 
 def _missing():
     raise RuntimeError("this libehr_hip.so has no feasibility kernel (ehr_config_clearance): rebuild it")
+
+
+def _missing_mesh():
+    raise RuntimeError("this libehr_hip.so has no mesh clearance kernel (ehr_mesh_clearance): rebuild it")
 
 
 # ---- proxy geometry (host, once per robot) --------------------------------------------------------------------------------
@@ -115,6 +123,27 @@ def robot_proxies(robot, leaf_triangles=64):
     spheres = np.concatenate(per_link) if per_link else np.zeros((0, 4))
     bounds = np.stack([link_bound(v, s) for (v, _), s in zip(robot.meshes, per_link)])
     return np.ascontiguousarray(spheres, dtype=np.float64), offsets, bounds
+
+
+def leaf_mesh(vertices, faces, leaf_triangles=64):
+    """(spheres [S,4], triangles [T,9] float64, counts [S] int64) of one link: :func:`link_spheres` and the link-frame corner
+    coordinates of the triangles, reordered so that those of sphere s follow those of sphere s - 1 (``counts`` of them each)."""
+    spheres, leaves = link_spheres(vertices, faces, leaf_triangles, return_leaves=True)
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    order = np.concatenate(leaves) if leaves else np.zeros(0, dtype=np.int64)
+    return spheres, np.ascontiguousarray(v[f[order]].reshape(-1, 9)), np.array([len(i) for i in leaves], dtype=np.int64)
+
+
+def robot_triangles(robot, leaf_triangles=64):
+    """(triangles [T,9] float64, tri_offsets [S+1] int32) of the robot's rendered links: the triangles of proxy sphere s of
+    :func:`robot_proxies` (same ``leaf_triangles``) are ``tri_offsets[s] .. tri_offsets[s+1]``."""
+    per_link = [leaf_mesh(v, f, leaf_triangles) for v, f in robot.meshes]
+    counts = np.concatenate([c for _, _, c in per_link] + [np.zeros(0, dtype=np.int64)])
+    offsets = np.zeros(counts.shape[0] + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(counts)
+    tri = np.concatenate([t for _, t, _ in per_link]) if per_link else np.zeros((0, 9))
+    return np.ascontiguousarray(tri, dtype=np.float64), offsets
 
 
 def _world_spheres(link_poses, spheres, offsets):
@@ -276,6 +305,55 @@ def config_clearance(link_poses, spheres, sphere_offsets, link_bounds, pair_enab
     return out
 
 
+def mesh_clearance(link_poses, spheres, sphere_offsets, link_bounds, pair_enable, triangles, tri_offsets, planes=None,
+                   obstacles=None, env_links=0, cutoff=0.02):
+    """One ``ehr_mesh_clearance`` launch (include/ehr.h).  Device tensors as :func:`config_clearance`'s, and triangles [T,9]
+    float64, tri_offsets [S+1] int32 (:func:`robot_triangles`); ``sphere_offsets`` [L+1]: a HOST array.  Returns a namespace of
+    device tensors: ``mesh_clear``, ``env_clear`` float64 [n], ``mesh_pair`` int32 [n], ``mesh_tri`` int32 [n,2].  Never
+    synchronises; the sizes' limits are the library's to refuse."""
+    if not _lib.has_mesh_clearance():
+        _missing_mesh()
+    dr._check_dev("link_poses", link_poses, torch.float32)
+    dev = link_poses.device
+    dr._require(link_poses.dim() == 4 and tuple(link_poses.shape[2:]) == (4, 4), "link_poses must have shape [n, L, 4, 4]")
+    n, L = int(link_poses.shape[0]), int(link_poses.shape[1])
+    off = np.ascontiguousarray(np.asarray(sphere_offsets), dtype=np.int32)
+    dr._require(off.shape == (L + 1,), "sphere_offsets must be a host array of L + 1 entries")
+    S = max(int(off[-1]), 0)
+
+    def f64(name, t, rows, cols=4):
+        if t is None:
+            return None
+        dr._check_dev(name, t, torch.float64)
+        dr._require(t.device == dev and t.dim() == 2 and t.shape[1] == cols and t.shape[0] >= rows,
+                    f"{name} must have shape [{rows}, {cols}]")
+        return t.contiguous()
+
+    spheres, link_bounds = f64("spheres", spheres, S), f64("link_bounds", link_bounds, L)
+    planes, obstacles = f64("planes", planes, 0), f64("obstacles", obstacles, 0)
+    triangles = f64("triangles", triangles, 0, 9)
+    dr._check_dev("pair_enable", pair_enable, torch.int32)
+    dr._require(pair_enable.device == dev and pair_enable.shape == (L,), "pair_enable must have shape [L]")
+    dr._check_dev("tri_offsets", tri_offsets, torch.int32)
+    dr._require(tri_offsets.device == dev and tri_offsets.dim() == 1 and tri_offsets.shape[0] >= S + 1,
+                "tri_offsets must have S + 1 entries")
+    out = types.SimpleNamespace(mesh_clear=torch.empty((n,), dtype=torch.float64, device=dev),
+                                mesh_pair=torch.empty((n,), dtype=torch.int32, device=dev),
+                                mesh_tri=torch.empty((n, 2), dtype=torch.int32, device=dev),
+                                env_clear=torch.empty((n,), dtype=torch.float64, device=dev))
+    Np = 0 if planes is None else int(planes.shape[0])
+    No = 0 if obstacles is None else int(obstacles.shape[0])
+    T = int(triangles.shape[0])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ehr_mesh_clearance(
+            _lib.ptr(link_poses.contiguous()), _lib.ptr(spheres), off.ctypes.data_as(ctypes.c_void_p), _lib.ptr(link_bounds),
+            _lib.ptr(pair_enable.contiguous()), _lib.ptr(planes) if Np else None, Np, _lib.ptr(obstacles) if No else None, No,
+            int(env_links) & 0xffffffff, float(cutoff), n, L, _lib.ptr(triangles) if T else None, _lib.ptr(tri_offsets.contiguous()),
+            T, _lib.ptr(out.mesh_clear), _lib.ptr(out.mesh_pair), _lib.ptr(out.mesh_tri), _lib.ptr(out.env_clear), _stream()),
+            "ehr_mesh_clearance")
+    return out
+
+
 # ---- the filter -------------------------------------------------------------------------------------------------------------
 def _rows4(a, name, limit):
     if a is None:
@@ -299,13 +377,25 @@ class FeasibilityFilter:
     an array, or a solve step's current offsets tensor (read on every call).  path_steps: what an online loop passes to
     :meth:`check` (None: 1).
 
-    ``pairs``: the enabled link pairs; ``ignored``: the others with reason and settle clearance."""
+    exact: judge the arm against itself and against planes and obstacles on the MESHES behind the proxies
+    (:func:`mesh_clearance`); reach stays on the proxies.  The proxies remain the broad phase, so nothing they clear is looked
+    at again.  exact_cutoff: mesh clearances are reported up to this value [m] (default ``max(2 margin, 0.02)``: only "above
+    margin or not" is needed, and a short cutoff is what lets the kernel skip most of the meshes).
+
+    ``pairs``: the enabled link pairs; ``ignored``: the others with reason and settle clearance.  With ``exact``, ``mesh_pairs``
+    is what the mesh kernel checks: ``pairs`` and every "settle"-ignored pair whose MESHES keep more than ``margin`` at the
+    settle configuration (the proxies touched there, the links do not); ``ignored`` then holds the rest, the "settle" entries
+    with their ``mesh_clearance``."""
 
     def __init__(self, robot, leaf_triangles=64, margin=0.01, ignore_pairs="auto", settle_qpos=None, planes=None,
-                 obstacles=None, env_links=None, reach=None, cutoff=0.25, offsets=None, device="cuda:0", path_steps=None):
+                 obstacles=None, env_links=None, reach=None, cutoff=0.25, offsets=None, device="cuda:0", path_steps=None,
+                 exact=False, exact_cutoff=None):
         from .joint_calib import _check_table
         if not _lib.has_feasibility():
             _missing()
+        self.exact = bool(exact)
+        if self.exact and not _lib.has_mesh_clearance():
+            _missing_mesh()
         if not (np.isfinite(cutoff) and cutoff > 0 and np.isfinite(margin) and 0 <= margin < cutoff):
             raise ValueError(f"FeasibilityFilter: need 0 <= margin < cutoff, finite (margin {margin}, cutoff {cutoff})")
         self.robot, self.margin, self.cutoff = robot, float(margin), float(cutoff)
@@ -354,6 +444,39 @@ class FeasibilityFilter:
                                                       dtype=np.float32)).to(dev)
         if tuple(self.offsets.shape) != (self.J,) or not self.offsets.is_contiguous():
             raise ValueError(f"offsets must be a contiguous [{self.J}] tensor")
+        if self.exact:
+            self._init_exact(leaf_triangles, exact_cutoff, settle_qpos)
+
+    def _init_exact(self, leaf_triangles, exact_cutoff, settle_qpos):
+        """The triangles behind the proxies and ``mesh_pairs``: one launch per "settle"-ignored pair, that pair alone enabled,
+        at the settle configuration(s) (the host's kinematics, as :func:`enabled_pairs` uses)."""
+        self.exact_cutoff = max(2.0 * self.margin, 0.02) if exact_cutoff is None else float(exact_cutoff)
+        if not (np.isfinite(self.exact_cutoff) and self.margin < self.exact_cutoff):
+            raise ValueError(f"FeasibilityFilter: need margin < exact_cutoff, finite (margin {self.margin}, exact_cutoff "
+                             f"{self.exact_cutoff})")
+        self.triangles, self.tri_offsets = robot_triangles(self.robot, leaf_triangles)
+        if self.triangles.shape[0] > _lib.MESH_MAX_TRIANGLES:
+            raise ValueError(f"FeasibilityFilter: {self.triangles.shape[0]} triangles; the kernel takes {_lib.MESH_MAX_TRIANGLES}")
+        dev = self.dev
+        self._triangles = torch.from_numpy(self.triangles).to(dev)
+        self._tri_offsets = torch.from_numpy(self.tri_offsets).to(dev)
+        self._pair_none = torch.zeros((self.L,), dtype=torch.int32, device=dev)
+        q0 = np.zeros((1, self.J)) if settle_qpos is None else np.atleast_2d(np.asarray(settle_qpos, dtype=np.float64))
+        lp = torch.from_numpy(np.ascontiguousarray(self.robot.link_poses_batch(q0), dtype=np.float32)).to(dev)
+        self.mesh_pairs, rest = list(self.pairs), []
+        for d in self.ignored:
+            if d["reason"] == "settle":
+                words = torch.from_numpy(pair_words([d["pair"]], self.L).view(np.int32)).to(dev)
+                clear = float(mesh_clearance(lp, self._spheres, self.sphere_offsets, self._bounds, words, self._triangles,
+                                             self._tri_offsets, cutoff=self.exact_cutoff).mesh_clear.min().cpu())
+                if clear > self.margin:
+                    self.mesh_pairs.append(d["pair"])
+                    continue
+                d = dict(d, mesh_clearance=clear)
+            rest.append(d)
+        self.mesh_pairs.sort()
+        self.ignored = rest
+        self._mesh_enable = torch.from_numpy(pair_words(self.mesh_pairs, self.L).view(np.int32)).to(dev)
 
     # -- the parts ----------------------------------------------------------------------------------------------------------
     def path_table(self, qposes, current_qpos=None, path_steps=1):
@@ -394,6 +517,14 @@ class FeasibilityFilter:
         return config_clearance(link_poses, self._spheres, self.sphere_offsets, self._bounds, self._pair_enable, self._planes,
                                 self._obstacles, self.env_mask, self._reach, self.cutoff)
 
+    def mesh_clearance(self, link_poses):
+        """The mesh kernel on link poses [n,L,4,4] (``exact=True`` only): a namespace of ``mesh_clear``, ``mesh_pair``,
+        ``mesh_tri``, ``env_clear``, over ``mesh_pairs`` and up to ``exact_cutoff``."""
+        if not self.exact:
+            raise RuntimeError("FeasibilityFilter.mesh_clearance: the filter was built with exact=False")
+        return mesh_clearance(link_poses, self._spheres, self.sphere_offsets, self._bounds, self._mesh_enable, self._triangles,
+                              self._tri_offsets, self._planes, self._obstacles, self.env_mask, self.exact_cutoff)
+
     def check(self, qposes, current_qpos=None, path_steps=1):
         """Judges candidates [Q, <= dof]; with ``current_qpos`` each at the ``path_steps`` configurations of the straight
         joint-space segment towards it (:meth:`path_table`).  Kinematics, one clearance launch and a reduction over the steps
@@ -404,10 +535,22 @@ class FeasibilityFilter:
         ``self_clear`` / ``env_clear`` / ``reach_clear`` float64: the minimum over the steps (NaN if any step's is);
         ``self_pair`` int32: the pair at the first step that attains ``self_clear`` (-1: none below cutoff, or NaN);
         ``worst_step`` int64: the first step with the least slack ``min(self_clear - margin, env_clear - margin, reach_clear)``,
-        a NaN counting as the least."""
+        a NaN counting as the least.
+
+        With ``exact=True`` the kinematics run once, the proxy kernel gives ``reach_clear`` and the mesh kernel the other two:
+        ``self_clear`` and ``env_clear`` are then distances of the meshes, reported up to ``exact_cutoff``, ``self_pair`` a
+        pair of ``mesh_pairs`` that attains ``self_clear``, and the result gains ``mesh_pair`` (the same) and ``mesh_tri``
+        int32 [Q,2], a triangle pair (rows of ``triangles``) that attains it, of the same step."""
         table, steps = self.path_table(qposes, current_qpos, path_steps)
         Q = table.shape[0] // steps
-        raw = self.clearance(self.kinematics(table))
+        lp = self.kinematics(table)
+        if self.exact:
+            mesh = self.mesh_clearance(lp)
+            raw = config_clearance(lp, self._spheres, self.sphere_offsets, self._bounds, self._pair_none, None, None, 0,
+                                   self._reach, self.cutoff)
+            raw.self_clear, raw.self_pair, raw.env_clear = mesh.mesh_clear, mesh.mesh_pair, mesh.env_clear
+        else:
+            raw = self.clearance(lp)
         sc, ec, rc = (t.view(Q, steps) for t in (raw.self_clear, raw.env_clear, raw.reach_clear))
         self_ok, env_ok, reach_ok = (sc > self.margin).all(dim=1), (ec > self.margin).all(dim=1), (rc >= 0).all(dim=1)
         ar = torch.arange(steps, device=self.dev)[None].expand(Q, steps)
@@ -419,6 +562,10 @@ class FeasibilityFilter:
         slack = torch.minimum(torch.minimum(sc - self.margin, ec - self.margin), rc)   # (torch.minimum hands a NaN on)
         at = first_min(sc)
         pair = raw.self_pair.view(Q, steps).gather(1, at[:, None])[:, 0]
-        return types.SimpleNamespace(valid=self_ok & env_ok & reach_ok, self_ok=self_ok, env_ok=env_ok, reach_ok=reach_ok,
-                                     self_clear=sc.amin(dim=1), env_clear=ec.amin(dim=1), reach_clear=rc.amin(dim=1),
-                                     self_pair=pair, worst_step=first_min(slack))
+        out = types.SimpleNamespace(valid=self_ok & env_ok & reach_ok, self_ok=self_ok, env_ok=env_ok, reach_ok=reach_ok,
+                                    self_clear=sc.amin(dim=1), env_clear=ec.amin(dim=1), reach_clear=rc.amin(dim=1),
+                                    self_pair=pair, worst_step=first_min(slack))
+        if self.exact:
+            out.mesh_pair = pair
+            out.mesh_tri = mesh.mesh_tri.view(Q, steps, 2).gather(1, at[:, None, None].expand(Q, 1, 2))[:, 0]
+        return out

@@ -34,7 +34,8 @@ class OnlineCalibration:
         feasible: a :class:`easyhec_amd.feasibility.FeasibilityFilter`, or None.  With a filter, the callback's ``valid`` is
         AND-ed with the filter's verdict on the candidates and on the straight joint-space segment from the last captured
         configuration to each (``feasible.path_steps`` configurations, 1 by default), and the round's log record gains
-        ``rejected_self`` / ``rejected_env`` / ``rejected_reach``, the candidates each test turned down.  When it turns all of
+        ``rejected_self`` / ``rejected_env`` / ``rejected_reach``, the candidates each test turned down (and, for a filter
+        built with ``exact=True``, ``rejected_mode = "exact"``: the meshes turned them down, not the proxies).  When it turns all of
         them down, the explorers' "no valid qpos found" error is what the caller sees."""
         if explore not in ("variance", "information"):
             raise ValueError(f"explore={explore!r}: 'variance' or 'information'")
@@ -87,6 +88,8 @@ class OnlineCalibration:
                     ok = fc.valid.cpu().numpy()
                     valid = ok if valid is None else (np.asarray(valid.cpu() if torch.is_tensor(valid) else valid) != 0) & ok
                     rejected = {f"rejected_{k}": int((~getattr(fc, f"{k}_ok")).sum()) for k in ("self", "env", "reach")}
+                    if getattr(self.feasible, "exact", False):            # (a proxy filter's record keeps today's keys)
+                        rejected["rejected_mode"] = "exact"
                 if self.explore == "information":
                     out = InformationExplorer(trainer.fast, robot=self.robot).forward(cand, valid=valid)
                     scores = {"info_gain": float(out["gain"]), "gain_mean": float(out["gain_mean"])}

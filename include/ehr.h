@@ -879,6 +879,67 @@ int ehr_config_clearance(const float* link_poses, const double* spheres, const i
                          int n_obstacles, uint32_t env_links, const double* reach, double cutoff, int n, int L,
                          double* self_clear, int32_t* self_pair, double* env_clear, double* reach_clear, void* stream);
 
+/* The meshes behind the sphere proxies (easyhec_amd/feasibility.py, csrc/ehr_mesh_clearance.hip): per configuration the exact
+ * distance between the triangle meshes of the enabled link pairs, and of the meshes to planes and obstacle spheres.  The proxy
+ * spheres are the broad phase, the triangles each of them stands for the narrow one.  Inputs as ehr_config_clearance's (the
+ * same limits; no reach), device pointers but for sphere_offsets, and
+ *   triangles [T,9] float64: link-frame corner coordinates (x y z of corner 0, 1, 2), ordered so that the triangles of proxy
+ *   sphere s are tri_offsets[s] .. tri_offsets[s+1]; tri_offsets [S+1] int32 on the DEVICE, ascending from 0 to T (nobody reads
+ *   it back: the kernel clamps every range into 0..T, so a wrong table gives wrong answers, not wild reads); T <=
+ *   EHR_MESH_MAX_TRIANGLES; pair_enable as above, the MESH pair list.  Every triangle of sphere s must lie inside that sphere,
+ *   and every sphere of a link inside link_bounds: they cull.
+ * Arithmetic: float64 throughout, every operation rounded on its own, division and square root correctly rounded, the pose
+ * entries widened to double.  With u.v = (u_x v_x + u_y v_y) + u_z v_z, u x v = (u_y v_z - u_z v_y, u_z v_x - u_x v_z,
+ * u_x v_y - u_y v_x), |u|^2 = (u_x u_x + u_y u_y) + u_z u_z, clamp(x) = 0 if x < 0, 1 if x > 1, else x, and ratio(p, q) = p / q
+ * if q > 0, else 0 (the exact-zero test of a zero-length edge or a zero-area triangle: nothing divides by 0, no epsilon):
+ *   world corner      w_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k                        (as a sphere's centre)
+ *   point / segment   P(p; a,b): ab = b - a, e = ab.ab, t = clamp((p - a).ab / e) if e > 0 else 0, q = a + ab t (per
+ *                     coordinate a_x + ab_x t); |p - q|^2
+ *   point / triangle  D(p; a,b,c): ab = b - a, ac = c - a, n = ab x ac.  If not n.n > 0 (zero area): min(P(p;a,b), P(p;b,c),
+ *                     P(p;c,a)).  Else with ap = p - a, bp = p - b, cp = p - c, d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp,
+ *                     d5 = ab.cp, d6 = ac.cp, vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, the first that holds of
+ *                       d1 <= 0 and d2 <= 0                        (v, w) = (0, 0)
+ *                       d3 >= 0 and d4 <= d3                       (1, 0)
+ *                       vc <= 0 and d1 >= 0 and d3 <= 0            (ratio(d1, d1 - d3), 0)
+ *                       d6 >= 0 and d5 <= d6                       (0, 1)
+ *                       vb <= 0 and d2 >= 0 and d6 <= 0            (0, ratio(d2, d2 - d6))
+ *                       va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0  w = ratio(d4 - d3, (d4 - d3) + (d5 - d6)), v = 1 - w
+ *                       otherwise (the face)                       s = (va + vb) + vc, (ratio(vb, s), ratio(vc, s))
+ *                     q = (a + ab v) + ac w per coordinate; |p - q|^2
+ *   segment / segment E(p1,q1; p2,q2): d1 = q1 - p1, d2 = q2 - p2, r = p1 - p2, a = d1.d1, e = d2.d2, f = d2.r, c = d1.r,
+ *                     b = d1.d2.  If a > 0 and e > 0: den = a e - b b, s = clamp((b f - c e) / den) if den > 0 else 0,
+ *                     t = (b s + f) / e; if t < 0: t = 0, s = clamp(-c / a); else if t > 1: t = 1, s = clamp((b - c) / a).
+ *                     Else if a > 0: t = 0, s = clamp(-c / a); else if e > 0: s = 0, t = clamp(f / e); else s = t = 0.
+ *                     |(p1 + d1 s) - (p2 + d2 t)|^2
+ *   piercing          X(p,q; a,b,c): n = (b - a) x (c - a), sp = n.(p - a), sq = n.(q - a); false unless (sp > 0 and sq < 0) or
+ *                     (sp < 0 and sq > 0); with d = q - p, pa = a - p, pb = b - p, pc = c - p, u = d.(pa x pb), v = d.(pb x pc),
+ *                     w = d.(pc x pa): true iff u, v, w are all >= 0 or all <= 0.  (A zero-area triangle has n = 0 and is never
+ *                     pierced; its own edges still pierce.)
+ *   triangle pair     0 if X holds for any of the three edges of one against the other (six tests); else the minimum of D of
+ *                     each corner against the other triangle (six) and E of each edge pair (nine; edge k runs from corner k to
+ *                     corner (k + 1) mod 3).  An edge through the middle of a large triangle is far from all fifteen.
+ *   plane             ((n_x w_x + n_y w_y) + n_z w_z) + d for a corner w;     obstacle   sqrt(D(centre; triangle)) - radius
+ * Outputs, [n] each (mesh_tri [n,2]): mesh_clear = min(cutoff, sqrt(the least triangle-pair value over all triangle pairs of
+ * all enabled link pairs)); mesh_pair = 32 i + j of A link pair that attains it and mesh_tri = A triangle pair (rows of
+ * `triangles`, of link i and of link j) that attains it -- not the lowest: among ties, the penetrating poses' many zeros
+ * included, any -- or -1 where nothing lies below cutoff; env_clear = min(cutoff, the least plane value over the corners and the
+ * least obstacle value over the triangles of the links in env_links).  A configuration with a pose entry that is not finite
+ * gets NaN clearances and -1 witnesses, and leaves its neighbours untouched.  Minima are exact in any order and what is culled
+ * lies above the result, so the clearances do not depend on how the work is dealt out: tests/mesh_clearance_reference.py
+ * restates the above in numpy and the kernel is compared bit for bit.  A leaf pair, a triangle against a leaf, a triangle pair, a
+ * leaf against a plane or an obstacle is skipped only where the gap of the spheres around the two exceeds the bar (cutoff, or
+ * the least distance found so far) by 1e-6, which covers the float32 pose being no exact rotation.
+ * One launch on `stream`; never allocates or synchronises; no atomics to global memory.  Refused (EHR_ERR_INVALID): the limits
+ * of ehr_config_clearance (L, S, n, planes, obstacles, sphere_offsets that do not ascend from 0, cutoff), T outside
+ * 0..EHR_MESH_MAX_TRIANGLES, NULL tensors.
+ * ehr_version() is unchanged: the presence of the symbol is the capability check. */
+#define EHR_MESH_MAX_TRIANGLES 1048576
+int ehr_mesh_clearance(const float* link_poses, const double* spheres, const int32_t* sphere_offsets, const double* link_bounds,
+                       const uint32_t* pair_enable, const double* planes, int n_planes, const double* obstacles, int n_obstacles,
+                       uint32_t env_links, double cutoff, int n, int L, const double* triangles, const int32_t* tri_offsets,
+                       int n_triangles, double* mesh_clear, int32_t* mesh_pair, int32_t* mesh_tri, double* env_clear,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@ the zero configuration; leaf_triangles 64, margin 0.01, the reference's workspac
 `--reps` host-clock windows that end in ONE device synchronise, after 3 warm-up runs, of
     the path table (host) | kinematics (upload + ehr_joint_forward) | the clearance kernel | check(), whole
 and, on the problem of tools/info_explorer_bench.py (4 frames at 640x360), `InformationExplorer.score` of the same candidates
-without a filter and with the filter's ``valid``.  Prints one JSON line."""
+without a filter and with the filter's ``valid``.  Then the same candidates through ``FeasibilityFilter(exact=True)``
+(``ehr_mesh_clearance``): the mesh kernel whole, its two phases alone (the arm against itself; planes), and
+``check()``.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -70,6 +72,26 @@ def main():
                      ("pose + six offsets", InformationExplorer(JointPoseStep(make(), batch, rb, qp)))):
         res[f"InformationExplorer.score, {name}"] = median_ms(lambda: ex.score(cand), a.reps, sync)
         res[f"InformationExplorer.score, {name}, the filter's valid"] = median_ms(lambda: ex.score(cand, valid), a.reps, sync)
+    # the meshes behind the proxies: the same candidates, path and box
+    ex = F.FeasibilityFilter(rb, leaf_triangles=64, margin=0.01, planes=F.box_planes((lo[0], lo[1], 0.0), hi), device=dev, exact=True)
+    res["exact: triangles"], res["exact: mesh pairs"], res["exact: cutoff"] = int(ex.triangles.shape[0]), len(ex.mesh_pairs), ex.exact_cutoff
+    lp = box["lp"]
+    none = torch.zeros((ex.L,), dtype=torch.int32, device=dev)
+    mesh = lambda pairs, planes, env: F.mesh_clearance(lp, ex._spheres, ex.sphere_offsets, ex._bounds, pairs, ex._triangles,
+                                                       ex._tri_offsets, planes, None, env, ex.exact_cutoff)
+    res["mesh kernel, whole"] = median_ms(lambda: ex.mesh_clearance(lp), a.reps, sync)
+    res["mesh kernel, the arm against itself alone"] = median_ms(lambda: mesh(ex._mesh_enable, None, 0), a.reps, sync)
+    res["mesh kernel, the planes alone"] = median_ms(lambda: mesh(none, ex._planes, ex.env_mask), a.reps, sync)
+    res["check(exact), whole"] = median_ms(lambda: ex.check(cand, current_qpos=cur, path_steps=a.path_steps), a.reps, sync)
+    res["check(exact), candidates alone"] = median_ms(lambda: ex.check(cand), a.reps, sync)
+    eo = ex.check(cand, current_qpos=cur, path_steps=a.path_steps)
+    res["exact: accepted"] = int(eo.valid.sum())
+    res["exact: rejected self / env / reach"] = [int((~getattr(eo, k)).sum()) for k in ("self_ok", "env_ok", "reach_ok")]
+    res["exact: accepted, candidates alone"] = int(ex.check(cand).valid.sum())
+    res["exact: accepted that the proxies reject"] = int((eo.valid.cpu().numpy() & ~valid).sum())
+    res["exact: rejected that the proxies accept"] = int((~eo.valid.cpu().numpy() & valid).sum())
+    raw = ex.mesh_clearance(lp)
+    res["exact: configurations at distance 0 / below cutoff"] = [int((raw.mesh_clear == 0).sum()), int((raw.mesh_clear < ex.exact_cutoff).sum())]
     print(json.dumps(res))
 
 
