@@ -11,7 +11,7 @@
 // -ffp-contract=off, so a product is rounded before it is added, as numpy evaluates tests/feasibility_reference.py).  A minimum
 // is exact in any order: the result does not depend on how the pairs are dealt to the threads.  No atomics, no allocation, no
 // synchronisation with the host.
-#include "ehr_feas_core.h"  // FeasOffsets, FEAS_CULL_SLACK and the expressions shared with ehr_mesh_clearance.hip (feas_*)
+#include "ehr_feas_core.h"  // FeasOffsets, FEAS_CULL_SLACK, the expressions (feas_*) and feas_to_base, shared with the siblings
 
 #define FEAS_THREADS 256
 
@@ -24,10 +24,6 @@ namespace ehr {
 #define FEAS_TAIL_INTS (FEAS_THREADS + 36)         // ints: the reduction's pair codes | the offsets (33, padded)
 #define FEAS_TAIL_BYTES ((FEAS_TAIL_BOUNDS + FEAS_TAIL_RED) * 8 + FEAS_TAIL_INTS * 4 + EHR_FEAS_MAX_OBSTACLES)
 static inline size_t feas_lds_bytes(int Sp) { return (size_t)Sp * 32 + FEAS_TAIL_BYTES; }
-
-__device__ __forceinline__ double feas_reach(double R, double dx, double dy, double dz, double r) {
-    return R - (sqrt(feas_norm2(dx, dy, dz)) + r);
-}
 
 __global__ void __launch_bounds__(FEAS_THREADS) config_clearance_kernel(
     const float* __restrict__ link_poses, const double* __restrict__ spheres, const FeasOffsets offs,
@@ -66,27 +62,7 @@ __global__ void __launch_bounds__(FEAS_THREADS) config_clearance_kernel(
     }
 
     // every sphere to the base frame, once
-    for (int s = tid; s < S; s += FEAS_THREADS) {
-        int lo = 0, hi = L;  // off[lo] <= s < off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (off[mid] <= s) lo = mid; else hi = mid;
-        }
-        const float* T = P + lo * 16;
-        const double x = spheres[4 * (size_t)s], y = spheres[4 * (size_t)s + 1], z = spheres[4 * (size_t)s + 2];
-        X[s] = feas_world(T, x, y, z);
-        Y[s] = feas_world(T + 4, x, y, z);
-        Z[s] = feas_world(T + 8, x, y, z);
-        Rr[s] = spheres[4 * (size_t)s + 3];
-    }
-    if (tid < L) {
-        const float* T = P + tid * 16;
-        const double x = link_bounds[4 * tid], y = link_bounds[4 * tid + 1], z = link_bounds[4 * tid + 2];
-        BW[4 * tid] = feas_world(T, x, y, z);
-        BW[4 * tid + 1] = feas_world(T + 4, x, y, z);
-        BW[4 * tid + 2] = feas_world(T + 8, x, y, z);
-        BW[4 * tid + 3] = link_bounds[4 * tid + 3];
-    }
+    feas_to_base<FEAS_THREADS>(P, spheres, off, link_bounds, L, S, X, Y, Z, Rr, BW);
     __syncthreads();
 
     // reach: every sphere inside the allowed ball
@@ -146,9 +122,7 @@ __global__ void __launch_bounds__(FEAS_THREADS) config_clearance_kernel(
         for (int j = i + 1; j < L; j++) {
             const int oj = off[j], nj = off[j + 1] - oj;
             if (!((m >> j) & 1u) || nj <= 0) continue;
-            if (feas_gap(BW[4 * i] - BW[4 * j], BW[4 * i + 1] - BW[4 * j + 1], BW[4 * i + 2] - BW[4 * j + 2], BW[4 * i + 3],
-                         BW[4 * j + 3]) > cull)
-                continue;
+            if (feas_bound_gap(BW, i, j) > cull) continue;
             const int code = 32 * i + j;
             const bool swap = nj < ni;
             const int a0 = swap ? oj : oi, na = swap ? nj : ni, b0 = swap ? oi : oj, nb = swap ? ni : nj;

@@ -15,9 +15,13 @@ a maximum-distance constraint over the links, a workspace-boundary point cloud).
     mesh_clearance    one ``ehr_mesh_clearance`` launch (csrc/ehr_mesh_clearance.hip; DESIGN.md section 6t, INTEGRATION.md
                       4a-14): the exact distance between the meshes behind the proxies, and of the meshes to planes and
                       obstacles.  ``FeasibilityFilter(exact=True)`` judges self and environment clearance with it.
+    segment_clearance one ``ehr_segment_clearance`` launch (csrc/ehr_segment_clearance.hip; DESIGN.md section 6u, INTEGRATION.md
+                      4a-15): a certificate that the proxies keep ``margin`` on the WHOLE segment to a candidate, or how far
+                      the move is certified and what stopped it.  ``FeasibilityFilter(swept=True).check_swept`` calls it;
+                      ``joint_below`` and ``reach_radii`` are its host tables.
 
-What it is NOT: a planner -- the straight segment is sampled at ``path_steps`` configurations, nothing is searched or timed; and,
-without ``exact=True``, a mesh-exact collision test.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
+What it is NOT: a planner -- the straight segment is sampled at ``path_steps`` configurations (``check``) or certified as a
+whole on the proxies (``check_swept``), nothing is searched or timed; and, without ``exact=True``, a mesh-exact collision test.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
 not covered.  HIP only; no fallback."""
 import ctypes
 import types
@@ -28,7 +32,8 @@ import torch
 from . import _lib, dr
 
 __all__ = ["link_spheres", "link_bound", "box_planes", "robot_proxies", "enabled_pairs", "config_clearance",
-           "leaf_mesh", "robot_triangles", "mesh_clearance", "FeasibilityFilter", "REFERENCE_WORKSPACE"]
+           "leaf_mesh", "robot_triangles", "mesh_clearance", "joint_below", "reach_radii", "segment_clearance",
+           "FeasibilityFilter", "REFERENCE_WORKSPACE"]
 
 REFERENCE_WORKSPACE = ((-0.2, -0.5, -0.5), (1.0, 0.5, 1.0))  # the reference's workspace box (workspace_boundary.py:9)
 
@@ -354,7 +359,135 @@ def mesh_clearance(link_poses, spheres, sphere_offsets, link_bounds, pair_enable
     return out
 
 
+def _missing_segment():
+    raise RuntimeError("this libehr_hip.so has no segment clearance kernel (ehr_segment_clearance): rebuild it")
+
+
+def joint_below(table):
+    """[J] uint32: bit k of word j = active joint k lies strictly below active joint j (the link k moves hangs from the link
+    j moves), so j moves k's axis."""
+    parent, qidx = np.asarray(table["parent"]), np.asarray(table["qidx"])
+    J = int(qidx.max()) + 1 if qidx.size else 0
+    out = np.zeros(J, dtype=np.uint32)
+    for n in range(parent.shape[0]):
+        k = int(qidx[n])
+        if k < 0:
+            continue
+        i = int(parent[n])
+        while i >= 0:
+            if qidx[i] >= 0:
+                out[int(qidx[i])] |= np.uint32(1) << np.uint32(k)
+            i = int(parent[i])
+    return out
+
+
+def reach_radii(robot, link_bounds, travel=None):
+    """W [J,L] float64 of ``ehr_segment_clearance``: a bound, at ANY configuration, on the distance of any point of any proxy of
+    rendered link l from the axis of active joint j.  0 where j is not upstream of l and 1 for a prismatic j.  For a revolute j
+    the axis passes through the origin of the link j moves; from there down the chain to link l every joint origin adds the
+    norm of its translation and every prismatic joint on the way its ``travel`` (the largest ``|q + offset|`` it may take, [J];
+    None: 0), and the link's own bound adds ``|centre| + radius``.  ``robot``: a Robot, or a joint table."""
+    table = robot if isinstance(robot, dict) else robot.joint_table()
+    parent, kind, qidx, use = (np.asarray(table[k]) for k in ("parent", "kind", "qidx", "use"))
+    origin = np.asarray(table["origin"], dtype=np.float64).reshape(-1, 4, 4)
+    bounds = np.asarray(link_bounds, dtype=np.float64).reshape(-1, 4)
+    J, L = int(qidx.max()) + 1, use.shape[0]
+    travel = np.zeros(J) if travel is None else np.abs(np.asarray(travel, dtype=np.float64).reshape(J))
+    W = np.zeros((J, L), dtype=np.float64)
+    for l in range(L):
+        c = bounds[l]
+        far = float(np.sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]) + c[3])    # from link l's origin
+        i = int(use[l])
+        while i >= 0:
+            j = int(qidx[i])
+            if j >= 0:
+                W[j, l] = far if kind[i] == 1 else 1.0
+            t = origin[i, :3, 3]
+            far += float(np.sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]))
+            if j >= 0 and kind[i] == 2:
+                far += float(travel[j])
+            i = int(parent[i])
+    return W
+
+
+def segment_clearance(table, q0, q1, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below, reach_radius,
+                      planes=None, obstacles=None, env_links=0, reach=None, cutoff=0.25, margin=0.01, depth=(3, 9), max_evals=96,
+                      trace=False):
+    """One ``ehr_segment_clearance`` launch (include/ehr.h).  Device tensors: ``table`` = (parent, origin, kind, axis, qidx, use)
+    of the joint table (int32 / float64), q0 [J], q1 [n,J] float64, offset [J] float32, the proxy arguments of
+    :func:`config_clearance` (``sphere_offsets`` [L+1]: a HOST array), upstream [L] and below [J] int32 (the uint32 words'
+    bits), reach_radius [J,L] float64.  Returns a namespace of device tensors [n]: ``status``, ``evals``, ``stop_pair`` int32,
+    ``t_free``, ``cert_self``, ``cert_env``, ``cert_reach``, ``stop_self``, ``stop_env``, ``stop_reach`` float64, pre-filled
+    with NaN / -1; with ``trace``, ``trace_t`` [n,max_evals] and ``trace_val`` [n,max_evals,6] (NaN past ``evals``).  Never
+    synchronises; the sizes' limits are the library's to refuse."""
+    if not _lib.has_segment_clearance():
+        _missing_segment()
+    parent, origin, kind, axis, qidx, use = table
+    dr._check_dev("q1", q1, torch.float64)
+    dev = q1.device
+    dr._require(q1.dim() == 2, "q1 must have shape [n, J]")
+    n, J = int(q1.shape[0]), int(q1.shape[1])
+    N, L = int(parent.shape[0]), int(use.shape[0])
+    off = np.ascontiguousarray(np.asarray(sphere_offsets), dtype=np.int32)
+    dr._require(off.shape == (L + 1,), "sphere_offsets must be a host array of L + 1 entries")
+
+    def dev_t(name, t, dtype, shape):
+        dr._check_dev(name, t, dtype)
+        dr._require(t.device == dev and tuple(t.shape) == tuple(shape), f"{name} must have shape {list(shape)}")
+        return t.contiguous()
+
+    def f64(name, t, rows):
+        if t is None:
+            return None
+        dr._check_dev(name, t, torch.float64)
+        dr._require(t.device == dev and t.dim() == 2 and t.shape[1] == 4 and t.shape[0] >= rows, f"{name} must have shape [{rows}, 4]")
+        return t.contiguous()
+
+    parent, kind, qidx = (dev_t(k, t, torch.int32, (N,)) for k, t in (("parent", parent), ("kind", kind), ("qidx", qidx)))
+    use = dev_t("use", use, torch.int32, (L,))
+    origin, axis = dev_t("origin", origin.reshape(N, 16), torch.float64, (N, 16)), dev_t("axis", axis, torch.float64, (N, 3))
+    q0, q1 = dev_t("q0", q0, torch.float64, (J,)), q1.contiguous()
+    offset = dev_t("offset", offset, torch.float32, (J,))
+    upstream, below = dev_t("upstream", upstream, torch.int32, (L,)), dev_t("below", below, torch.int32, (J,))
+    reach_radius = dev_t("reach_radius", reach_radius, torch.float64, (J, L))
+    pair_enable = dev_t("pair_enable", pair_enable, torch.int32, (L,))
+    spheres, link_bounds = f64("spheres", spheres, max(int(off[-1]), 0)), f64("link_bounds", link_bounds, L)
+    planes, obstacles = f64("planes", planes, 0), f64("obstacles", obstacles, 0)
+    if reach is not None:
+        reach = dev_t("reach", reach.reshape(-1), torch.float64, (4,))
+    Np = 0 if planes is None else int(planes.shape[0])
+    No = 0 if obstacles is None else int(obstacles.shape[0])
+    max_evals = int(max_evals)
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+    ints = lambda: torch.full((n,), -1, dtype=torch.int32, device=dev)
+    out = types.SimpleNamespace(status=ints(), t_free=nan(n), evals=ints(), cert_self=nan(n), cert_env=nan(n), cert_reach=nan(n),
+                                stop_self=nan(n), stop_env=nan(n), stop_reach=nan(n), stop_pair=ints())
+    if trace:
+        out.trace_t, out.trace_val = nan(n, max(max_evals, 1)), nan(n, max(max_evals, 1), 6)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ehr_segment_clearance(
+            _lib.ptr(parent), _lib.ptr(origin), _lib.ptr(kind), _lib.ptr(axis), _lib.ptr(qidx), _lib.ptr(use), N, J, L,
+            _lib.ptr(q0), _lib.ptr(q1), _lib.ptr(offset), n, _lib.ptr(spheres), off.ctypes.data_as(ctypes.c_void_p),
+            _lib.ptr(link_bounds), _lib.ptr(pair_enable), _lib.ptr(planes) if Np else None, Np,
+            _lib.ptr(obstacles) if No else None, No, int(env_links) & 0xffffffff, _lib.ptr(reach), float(cutoff),
+            _lib.ptr(upstream), _lib.ptr(below), _lib.ptr(reach_radius), float(margin), int(depth[0]), int(depth[1]), max_evals,
+            _lib.ptr(out.status), _lib.ptr(out.t_free), _lib.ptr(out.evals), _lib.ptr(out.cert_self), _lib.ptr(out.cert_env),
+            _lib.ptr(out.cert_reach), _lib.ptr(out.stop_self), _lib.ptr(out.stop_env), _lib.ptr(out.stop_reach),
+            _lib.ptr(out.stop_pair), _lib.ptr(out.trace_t) if trace else None, _lib.ptr(out.trace_val) if trace else None,
+            _stream()), "ehr_segment_clearance")
+    return out
+
+
 # ---- the filter -------------------------------------------------------------------------------------------------------------
+def _joint_kinds(table, J):
+    """[J]: the kind of the link each active joint moves."""
+    out = np.zeros(J, dtype=np.int32)
+    for k, c in zip(np.asarray(table["kind"]), np.asarray(table["qidx"])):
+        if 0 <= c < J:
+            out[c] = k
+    return out
+
+
 def _rows4(a, name, limit):
     if a is None:
         return None
@@ -382,6 +515,10 @@ class FeasibilityFilter:
     at again.  exact_cutoff: mesh clearances are reported up to this value [m] (default ``max(2 margin, 0.02)``: only "above
     margin or not" is needed, and a short cutoff is what lets the kernel skip most of the meshes).
 
+    swept: :meth:`check_swept` is what an online loop calls: a certificate for the whole segment instead of ``path_steps``
+    samples of it, with a search budget of ``swept_depth`` = (min, max) bisection depth and ``swept_evals`` evaluations per
+    candidate; offset_bound: the largest joint offset [rad or m] the certificate allows for.  Not with ``exact``.
+
     ``pairs``: the enabled link pairs; ``ignored``: the others with reason and settle clearance.  With ``exact``, ``mesh_pairs``
     is what the mesh kernel checks: ``pairs`` and every "settle"-ignored pair whose MESHES keep more than ``margin`` at the
     settle configuration (the proxies touched there, the links do not); ``ignored`` then holds the rest, the "settle" entries
@@ -389,11 +526,22 @@ class FeasibilityFilter:
 
     def __init__(self, robot, leaf_triangles=64, margin=0.01, ignore_pairs="auto", settle_qpos=None, planes=None,
                  obstacles=None, env_links=None, reach=None, cutoff=0.25, offsets=None, device="cuda:0", path_steps=None,
-                 exact=False, exact_cutoff=None):
+                 exact=False, exact_cutoff=None, swept=False, swept_depth=(3, 9), swept_evals=96, offset_bound=0.2):
         from .joint_calib import _check_table
         if not _lib.has_feasibility():
             _missing()
-        self.exact = bool(exact)
+        self.exact, self.swept = bool(exact), bool(swept)
+        if self.swept and self.exact:
+            raise ValueError("FeasibilityFilter: swept=True certifies the sphere proxies; a mesh-exact certificate (exact=True) "
+                             "does not exist")
+        if self.swept and not _lib.has_segment_clearance():
+            _missing_segment()
+        self.swept_depth, self.swept_evals = (int(swept_depth[0]), int(swept_depth[1])), int(swept_evals)
+        self.offset_bound = float(offset_bound)
+        if not (0 <= self.swept_depth[0] <= self.swept_depth[1] <= _lib.SEG_MAX_DEPTH and
+                1 <= self.swept_evals <= _lib.SEG_MAX_EVALS and np.isfinite(self.offset_bound) and self.offset_bound >= 0):
+            raise ValueError(f"FeasibilityFilter: swept_depth {swept_depth} must be 0 <= min <= max <= {_lib.SEG_MAX_DEPTH}, "
+                             f"swept_evals {swept_evals} 1..{_lib.SEG_MAX_EVALS}, offset_bound {offset_bound} >= 0")
         if self.exact and not _lib.has_mesh_clearance():
             _missing_mesh()
         if not (np.isfinite(cutoff) and cutoff > 0 and np.isfinite(margin) and 0 <= margin < cutoff):
@@ -446,6 +594,13 @@ class FeasibilityFilter:
             raise ValueError(f"offsets must be a contiguous [{self.J}] tensor")
         if self.exact:
             self._init_exact(leaf_triangles, exact_cutoff, settle_qpos)
+        if self.swept and self.spheres.shape[0] > _lib.SEG_MAX_SPHERES:
+            raise ValueError(f"FeasibilityFilter: {self.spheres.shape[0]} proxy spheres; the swept kernel takes "
+                             f"{_lib.SEG_MAX_SPHERES} (raise leaf_triangles)")
+        self._table = table
+        self._upstream = up(np.asarray(table["upstream"], dtype=np.uint32).view(np.int32), np.int32)
+        self._below = up(joint_below(table).view(np.int32), np.int32)
+        self._prismatic = np.array([int(k) == 2 for k in _joint_kinds(table, self.J)])
 
     def _init_exact(self, leaf_triangles, exact_cutoff, settle_qpos):
         """The triangles behind the proxies and ``mesh_pairs``: one launch per "settle"-ignored pair, that pair alone enabled,
@@ -516,6 +671,36 @@ class FeasibilityFilter:
         """The kernel on link poses [n,L,4,4]: a namespace of ``self_clear``, ``self_pair``, ``env_clear``, ``reach_clear`` [n]."""
         return config_clearance(link_poses, self._spheres, self.sphere_offsets, self._bounds, self._pair_enable, self._planes,
                                 self._obstacles, self.env_mask, self._reach, self.cutoff)
+
+    def check_swept(self, qposes, current_qpos, trace=False):
+        """Judges the WHOLE straight joint-space segment from ``current_qpos`` to each candidate [Q, <= dof] on the sphere
+        proxies: one ``ehr_segment_clearance`` launch with the budget ``swept_depth`` / ``swept_evals``; nothing synchronises.
+        The prismatic joints' travel in ``reach_radii`` is their largest ``|q|`` over ``current_qpos`` and the candidates plus
+        ``offset_bound``, which the joint offsets must stay within.  Returns a namespace of device tensors [Q]:
+
+        ``valid`` bool: ``status == 0``, more than ``margin`` is kept on all of the segment; ``status`` int32 (0 clear, 1 hit,
+        2 undecided within the budget, 3 cannot judge: a value that is not finite), ``t_free`` (the move is certified on
+        ``[0, t_free]``), ``evals``; ``self_ok`` / ``env_ok`` / ``reach_ok``: what stopped it -- for a hit the tests the
+        stopping configuration passes, for status 2 and 3 none (the kernel does not say which certificate fell short, so
+        none counts as passed); ``cert_self`` / ``cert_env`` / ``cert_reach``: the least certified values, and
+        ``stop_self`` / ``stop_env`` / ``stop_reach`` / ``stop_pair``: the raw values where the search stopped (NaN, -1 when
+        clear).  ``trace``: also ``trace_t`` and ``trace_val`` of :func:`segment_clearance`."""
+        qp, _ = self.path_table(qposes)
+        cur, _ = self.path_table(np.asarray(current_qpos, dtype=np.float64).reshape(1, -1))
+        travel = np.where(self._prismatic, np.abs(np.concatenate([qp, cur])).max(axis=0) + self.offset_bound, 0.0)
+        W = reach_radii(self._table, self.link_bounds, travel)
+        dev = self.dev
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        out = segment_clearance(self._t, to(cur[0]), to(qp), self.offsets, self._spheres, self.sphere_offsets, self._bounds,
+                                self._pair_enable, self._upstream, self._below, to(W), self._planes, self._obstacles,
+                                self.env_mask, self._reach, self.cutoff, self.margin, self.swept_depth, self.swept_evals,
+                                trace=trace)
+        hit = out.status == 1
+        out.valid = out.status == 0
+        out.self_ok = out.valid | (hit & (out.stop_self > self.margin))
+        out.env_ok = out.valid | (hit & (out.stop_env > self.margin))
+        out.reach_ok = out.valid | (hit & (out.stop_reach >= 0))
+        return out
 
     def mesh_clearance(self, link_poses):
         """The mesh kernel on link poses [n,L,4,4] (``exact=True`` only): a namespace of ``mesh_clear``, ``mesh_pair``,

@@ -35,7 +35,9 @@ class OnlineCalibration:
         AND-ed with the filter's verdict on the candidates and on the straight joint-space segment from the last captured
         configuration to each (``feasible.path_steps`` configurations, 1 by default), and the round's log record gains
         ``rejected_self`` / ``rejected_env`` / ``rejected_reach``, the candidates each test turned down (and, for a filter
-        built with ``exact=True``, ``rejected_mode = "exact"``: the meshes turned them down, not the proxies).  When it turns all of
+        built with ``exact=True``, ``rejected_mode = "exact"``: the meshes turned them down, not the proxies).  A filter built
+        with ``swept=True`` judges the WHOLE segment instead (``check_swept``): the record then has ``rejected_mode = "swept"``
+        and ``undecided``, the candidates the certificate's budget could not decide (they count as turned down).  When it turns all of
         them down, the explorers' "no valid qpos found" error is what the caller sees."""
         if explore not in ("variance", "information"):
             raise ValueError(f"explore={explore!r}: 'variance' or 'information'")
@@ -84,12 +86,19 @@ class OnlineCalibration:
                 cand, valid = self.candidates(it)
                 rejected = {}
                 if self.feasible is not None:
-                    fc = self.feasible.check(cand, current_qpos=qpos, path_steps=self.feasible.path_steps or 1)
+                    swept = getattr(self.feasible, "swept", False)
+                    if swept:
+                        fc = self.feasible.check_swept(cand, qpos)
+                    else:
+                        fc = self.feasible.check(cand, current_qpos=qpos, path_steps=self.feasible.path_steps or 1)
                     ok = fc.valid.cpu().numpy()
                     valid = ok if valid is None else (np.asarray(valid.cpu() if torch.is_tensor(valid) else valid) != 0) & ok
                     rejected = {f"rejected_{k}": int((~getattr(fc, f"{k}_ok")).sum()) for k in ("self", "env", "reach")}
                     if getattr(self.feasible, "exact", False):            # (a proxy filter's record keeps today's keys)
                         rejected["rejected_mode"] = "exact"
+                    if swept:                                             # the whole segment, certified or turned down
+                        rejected["rejected_mode"] = "swept"
+                        rejected["undecided"] = int((fc.status >= 2).sum())
                 if self.explore == "information":
                     out = InformationExplorer(trainer.fast, robot=self.robot).forward(cand, valid=valid)
                     scores = {"info_gain": float(out["gain"]), "gain_mean": float(out["gain_mean"])}

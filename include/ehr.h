@@ -940,6 +940,70 @@ int ehr_mesh_clearance(const float* link_poses, const double* spheres, const int
                        int n_triangles, double* mesh_clear, int32_t* mesh_pair, int32_t* mesh_tri, double* env_clear,
                        void* stream);
 
+/* Certified clearance along the whole joint segment (easyhec_amd/feasibility.py, csrc/ehr_segment_clearance.hip): per candidate
+ * either the sphere proxies keep more than `margin` on ALL of the straight joint-space segment q(t) = q0 + t d, d = q1 - q0, t in
+ * [0,1], or how far the move is certified and what stopped it.  Bisection with conservative advancement; on the device,
+ * conservative, one launch on `stream`, no atomics, no allocation, no host round trip.
+ * Inputs: the kinematic table, offset [J] float32, N, J, L as ehr_joint_forward takes them; q0 [J], q1 [n,J] float64; spheres,
+ * sphere_offsets (HOST), link_bounds, pair_enable, planes, obstacles, env_links, reach, cutoff as ehr_config_clearance takes them
+ * (L <= EHR_FEAS_MAX_LINKS here too); upstream [L] uint32 (bit j: active joint j lies between the root and rendered link l);
+ * joint_below [J] uint32 (bit k of word j: joint k lies strictly below joint j, i.e. j moves k's axis); reach_radius W [J,L] float64
+ * (below); margin; the budget min_depth <= max_depth <= EHR_SEG_MAX_DEPTH, 1 <= max_evals <= EHR_SEG_MAX_EVALS.
+ * Arithmetic: float64, every operation rounded on its own; a sum "over j" runs over ascending j and starts from 0.0.
+ *   An evaluation at centre c with half-width h (dyadic, exact): q(c)_j = q0_j + c d_j; the kinematics of ehr_joint_forward at
+ *   q(c) (offsets added inside, as there) give float32 link_poses and joint_frames (a_j, p_j); the spheres and link bounds go to
+ *   the base frame by ehr_config_clearance's expression.  The RAW values self, self_pair, env, reach are those of
+ *   ehr_joint_forward + ehr_config_clearance at q(c), bit for bit.
+ *   lever arm      rho[j,s] = sqrt(|u|^2) + r_s, u = (c_s - p_j) x a_j = (v_y a_z - v_z a_y, v_z a_x - v_x a_z, v_x a_y - v_y a_x),
+ *                  |u|^2 = (u_x u_x + u_y u_y) + u_z u_z, for a revolute joint j (a, p widened to double); 1 for any other
+ *   W[j,l]         a bound, independent of the configuration, on the distance of any point of any proxy of link l from joint j's
+ *                  axis: 0 where j is not upstream of l, 1 for a prismatic j (the host's; see feasibility.reach_radii)
+ *   G[j,l]         sum over k in up(l) with k below j of |d_k| W[k,l]                              (once per candidate)
+ *   C(l,M)         sum over j in M of |d_j| G[j,l]
+ *   E_s            h * (sum over j in M of |d_j| rho[j,s]) + ((0.5 * h) * h) * C(l,M)               sphere s of link l under mask M
+ *   Ebar(l,M)      h * (sum over j in M of |d_j| W[j,l]) + ((0.5 * h) * h) * C(l,M)                 >= every E_s of the link
+ *   masks          link pair (a,b): up(a) & ~up(b) for a's spheres, up(b) & ~up(a) for b's (joints upstream of both move them
+ *                  rigidly together); planes, obstacles and reach: up(l)
+ * Why it holds: a point moves at most sum_j |d_j| dist(point, axis_j) per unit of t; that distance changes only through the
+ * joints below j, by at most G[j,l] per unit of t; integrated over |t - c| <= h this is E_s.
+ *   Certified values of [c - h, c + h], FEAS_CULL_SLACK = 1e-6 subtracted ONCE from each (the float32 rounding of poses and axes):
+ *   cert_self  = min over the enabled pairs (a,b) with spheres on both links of: gap - (E_sa + E_sb) over the sphere pairs with
+ *                gap < cutoff, and the pair's far value cutoff - (Ebar(a,Ma) + Ebar(b,Mb)), which stands for every sphere pair
+ *                at or beyond cutoff (so a link pair culled through link_bounds changes no bit); cutoff where there is no pair
+ *   cert_env   = min over the links of env_links with spheres (none if there are neither planes nor obstacles) of: value - E_s
+ *                over the (sphere, plane) and (sphere, obstacle) values < cutoff, and the link's far value cutoff - Ebar(l,up(l))
+ *   cert_reach = the same over all links with spheres and the reach values; cutoff where reach is NULL
+ * Search: depth first, left to right, over the 2^min_depth dyadic intervals of [0,1].  For interval [a, a + 2h] of depth k,
+ * evals counting this evaluation:
+ *   1. a pose entry not finite: status 3.   2. raw fails (not self > margin, or not env > margin, or not reach >= 0): status 1 (hit).
+ *   3. cert_self > margin, cert_env > margin and cert_reach >= 0: the three are folded into the running minima; next interval.
+ *   4. k < max_depth and evals < max_evals: the two halves take the interval's place, the left one first.
+ *   5. otherwise: status 2 (undecided).
+ * No interval left: status 0 (clear).  evals == max_evals with intervals left after a certified one: status 2 with NaN stop values
+ * (no evaluation stopped the search).  A q0 or q1 entry that is not finite: status 3 with evals 0.
+ * Outputs [n]: status int32; t_free float64 = a at a stop (everything left of it is certified), 1 when clear; evals int32;
+ * cert_self, cert_env, cert_reach = the minima over the certified intervals, cutoff if none; stop_self, stop_env, stop_reach,
+ * stop_pair = the raw values of the evaluation that stopped the search (status 1, 2), NaN and -1 otherwise.  Optional trace
+ * (both or neither NULL): trace_t [n,max_evals] = c and trace_val [n,max_evals,6] = raw self, env, reach, certified self, env,
+ * reach (NaN for a status-3 evaluation) of every evaluation in order; entries past evals are untouched.  A candidate leaves its
+ * neighbours untouched.
+ * One workgroup of 256 threads per candidate, the spheres in LDS (40 bytes each).  Refused (EHR_ERR_INVALID): the limits of
+ * ehr_joint_forward and ehr_config_clearance, S > EHR_SEG_MAX_SPHERES (what the 160 KiB of LDS of a gfx950 compute unit hold
+ * beside the kinematics' frames), a budget outside its limits, margin outside 0 <= margin < cutoff, NULL tensors.
+ * ehr_version() is unchanged: the presence of the symbol is the capability check. */
+#define EHR_SEG_MAX_DEPTH 20
+#define EHR_SEG_MAX_EVALS 4096
+#define EHR_SEG_MAX_SPHERES 3264
+int ehr_segment_clearance(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                          const int32_t* qidx, const int32_t* use, int N, int J, int L, const double* q0, const double* q1,
+                          const float* offset, int n, const double* spheres, const int32_t* sphere_offsets,
+                          const double* link_bounds, const uint32_t* pair_enable, const double* planes, int n_planes,
+                          const double* obstacles, int n_obstacles, uint32_t env_links, const double* reach, double cutoff,
+                          const uint32_t* upstream, const uint32_t* joint_below, const double* reach_radius, double margin,
+                          int min_depth, int max_depth, int max_evals, int32_t* status, double* t_free, int32_t* evals,
+                          double* cert_self, double* cert_env, double* cert_reach, double* stop_self, double* stop_env,
+                          double* stop_reach, int32_t* stop_pair, double* trace_t, double* trace_val, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
