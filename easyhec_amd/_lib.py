@@ -115,6 +115,10 @@ SIGNATURES = {
     "ehr_segment_clearance": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 +
                               [c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, ctypes.c_double] + [c_void_p] * 3 +
                               [ctypes.c_double] + [c_int] * 3 + [c_void_p] * 13),
+    "ehr_edge_clearance": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 +
+                           [c_int, c_void_p, c_int, ctypes.c_uint32, c_void_p, ctypes.c_double] + [c_void_p] * 3 +
+                           [ctypes.c_double] + [c_int] * 3 + [c_void_p] * 14),
+    "ehr_roadmap_paths": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 8),
 }
 
 
@@ -219,10 +223,15 @@ def has_segment_clearance():
     return has_symbols("ehr_segment_clearance")
 
 
+def has_roadmap():
+    return has_symbols("ehr_edge_clearance", "ehr_roadmap_paths")
+
+
 IG_MAX_PARAMS = 32  # include/ehr.h: EHR_IG_MAX_PARAMS
 FEAS_MAX_LINKS, FEAS_MAX_SPHERES, FEAS_MAX_PLANES, FEAS_MAX_OBSTACLES = 32, 4096, 16, 1024  # include/ehr.h: EHR_FEAS_*
 MESH_MAX_TRIANGLES = 1048576  # include/ehr.h: EHR_MESH_MAX_TRIANGLES
 SEG_MAX_DEPTH, SEG_MAX_EVALS, SEG_MAX_SPHERES = 20, 4096, 3264  # include/ehr.h: EHR_SEG_*
+ROADMAP_MAX_NODES, ROADMAP_MAX_HOPS = 4096, 8  # include/ehr.h: EHR_ROADMAP_*
 
 
 # the state block of ehr_lm_update (include/ehr.h: EHR_LM_*), in float64 words

@@ -19,9 +19,14 @@ a maximum-distance constraint over the links, a workspace-boundary point cloud).
                       4a-15): a certificate that the proxies keep ``margin`` on the WHOLE segment to a candidate, or how far
                       the move is certified and what stopped it.  ``FeasibilityFilter(swept=True).check_swept`` calls it;
                       ``joint_below`` and ``reach_radii`` are its host tables.
+    edge_clearance    one ``ehr_edge_clearance`` launch: the same certificate for the edges of a roadmap, each between its own
+                      two nodes; roadmap_edges builds the edge list and its adjacency on the device, roadmap_paths is one
+                      ``ehr_roadmap_paths`` launch (csrc/ehr_roadmap.hip): shortest
+                      paths of at most H certified moves.  ``FeasibilityFilter(swept=True, detour_hops=H).plan`` calls the three.
 
-What it is NOT: a planner -- the straight segment is sampled at ``path_steps`` configurations (``check``) or certified as a
-whole on the proxies (``check_swept``), nothing is searched or timed; and, without ``exact=True``, a mesh-exact collision test.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
+What it is NOT: a motion planner with smoothing or timing -- the straight segment is sampled at ``path_steps`` configurations
+(``check``) or certified as a whole on the proxies (``check_swept``), ``plan`` chains such certified segments over the round's
+own candidates, and nothing is shortcut or timed; and, without ``exact=True``, a mesh-exact collision test.  Links that are not rendered (a gripper whose meshes are not packaged) have no proxies and are
 not covered.  HIP only; no fallback."""
 import ctypes
 import types
@@ -33,7 +38,7 @@ from . import _lib, dr
 
 __all__ = ["link_spheres", "link_bound", "box_planes", "robot_proxies", "enabled_pairs", "config_clearance",
            "leaf_mesh", "robot_triangles", "mesh_clearance", "joint_below", "reach_radii", "segment_clearance",
-           "FeasibilityFilter", "REFERENCE_WORKSPACE"]
+           "edge_clearance", "roadmap_paths", "roadmap_edges", "FeasibilityFilter", "REFERENCE_WORKSPACE"]
 
 REFERENCE_WORKSPACE = ((-0.2, -0.5, -0.5), (1.0, 0.5, 1.0))  # the reference's workspace box (workspace_boundary.py:9)
 
@@ -410,23 +415,12 @@ def reach_radii(robot, link_bounds, travel=None):
     return W
 
 
-def segment_clearance(table, q0, q1, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below, reach_radius,
-                      planes=None, obstacles=None, env_links=0, reach=None, cutoff=0.25, margin=0.01, depth=(3, 9), max_evals=96,
-                      trace=False):
-    """One ``ehr_segment_clearance`` launch (include/ehr.h).  Device tensors: ``table`` = (parent, origin, kind, axis, qidx, use)
-    of the joint table (int32 / float64), q0 [J], q1 [n,J] float64, offset [J] float32, the proxy arguments of
-    :func:`config_clearance` (``sphere_offsets`` [L+1]: a HOST array), upstream [L] and below [J] int32 (the uint32 words'
-    bits), reach_radius [J,L] float64.  Returns a namespace of device tensors [n]: ``status``, ``evals``, ``stop_pair`` int32,
-    ``t_free``, ``cert_self``, ``cert_env``, ``cert_reach``, ``stop_self``, ``stop_env``, ``stop_reach`` float64, pre-filled
-    with NaN / -1; with ``trace``, ``trace_t`` [n,max_evals] and ``trace_val`` [n,max_evals,6] (NaN past ``evals``).  Never
-    synchronises; the sizes' limits are the library's to refuse."""
-    if not _lib.has_segment_clearance():
-        _missing_segment()
+def _segment_common(table, J, dev, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below, reach_radius,
+                    planes, obstacles, reach, n, max_evals, trace):
+    """What :func:`segment_clearance` and :func:`edge_clearance` share: the checked tensors as the argument groups the library
+    takes around the segments' own (table and sizes, offset, proxies, reach, host tables), the pre-filled outputs [n] and the
+    tensors those pointers belong to."""
     parent, origin, kind, axis, qidx, use = table
-    dr._check_dev("q1", q1, torch.float64)
-    dev = q1.device
-    dr._require(q1.dim() == 2, "q1 must have shape [n, J]")
-    n, J = int(q1.shape[0]), int(q1.shape[1])
     N, L = int(parent.shape[0]), int(use.shape[0])
     off = np.ascontiguousarray(np.asarray(sphere_offsets), dtype=np.int32)
     dr._require(off.shape == (L + 1,), "sphere_offsets must be a host array of L + 1 entries")
@@ -446,7 +440,6 @@ def segment_clearance(table, q0, q1, offset, spheres, sphere_offsets, link_bound
     parent, kind, qidx = (dev_t(k, t, torch.int32, (N,)) for k, t in (("parent", parent), ("kind", kind), ("qidx", qidx)))
     use = dev_t("use", use, torch.int32, (L,))
     origin, axis = dev_t("origin", origin.reshape(N, 16), torch.float64, (N, 16)), dev_t("axis", axis, torch.float64, (N, 3))
-    q0, q1 = dev_t("q0", q0, torch.float64, (J,)), q1.contiguous()
     offset = dev_t("offset", offset, torch.float32, (J,))
     upstream, below = dev_t("upstream", upstream, torch.int32, (L,)), dev_t("below", below, torch.int32, (J,))
     reach_radius = dev_t("reach_radius", reach_radius, torch.float64, (J, L))
@@ -457,25 +450,191 @@ def segment_clearance(table, q0, q1, offset, spheres, sphere_offsets, link_bound
         reach = dev_t("reach", reach.reshape(-1), torch.float64, (4,))
     Np = 0 if planes is None else int(planes.shape[0])
     No = 0 if obstacles is None else int(obstacles.shape[0])
-    max_evals = int(max_evals)
     nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
     ints = lambda: torch.full((n,), -1, dtype=torch.int32, device=dev)
     out = types.SimpleNamespace(status=ints(), t_free=nan(n), evals=ints(), cert_self=nan(n), cert_env=nan(n), cert_reach=nan(n),
                                 stop_self=nan(n), stop_env=nan(n), stop_reach=nan(n), stop_pair=ints())
     if trace:
         out.trace_t, out.trace_val = nan(n, max(max_evals, 1)), nan(n, max(max_evals, 1), 6)
+    head = [_lib.ptr(t) for t in (parent, origin, kind, axis, qidx, use)] + [N, J, L]
+    proxies = [_lib.ptr(spheres), off.ctypes.data_as(ctypes.c_void_p), _lib.ptr(link_bounds), _lib.ptr(pair_enable),
+               _lib.ptr(planes) if Np else None, Np, _lib.ptr(obstacles) if No else None, No]
+    tables = [_lib.ptr(upstream), _lib.ptr(below), _lib.ptr(reach_radius)]
+    keep = (parent, origin, kind, axis, qidx, use, offset, spheres, off, link_bounds, pair_enable, planes, obstacles, reach,
+            upstream, below, reach_radius)               # (alive until the launch is queued)
+    return head, _lib.ptr(offset), proxies, _lib.ptr(reach), tables, out, keep
+
+
+def _segment_outputs(out, trace):
+    return [_lib.ptr(getattr(out, k)) for k in ("status", "t_free", "evals", "cert_self", "cert_env", "cert_reach", "stop_self",
+                                                "stop_env", "stop_reach", "stop_pair")], \
+        [_lib.ptr(out.trace_t) if trace else None, _lib.ptr(out.trace_val) if trace else None]
+
+
+def segment_clearance(table, q0, q1, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below, reach_radius,
+                      planes=None, obstacles=None, env_links=0, reach=None, cutoff=0.25, margin=0.01, depth=(3, 9), max_evals=96,
+                      trace=False):
+    """One ``ehr_segment_clearance`` launch (include/ehr.h).  Device tensors: ``table`` = (parent, origin, kind, axis, qidx, use)
+    of the joint table (int32 / float64), q0 [J], q1 [n,J] float64, offset [J] float32, the proxy arguments of
+    :func:`config_clearance` (``sphere_offsets`` [L+1]: a HOST array), upstream [L] and below [J] int32 (the uint32 words'
+    bits), reach_radius [J,L] float64.  Returns a namespace of device tensors [n]: ``status``, ``evals``, ``stop_pair`` int32,
+    ``t_free``, ``cert_self``, ``cert_env``, ``cert_reach``, ``stop_self``, ``stop_env``, ``stop_reach`` float64, pre-filled
+    with NaN / -1; with ``trace``, ``trace_t`` [n,max_evals] and ``trace_val`` [n,max_evals,6] (NaN past ``evals``).  Never
+    synchronises; the sizes' limits are the library's to refuse."""
+    if not _lib.has_segment_clearance():
+        _missing_segment()
+    dr._check_dev("q1", q1, torch.float64)
+    dev = q1.device
+    dr._require(q1.dim() == 2, "q1 must have shape [n, J]")
+    n, J = int(q1.shape[0]), int(q1.shape[1])
+    max_evals = int(max_evals)
+    head, offset, proxies, reach, tables, out, keep = _segment_common(
+        table, J, dev, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below, reach_radius, planes, obstacles,
+        reach, n, max_evals, trace)
+    dr._check_dev("q0", q0, torch.float64)
+    dr._require(q0.device == dev and tuple(q0.shape) == (J,), f"q0 must have shape {[J]}")
+    q0, q1 = q0.contiguous(), q1.contiguous()
+    outs, traces = _segment_outputs(out, trace)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().ehr_segment_clearance(
-            _lib.ptr(parent), _lib.ptr(origin), _lib.ptr(kind), _lib.ptr(axis), _lib.ptr(qidx), _lib.ptr(use), N, J, L,
-            _lib.ptr(q0), _lib.ptr(q1), _lib.ptr(offset), n, _lib.ptr(spheres), off.ctypes.data_as(ctypes.c_void_p),
-            _lib.ptr(link_bounds), _lib.ptr(pair_enable), _lib.ptr(planes) if Np else None, Np,
-            _lib.ptr(obstacles) if No else None, No, int(env_links) & 0xffffffff, _lib.ptr(reach), float(cutoff),
-            _lib.ptr(upstream), _lib.ptr(below), _lib.ptr(reach_radius), float(margin), int(depth[0]), int(depth[1]), max_evals,
-            _lib.ptr(out.status), _lib.ptr(out.t_free), _lib.ptr(out.evals), _lib.ptr(out.cert_self), _lib.ptr(out.cert_env),
-            _lib.ptr(out.cert_reach), _lib.ptr(out.stop_self), _lib.ptr(out.stop_env), _lib.ptr(out.stop_reach),
-            _lib.ptr(out.stop_pair), _lib.ptr(out.trace_t) if trace else None, _lib.ptr(out.trace_val) if trace else None,
-            _stream()), "ehr_segment_clearance")
+            *head, _lib.ptr(q0), _lib.ptr(q1), offset, n, *proxies, int(env_links) & 0xffffffff, reach, float(cutoff), *tables,
+            float(margin), int(depth[0]), int(depth[1]), max_evals, *outs, *traces, _stream()), "ehr_segment_clearance")
     return out
+
+
+def _missing_roadmap():
+    raise RuntimeError("this libehr_hip.so has no roadmap kernels (ehr_edge_clearance, ehr_roadmap_paths): rebuild it")
+
+
+def edge_clearance(table, nodes, edge_a, edge_b, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below,
+                   reach_radius, planes=None, obstacles=None, env_links=0, reach=None, cutoff=0.25, margin=0.01, depth=(3, 9),
+                   max_evals=96, trace=False):
+    """One ``ehr_edge_clearance`` launch (include/ehr.h): :func:`segment_clearance` for the edges of a roadmap.  Device tensors
+    as there, but nodes [V,J] float64 and edge_a, edge_b [n] int32 take the place of q0 and q1: edge e runs from node
+    ``edge_a[e]`` to node ``edge_b[e]``, and an index outside ``0..V-1`` marks an edge that is skipped (status 3, evals 0).
+    Returns :func:`segment_clearance`'s namespace [n] and ``length`` [n] float64, pre-filled with NaN / -1.  Never synchronises;
+    the sizes' limits are the library's to refuse."""
+    if not _lib.has_roadmap():
+        _missing_roadmap()
+    dr._check_dev("nodes", nodes, torch.float64)
+    dev = nodes.device
+    dr._require(nodes.dim() == 2, "nodes must have shape [V, J]")
+    V, J = int(nodes.shape[0]), int(nodes.shape[1])
+    dr._check_dev("edge_a", edge_a, torch.int32)
+    dr._check_dev("edge_b", edge_b, torch.int32)
+    dr._require(edge_a.device == dev and edge_b.device == dev and edge_a.dim() == 1 and edge_a.shape == edge_b.shape,
+                "edge_a and edge_b must have shape [n]")
+    n, max_evals = int(edge_a.shape[0]), int(max_evals)
+    head, offset, proxies, reach, tables, out, keep = _segment_common(
+        table, J, dev, offset, spheres, sphere_offsets, link_bounds, pair_enable, upstream, below, reach_radius, planes, obstacles,
+        reach, n, max_evals, trace)
+    out.length = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    nodes, edge_a, edge_b = nodes.contiguous(), edge_a.contiguous(), edge_b.contiguous()
+    outs, traces = _segment_outputs(out, trace)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ehr_edge_clearance(
+            *head, _lib.ptr(nodes), V, _lib.ptr(edge_a), _lib.ptr(edge_b), offset, n, *proxies, int(env_links) & 0xffffffff, reach,
+            float(cutoff), *tables, float(margin), int(depth[0]), int(depth[1]), max_evals, *outs, _lib.ptr(out.length), *traces,
+            _stream()), "ehr_edge_clearance")
+    return out
+
+
+def roadmap_paths(adj_start, adj_node, adj_edge, edge_status, edge_length, source=0, hops=4):
+    """One ``ehr_roadmap_paths`` launch (include/ehr.h): shortest paths of at most ``hops`` usable edges from ``source``.  Device
+    tensors: the CSR adjacency adj_start [V+1], adj_node [A], adj_edge [A] int32 (:func:`roadmap_edges`), edge_status [E] int32
+    and edge_length [E] float64 (:func:`edge_clearance`).  Returns a namespace of device tensors, pre-filled with NaN / -1:
+    ``dist`` [H+1,V] float64, ``pred_node``, ``pred_edge`` [H,V], ``hops`` [V], ``path`` [V,H+1], ``path_edge`` [V,H] and
+    ``changed`` [H] int32.  Never synchronises; the sizes' limits are the library's to refuse."""
+    if not _lib.has_roadmap():
+        _missing_roadmap()
+    dr._check_dev("adj_start", adj_start, torch.int32)
+    dev = adj_start.device
+    dr._require(adj_start.dim() == 1 and adj_start.shape[0] >= 1, "adj_start must have shape [V + 1]")
+    V, H = int(adj_start.shape[0]) - 1, int(hops)
+    for name, t, dtype in (("adj_node", adj_node, torch.int32), ("adj_edge", adj_edge, torch.int32),
+                           ("edge_status", edge_status, torch.int32), ("edge_length", edge_length, torch.float64)):
+        dr._check_dev(name, t, dtype)
+        dr._require(t.device == dev and t.dim() == 1, f"{name} must have one dimension")
+    dr._require(adj_node.shape == adj_edge.shape, "adj_node and adj_edge must have shape [A]")
+    dr._require(edge_status.shape == edge_length.shape, "edge_status and edge_length must have shape [E]")
+    A, E = int(adj_node.shape[0]), int(edge_status.shape[0])
+    adj_start, adj_node, adj_edge = adj_start.contiguous(), adj_node.contiguous(), adj_edge.contiguous()
+    edge_status, edge_length = edge_status.contiguous(), edge_length.contiguous()
+    Hs, Vs = max(H, 0), max(V, 0)
+    ints = lambda *shape: torch.full(shape, -1, dtype=torch.int32, device=dev)
+    out = types.SimpleNamespace(dist=torch.full((Hs + 1, Vs), float("nan"), dtype=torch.float64, device=dev),
+                                pred_node=ints(Hs, Vs), pred_edge=ints(Hs, Vs), hops=ints(Vs), path=ints(Vs, Hs + 1),
+                                path_edge=ints(Vs, Hs), changed=ints(Hs))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ehr_roadmap_paths(
+            _lib.ptr(adj_start), _lib.ptr(adj_node) if A else None, _lib.ptr(adj_edge) if A else None, A,
+            _lib.ptr(edge_status) if E else None, _lib.ptr(edge_length) if E else None, V, E, int(source), H, _lib.ptr(out.dist),
+            _lib.ptr(out.pred_node), _lib.ptr(out.pred_edge), _lib.ptr(out.hops), _lib.ptr(out.path), _lib.ptr(out.path_edge),
+            _lib.ptr(out.changed), _stream()), "ehr_roadmap_paths")
+    return out
+
+
+def roadmap_edges(nodes, ok, neighbours):
+    """The edge list and the adjacency of one round's roadmap, on the device, with fixed shapes and no synchronisation.
+    nodes [V,J] float64 (node 0: where the arm is), ok [V] bool (the node may be an end point), ``neighbours`` = K >= 0.
+
+    Edges ``0 .. V-2`` are the direct moves ``(0, v)``, v = 1..V-1.  Edge ``V - 1 + (v - 1) K + k`` is node v's k-th nearest
+    OTHER node u >= 1, written ``(min(u, v), max(u, v))``: nearness by the squared joint-space distance, accumulated ``acc = acc +
+    d_j * d_j`` over ascending j from 0.0, each operation rounded on its own; a stable sort, so ties go to the lower index, and
+    a second stable sort that puts the nodes with ``ok`` before the others (a slot is not spent on a node that cannot be an
+    end point while one that can is left).  It is written ``(-1, -1)`` -- skipped -- where either end has no ``ok``, where
+    u < v lists v among its own K (the lower index's copy stands), and where v has fewer than k + 1 other nodes.
+
+    Returns (edge_a [E], edge_b [E], adj_start [V+1], adj_node [2E], adj_edge [2E]) int32, E = (V - 1)(1 + K): the CSR
+    adjacency over all E edges, both directions, each node's slots in ascending edge index; the slots of skipped edges lie
+    past ``adj_start[V]`` with node -1.
+
+    Memory: dense [V,V] transients -- two float64 and three int64 matrices and one of bool, about 41 V^2 bytes: 0.7 GB at the
+    4096 nodes a roadmap may have, 41 MB at 1000."""
+    dr._check_dev("nodes", nodes, torch.float64)
+    dev = nodes.device
+    dr._require(nodes.dim() == 2 and nodes.shape[0] >= 1, "nodes must have shape [V, J]")
+    V, J, K = int(nodes.shape[0]), int(nodes.shape[1]), int(neighbours)
+    dr._require(K >= 0, "neighbours must be >= 0")
+    dr._require(ok.device == dev and ok.dtype == torch.bool and tuple(ok.shape) == (V,), "ok must be a bool tensor [V]")
+    M = V - 1                                            # the nodes that have neighbours: 1..V-1
+    ar = torch.arange(1, V, device=dev, dtype=torch.int64)
+    da, db = torch.zeros_like(ar), ar.clone()            # the direct moves
+    if K > 0 and M > 0:
+        O = max(M - 1, 0)                                # the others of each node
+        rows = torch.arange(M, device=dev)[:, None]
+        cols = torch.arange(O, device=dev)[None, :]
+        other = cols + (cols >= rows)                    # [M,O]: 0..M-1 without the row itself, ascending
+        x = nodes[1:]
+        acc = torch.zeros((M, M), dtype=torch.float64, device=dev)   # every pair once, the diagonal dropped below
+        for j in range(J):
+            d = x[None, :, j] - x[:, None, j]
+            acc = acc + d * d
+        acc = torch.gather(acc, 1, other)
+        order = torch.argsort(acc, dim=1, stable=True)               # (NaN sorts last, as numpy's)
+        near = torch.gather(other, 1, order)                         # 0-based among nodes 1.., nearest first
+        first = torch.argsort((~ok[1:][near]).to(torch.int8), dim=1, stable=True)[:, :K]
+        near = torch.gather(near, 1, first)                          # [M,min(K,O)]: those with ok before the others
+        lists = torch.zeros((M, M), dtype=torch.bool, device=dev)
+        lists.scatter_(1, near, True)                                # lists[v,u]: v lists u
+        v0 = rows.expand_as(near)
+        good = ok[1:][v0] & ok[1:][near] & ~((near < v0) & lists[near, v0])
+        na = torch.where(good, torch.minimum(near, v0) + 1, -1)
+        nb = torch.where(good, torch.maximum(near, v0) + 1, -1)
+        pad = torch.full((M, K - near.shape[1]), -1, dtype=torch.int64, device=dev)
+        na, nb = torch.cat([na, pad], dim=1).reshape(-1), torch.cat([nb, pad], dim=1).reshape(-1)
+    else:
+        na = nb = torch.full((M * K,), -1, dtype=torch.int64, device=dev)
+    ea, eb = torch.cat([da, na]), torch.cat([db, nb])
+    E = int(ea.shape[0])
+    eidx = torch.arange(E, device=dev, dtype=torch.int64)
+    owner, partner = torch.cat([ea, eb]), torch.cat([eb, ea])
+    owner = torch.where(owner < 0, V, owner)                         # skipped edges: past every node
+    # (the keys of kept edges differ; the two slots of a skipped edge tie, and both read (-1, e): their order does not show)
+    at = torch.argsort(owner * max(E, 1) + torch.cat([eidx, eidx]))
+    start = torch.searchsorted(owner[at].contiguous(), torch.arange(V + 1, device=dev, dtype=torch.int64))
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    return i32(ea), i32(eb), i32(start), i32(partner[at]), i32(torch.cat([eidx, eidx])[at])
 
 
 # ---- the filter -------------------------------------------------------------------------------------------------------------
@@ -519,6 +678,11 @@ class FeasibilityFilter:
     samples of it, with a search budget of ``swept_depth`` = (min, max) bisection depth and ``swept_evals`` evaluations per
     candidate; offset_bound: the largest joint offset [rad or m] the certificate allows for.  Not with ``exact``.
 
+    detour_hops: 0, or 2..8 (with ``swept``): :meth:`plan` is what an online loop calls -- a candidate whose straight move is
+    turned down is kept if a path of at most ``detour_hops`` certified straight moves over the other candidates leads to it.
+    detour_neighbours: the nearest candidates each candidate is joined to; detour_via: extra nodes per :meth:`plan`, drawn with
+    ``robot.sample_qpos`` from a generator seeded with ``detour_seed`` at construction.
+
     ``pairs``: the enabled link pairs; ``ignored``: the others with reason and settle clearance.  With ``exact``, ``mesh_pairs``
     is what the mesh kernel checks: ``pairs`` and every "settle"-ignored pair whose MESHES keep more than ``margin`` at the
     settle configuration (the proxies touched there, the links do not); ``ignored`` then holds the rest, the "settle" entries
@@ -526,7 +690,8 @@ class FeasibilityFilter:
 
     def __init__(self, robot, leaf_triangles=64, margin=0.01, ignore_pairs="auto", settle_qpos=None, planes=None,
                  obstacles=None, env_links=None, reach=None, cutoff=0.25, offsets=None, device="cuda:0", path_steps=None,
-                 exact=False, exact_cutoff=None, swept=False, swept_depth=(3, 9), swept_evals=96, offset_bound=0.2):
+                 exact=False, exact_cutoff=None, swept=False, swept_depth=(3, 9), swept_evals=96, offset_bound=0.2,
+                 detour_hops=0, detour_neighbours=8, detour_via=0, detour_seed=0):
         from .joint_calib import _check_table
         if not _lib.has_feasibility():
             _missing()
@@ -536,6 +701,16 @@ class FeasibilityFilter:
                              "does not exist")
         if self.swept and not _lib.has_segment_clearance():
             _missing_segment()
+        self.detour_hops, self.detour_neighbours, self.detour_via = int(detour_hops), int(detour_neighbours), int(detour_via)
+        if self.detour_hops != 0 and not 2 <= self.detour_hops <= _lib.ROADMAP_MAX_HOPS:
+            raise ValueError(f"FeasibilityFilter: detour_hops {detour_hops} must be 0 (no detours) or 2..{_lib.ROADMAP_MAX_HOPS}")
+        if self.detour_hops and not self.swept:
+            raise ValueError("FeasibilityFilter: detour_hops needs swept=True (a roadmap's edges are certified segments)")
+        if self.detour_neighbours < 0 or self.detour_via < 0:
+            raise ValueError(f"FeasibilityFilter: detour_neighbours {detour_neighbours} and detour_via {detour_via} must be >= 0")
+        if self.detour_hops and not _lib.has_roadmap():
+            _missing_roadmap()
+        self._via_rng = np.random.default_rng(detour_seed)             # seeded once: every plan() draws on from it
         self.swept_depth, self.swept_evals = (int(swept_depth[0]), int(swept_depth[1])), int(swept_evals)
         self.offset_bound = float(offset_bound)
         if not (0 <= self.swept_depth[0] <= self.swept_depth[1] <= _lib.SEG_MAX_DEPTH and
@@ -700,6 +875,76 @@ class FeasibilityFilter:
         out.self_ok = out.valid | (hit & (out.stop_self > self.margin))
         out.env_ok = out.valid | (hit & (out.stop_env > self.margin))
         out.reach_ok = out.valid | (hit & (out.stop_reach >= 0))
+        return out
+
+    def plan(self, qposes, current_qpos, via=None):
+        """A roadmap over one round's candidates: which of them [Q, <= dof] the arm can reach from ``current_qpos`` by at most
+        ``detour_hops`` straight joint-space moves, each certified on the
+        sphere proxies as :meth:`check_swept` certifies the direct one.  The nodes are ``[current] + candidates + via``
+        (``via`` [., <= dof]: extra configurations to pass through; None: ``detour_via`` samples of ``robot.sample_qpos``), at
+        most 4096.  End-point validity comes from :meth:`check` of all nodes but the first (one kinematics and one
+        ``ehr_config_clearance`` launch), the edges from :func:`roadmap_edges` (every direct move and each valid node's
+        ``detour_neighbours`` nearest), their certificates from one ``ehr_edge_clearance`` launch, the paths from one
+        ``ehr_roadmap_paths`` launch.  ``reach_radii`` takes the prismatic joints' travel over ALL nodes plus ``offset_bound``.
+        Nothing synchronises.  Returns a namespace of device tensors:
+
+        ``direct``: the fields of :meth:`check_swept` [Q] for the direct moves (the same bits as ``check_swept`` when there are
+        no via nodes or no prismatic joints; otherwise :func:`segment_clearance` at this roadmap's ``reach_radii``);
+        ``reachable`` bool [Q]; ``hops`` int32 [Q] (-1: not reachable); ``length`` float64 [Q]: the path's joint-space length
+        (inf: not reachable); ``detour`` bool [Q] = ``reachable & ~direct.valid``; ``path_nodes`` int32 [Q,H+1]: node indices,
+        0 (the current configuration) first, -1 past the end; ``waypoints`` float64 [Q,H+1,J]: those nodes' rows, NaN past the
+        end; ``path_cert`` float64 [Q]: the least ``cert_self`` / ``cert_env`` over the path's edges (NaN: not reachable);
+        ``nodes`` [V,J], ``end_valid`` bool [V], ``edges`` int32 [E,2] ((-1, -1): skipped), ``edge_status``, ``edge_evals`` int32
+        [E], ``edge_length`` float64 [E], ``changed`` int32 [H] (``changed[-1] == 0``: more hops reach nothing more),
+        ``paths``, the whole of :func:`roadmap_paths`, and ``edge_clearance``, the whole of :func:`edge_clearance`.
+
+        What it is NOT: a time parameterisation or a smoother.  The waypoints are the corners of a polyline in joint space;
+        nothing is shortcut, blended or timed (the reference's TOPP pass has no counterpart here)."""
+        if not self.detour_hops:
+            raise RuntimeError("FeasibilityFilter.plan: the filter was built with detour_hops=0")
+        H, K = self.detour_hops, self.detour_neighbours
+        qp, _ = self.path_table(qposes)
+        cur, _ = self.path_table(np.asarray(current_qpos, dtype=np.float64).reshape(1, -1))
+        if via is None:
+            via = self.robot.sample_qpos(self.detour_via, self._via_rng) if self.detour_via else np.zeros((0, self.J))
+        via = np.asarray(via, dtype=np.float64)
+        vp = self.path_table(via)[0] if via.size else np.zeros((0, self.J))
+        nodes = np.ascontiguousarray(np.concatenate([cur, qp, vp]))
+        Q, V = qp.shape[0], nodes.shape[0]
+        if V > _lib.ROADMAP_MAX_NODES:
+            raise ValueError(f"FeasibilityFilter.plan: {V} nodes (1 + {Q} candidates + {vp.shape[0]} via); the roadmap takes "
+                             f"{_lib.ROADMAP_MAX_NODES}")
+        dev = self.dev
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+        end_valid = torch.cat([torch.ones((1,), dtype=torch.bool, device=dev), self.check(nodes[1:]).valid]) if V > 1 else \
+            torch.ones((1,), dtype=torch.bool, device=dev)
+        travel = np.where(self._prismatic, np.abs(nodes).max(axis=0) + self.offset_bound, 0.0)
+        W = reach_radii(self._table, self.link_bounds, travel)
+        nd = to(nodes)
+        ea, eb, adj_start, adj_node, adj_edge = roadmap_edges(nd, end_valid, K)
+        ec = edge_clearance(self._t, nd, ea, eb, self.offsets, self._spheres, self.sphere_offsets, self._bounds, self._pair_enable,
+                            self._upstream, self._below, to(W), self._planes, self._obstacles, self.env_mask, self._reach,
+                            self.cutoff, self.margin, self.swept_depth, self.swept_evals)
+        paths = roadmap_paths(adj_start, adj_node, adj_edge, ec.status, ec.length, 0, H)
+        direct = types.SimpleNamespace(**{k: getattr(ec, k)[:Q] for k in (
+            "status", "t_free", "evals", "cert_self", "cert_env", "cert_reach", "stop_self", "stop_env", "stop_reach", "stop_pair")})
+        hit = direct.status == 1
+        direct.valid = direct.status == 0
+        direct.self_ok = direct.valid | (hit & (direct.stop_self > self.margin))
+        direct.env_ok = direct.valid | (hit & (direct.stop_env > self.margin))
+        direct.reach_ok = direct.valid | (hit & (direct.stop_reach >= 0))
+        hops_q = paths.hops[1:Q + 1]
+        path_nodes, path_edge = paths.path[1:Q + 1], paths.path_edge[1:Q + 1].to(torch.int64)
+        reachable = hops_q >= 0
+        cert = torch.minimum(ec.cert_self, ec.cert_env)[path_edge.clamp(min=0)]
+        cert = torch.where(path_edge >= 0, cert, torch.full_like(cert, float("inf"))).amin(dim=1)
+        way = nd[path_nodes.to(torch.int64).clamp(min=0)]
+        out = types.SimpleNamespace(
+            direct=direct, reachable=reachable, hops=hops_q, length=paths.dist[H, 1:Q + 1], detour=reachable & ~direct.valid,
+            path_nodes=path_nodes, waypoints=torch.where((path_nodes >= 0)[:, :, None], way, torch.full_like(way, float("nan"))),
+            path_cert=torch.where(reachable, cert, torch.full_like(cert, float("nan"))), nodes=nd, end_valid=end_valid,
+            edges=torch.stack([ea, eb], dim=1), edge_status=ec.status, edge_evals=ec.evals, edge_length=ec.length,
+            changed=paths.changed, paths=paths, edge_clearance=ec)
         return out
 
     def mesh_clearance(self, link_poses):

@@ -37,7 +37,12 @@ class OnlineCalibration:
         ``rejected_self`` / ``rejected_env`` / ``rejected_reach``, the candidates each test turned down (and, for a filter
         built with ``exact=True``, ``rejected_mode = "exact"``: the meshes turned them down, not the proxies).  A filter built
         with ``swept=True`` judges the WHOLE segment instead (``check_swept``): the record then has ``rejected_mode = "swept"``
-        and ``undecided``, the candidates the certificate's budget could not decide (they count as turned down).  When it turns all of
+        and ``undecided``, the candidates the certificate's budget could not decide (they count as turned down).  A filter built
+        with ``detour_hops >= 2`` replaces a move that is turned down by a detour over the other candidates (``plan``): a
+        candidate is valid if a path of certified moves reaches it; the ``rejected_*`` and ``undecided`` counts stay those of
+        the direct moves, ``rejected_mode`` is ``"roadmap"``, ``detours`` counts the candidates only a detour reaches,
+        ``roadmap_edges`` the edges searched, and ``hops`` and ``path`` (the waypoints, lists of joint values, the current
+        configuration first) describe the way to the chosen candidate.  When it turns all of
         them down, the explorers' "no valid qpos found" error is what the caller sees."""
         if explore not in ("variance", "information"):
             raise ValueError(f"explore={explore!r}: 'variance' or 'information'")
@@ -87,11 +92,14 @@ class OnlineCalibration:
                 rejected = {}
                 if self.feasible is not None:
                     swept = getattr(self.feasible, "swept", False)
-                    if swept:
+                    roadmap = self.feasible.plan(cand, qpos) if getattr(self.feasible, "detour_hops", 0) >= 2 else None
+                    if roadmap is not None:                               # a path of certified moves, not the direct one alone
+                        fc = roadmap.direct
+                    elif swept:
                         fc = self.feasible.check_swept(cand, qpos)
                     else:
                         fc = self.feasible.check(cand, current_qpos=qpos, path_steps=self.feasible.path_steps or 1)
-                    ok = fc.valid.cpu().numpy()
+                    ok = (fc.valid if roadmap is None else roadmap.reachable).cpu().numpy()
                     valid = ok if valid is None else (np.asarray(valid.cpu() if torch.is_tensor(valid) else valid) != 0) & ok
                     rejected = {f"rejected_{k}": int((~getattr(fc, f"{k}_ok")).sum()) for k in ("self", "env", "reach")}
                     if getattr(self.feasible, "exact", False):            # (a proxy filter's record keeps today's keys)
@@ -99,6 +107,9 @@ class OnlineCalibration:
                     if swept:                                             # the whole segment, certified or turned down
                         rejected["rejected_mode"] = "swept"
                         rejected["undecided"] = int((fc.status >= 2).sum())
+                    if roadmap is not None:
+                        rejected.update(rejected_mode="roadmap", detours=int(roadmap.detour.sum()),
+                                        roadmap_edges=int((roadmap.edges[:, 0] >= 0).sum()))
                 if self.explore == "information":
                     out = InformationExplorer(trainer.fast, robot=self.robot).forward(cand, valid=valid)
                     scores = {"info_gain": float(out["gain"]), "gain_mean": float(out["gain_mean"])}
@@ -108,6 +119,10 @@ class OnlineCalibration:
                     scores = {"variance": float(out["variance"]), "var_mean": float(out["var_mean"])}
                 torch.cuda.synchronize(self.device)
                 qpos = np.asarray(out["qpos"], dtype=np.float64)
+                if self.feasible is not None and roadmap is not None:      # how the arm gets there: the path's corners
+                    i = int(out["qpos_idx"])
+                    h = int(roadmap.hops[i])
+                    rejected.update(hops=h, path=roadmap.waypoints[i, :h + 1].cpu().numpy().tolist())
                 rec.update(explore_s=time.perf_counter() - t1, **scores, candidates=int(len(cand)), **rejected)
             self.log.append(rec)
         return self.model.Tc_c2b().detach().cpu().numpy()

@@ -1004,6 +1004,58 @@ int ehr_segment_clearance(const int32_t* parent, const double* origin, const int
                           double* cert_self, double* cert_env, double* cert_reach, double* stop_self, double* stop_env,
                           double* stop_reach, int32_t* stop_pair, double* trace_t, double* trace_val, void* stream);
 
+/* The same certificate for the edges of a roadmap (easyhec_amd/feasibility.py, csrc/ehr_segment_clearance.hip; DESIGN.md section
+ * 6v): edge e is the straight joint-space segment from node edge_a[e] to node edge_b[e].  One launch on `stream`, one workgroup
+ * of 256 threads per edge, no atomics, no allocation, no host round trip.
+ * Inputs: as ehr_segment_clearance takes them, but for q0, q1, n: nodes [V,J] float64, V, edge_a, edge_b [n] int32 (device).
+ * Outputs: those of ehr_segment_clearance [n] and length [n] float64.
+ *   Index out of range (edge_a[e] or edge_b[e] outside 0..V-1): status 3, evals 0, t_free 0, cert_self = cert_env = cert_reach =
+ *   cutoff, stop_self = stop_env = stop_reach = NaN, stop_pair -1, length NaN; no node row is read and the edge's trace row is
+ *   untouched.  This is how a caller marks an edge of a fixed-shape list "skipped" (-1).
+ *   Valid edge: every output and every trace entry is, bit for bit, what ehr_segment_clearance gives as a one-candidate call with
+ *   q0 = nodes[edge_a[e]], q1 = nodes[edge_b[e]] and the other arguments unchanged -- the same reach_radius, the same status 3 with
+ *   evals 0 for a node entry that is not finite.
+ *   length[e] = sqrt(sum over j of d_j * d_j), j ascending from 0.0, every operation rounded on its own, d_j = nodes[b][j] -
+ *   nodes[a][j] (the d of the search); NaN where an entry of either node is not finite.
+ * An edge leaves its neighbours untouched.  Refused (EHR_ERR_INVALID): what ehr_segment_clearance refuses, V < 1, NULL nodes,
+ * edge_a, edge_b or length.
+ * ehr_version() is unchanged: the presence of the symbol is the capability check. */
+int ehr_edge_clearance(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis, const int32_t* qidx,
+                       const int32_t* use, int N, int J, int L, const double* nodes, int V, const int32_t* edge_a,
+                       const int32_t* edge_b, const float* offset, int n, const double* spheres, const int32_t* sphere_offsets,
+                       const double* link_bounds, const uint32_t* pair_enable, const double* planes, int n_planes,
+                       const double* obstacles, int n_obstacles, uint32_t env_links, const double* reach, double cutoff,
+                       const uint32_t* upstream, const uint32_t* joint_below, const double* reach_radius, double margin,
+                       int min_depth, int max_depth, int max_evals, int32_t* status, double* t_free, int32_t* evals,
+                       double* cert_self, double* cert_env, double* cert_reach, double* stop_self, double* stop_env,
+                       double* stop_reach, int32_t* stop_pair, double* length, double* trace_t, double* trace_val, void* stream);
+
+/* Single-source shortest paths of at most H edges over the usable edges of a roadmap (csrc/ehr_roadmap.hip).
+ * One launch of ONE workgroup of 256 threads on `stream`, float64, no atomics, no allocation, no host round trip.
+ * Inputs (device): a CSR adjacency adj_start [V+1], adj_node [A], adj_edge [A] int32 -- the slots of node v are adj_start[v] ..
+ * adj_start[v+1] - 1, slot i leads to node adj_node[i] over edge adj_edge[i]; A is the number of slots the two arrays hold, and a
+ * slot index outside 0..A-1 is not read; edge_status [E] int32, edge_length [E] float64 (ehr_edge_clearance's); 1 <= V <=
+ * EHR_ROADMAP_MAX_NODES, E, source in 0..V-1, 1 <= H <= EHR_ROADMAP_MAX_HOPS.
+ * Layers: D_0[v] = +inf, D_0[source] = 0.  Round r = 1..H, for every v: best = D_{r-1}[v], "carried"; over the slots i of v in
+ * ascending order, u = adj_node[i], e = adj_edge[i]: the slot is skipped unless 0 <= u < V, 0 <= e < E, edge_status[e] == 0 and
+ * edge_length[e] is finite and >= 0; c = D_{r-1}[u] + edge_length[e]; if c < best (strictly) then best = c and (u, e) is round
+ * r's predecessor of v.  D_r[v] = best.  All H rounds always run.  Among equal lengths the lowest slot wins.
+ * Outputs: dist [H+1,V] float64 = the layers; pred_node, pred_edge [H,V] int32 = round r's predecessor at row r-1, -1 where
+ * carried; changed [H] int32 = the nodes that improved in each round (changed[H-1] == 0: any larger H gives the same answer);
+ * hops [V], path [V,H+1] and path_edge [V,H] int32: the path of v, source first, -1 past its end, found by walking from (r = H,
+ * x = v): while x's predecessor at r is "carried", r--; record it, go to the predecessor node, r--; until x == source.  hops is 0
+ * for the source and -1, with a path of -1 throughout, for a node the walk does not bring to the source.  dist[H,v] is the
+ * left-to-right float sum of edge_length along path_edge[v].
+ * Refused (EHR_ERR_INVALID): V, H outside their limits, E < 0, A < 0, source outside 0..V-1, NULL tensors (adj_node, adj_edge may be
+ * NULL when A == 0, edge_status and edge_length when E == 0).
+ * ehr_version() is unchanged: the presence of the symbol is the capability check. */
+#define EHR_ROADMAP_MAX_NODES 4096
+#define EHR_ROADMAP_MAX_HOPS 8
+int ehr_roadmap_paths(const int32_t* adj_start, const int32_t* adj_node, const int32_t* adj_edge, int A,
+                      const int32_t* edge_status, const double* edge_length, int V, int E, int source, int H, double* dist,
+                      int32_t* pred_node, int32_t* pred_edge, int32_t* hops, int32_t* path, int32_t* path_edge, int32_t* changed,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
