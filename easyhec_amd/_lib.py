@@ -95,6 +95,10 @@ SIGNATURES = {
     "ehr_lm_update_multi": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] + [ctypes.c_double] * 2 + [c_int] +
                             [c_void_p] * 2 + [c_int, c_void_p]),
     "ehr_joint_forward_multi": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    "ehr_joint_forward_mounted": (c_int, [c_void_p] * 6 + [c_int] * 4 + [ctypes.c_uint32, c_void_p, c_void_p, c_int] +
+                                  [c_void_p] * 3),
+    "ehr_joint_forward_multi_mounted": (c_int, [c_void_p] * 6 + [c_int] * 4 + [ctypes.c_uint32, c_void_p, c_void_p, c_int, c_int] +
+                                        [c_void_p] * 3),
     "ehr_lm_linearize_multi_calib": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 4 + [c_int] * 5 +
                                      [c_void_p] * 3),
     "ehr_lm_update_multi_calib": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 2 + [c_void_p] +
@@ -193,6 +197,10 @@ def has_lm_multi():
 
 def has_lm_multi_calib():
     return has_symbols("ehr_joint_forward_multi", "ehr_lm_linearize_multi_calib", "ehr_lm_update_multi_calib")
+
+
+def has_mounted():
+    return has_symbols("ehr_joint_forward_mounted", "ehr_joint_forward_multi_mounted")
 
 
 def has_lm_rig():

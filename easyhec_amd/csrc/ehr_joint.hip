@@ -6,6 +6,9 @@
 //                        world axis a and a world point p on the axis of every active joint.
 //   joint_forward_multi: the same for P hypotheses of one arm: virtual view p * Bv + j walks qpos[j] + offset[p] (the multi-start
 //                        Levenberg-Marquardt solve, easyhec_amd/lm_multi.py); the body is the solo kernel's device function.
+//   joint_forward_mounted: both of the above for a camera bolted to a link of the arm (eye-in-hand): link_poses = inv(F_m) F_l
+//                        and joint_frames in the mount's frame with the sign of the axes of the joints that move the mount
+//                        folded in, so that every kernel below and in ehr_lm.hip differentiates them unchanged.
 //   joint_backward_adam: grad_mvp [B,L,16] (written by the chain) -> d(sum_b loss_b) / d offset_j =
 //                        sum_{b,l: j upstream of l} <(PF @ Tc)^T grad_mvp[b,l], D_blj>, with
 //                            revolute  D = [[a]x R_l | a x (t_l - p); 0 0],   prismatic  D = [0 | a; 0 0]
@@ -50,6 +53,22 @@ __global__ void __launch_bounds__(64) joint_forward_multi_kernel(const int* __re
     const size_t b = blockIdx.x, p = b / (size_t)Bv, j = b - p * (size_t)Bv;
     joint_forward_view<64>(parent, origin, kind, axis, qidx, use, N, J, L, qpos + j * J, offset + p * J, link_poses + b * L * 16,
                        joint_frames + b * J * 6);
+}
+
+// Eye-in-hand (a camera on table node `mount`): the two kernels above with joint_forward_view's MOUNTED branch, which writes the
+// poses and the sign-folded joint frames in the mount's frame.  Kernels of their own: the unmounted ones keep their code.
+__global__ void __launch_bounds__(64) joint_forward_mounted_kernel(const int* __restrict__ parent, const double* __restrict__ origin,
+                                                                  const int* __restrict__ kind, const double* __restrict__ axis,
+                                                                  const int* __restrict__ qidx, const int* __restrict__ use,
+                                                                  int N, int J, int L, int mount, unsigned mount_upstream,
+                                                                  const double* __restrict__ qpos,
+                                                                  const float* __restrict__ offset, int Bv,
+                                                                  float* __restrict__ link_poses,
+                                                                  float* __restrict__ joint_frames) {
+    // (Bv == 0: the solo layout, one offset row; otherwise virtual view b = p * Bv + j walks qpos[j] + offset[p])
+    const size_t b = blockIdx.x, p = Bv ? b / (size_t)Bv : 0, j = Bv ? b - p * (size_t)Bv : b;
+    joint_forward_view<64, true>(parent, origin, kind, axis, qidx, use, N, J, L, qpos + j * J, offset + p * J,
+                                 link_poses + b * L * 16, joint_frames + b * J * 6, mount, mount_upstream);
 }
 
 // The sum of one camera's offset gradient, shared by joint_backward_adam_kernel and rig_backward_adam_kernel; call with all
@@ -257,6 +276,42 @@ int ehr_joint_forward_multi(const int32_t* parent, const double* origin, const i
                     "ehr_joint_forward_multi: bad sizes (N %d <= 64 links, J %d <= 32 joints, L %d, P %d, Bv %d)", N, J, L, P, Bv);
     joint_forward_multi_kernel<<<(unsigned)(P * Bv), 64, 0, (hipStream_t)stream>>>(parent, origin, kind, axis, qidx, use, N, J, L,
                                                                                  qpos, offset, Bv, link_poses, joint_frames);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_joint_forward_mounted(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                              const int32_t* qidx, const int32_t* use, int N, int J, int L, int mount, uint32_t mount_upstream,
+                              const double* qpos, const float* offset, int B, float* link_poses, float* joint_frames,
+                              void* stream) {
+    if (!parent || !origin || !kind || !axis || !qidx || !use || !qpos || !offset || !link_poses || !joint_frames)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward_mounted: NULL tensor");
+    if (N < 1 || N > EHR_JOINT_MAX_LINKS || J < 1 || J > EHR_JOINT_MAX_JOINTS || L < 1 || B < 1)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward_mounted: bad sizes (N %d <= 64 links, J %d <= 32 joints, L %d, B %d)", N,
+                    J, L, B);
+    if (mount < 0 || mount >= N)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward_mounted: mount %d is not a node of the table (N %d)", mount, N);
+    joint_forward_mounted_kernel<<<B, 64, 0, (hipStream_t)stream>>>(parent, origin, kind, axis, qidx, use, N, J, L, mount,
+                                                                   mount_upstream, qpos, offset, 0, link_poses, joint_frames);
+    EHR_LAUNCH_CHECK();
+    return EHR_OK;
+}
+
+int ehr_joint_forward_multi_mounted(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                                    const int32_t* qidx, const int32_t* use, int N, int J, int L, int mount,
+                                    uint32_t mount_upstream, const double* qpos, const float* offset, int P, int Bv,
+                                    float* link_poses, float* joint_frames, void* stream) {
+    if (!parent || !origin || !kind || !axis || !qidx || !use || !qpos || !offset || !link_poses || !joint_frames)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward_multi_mounted: NULL tensor");
+    if (N < 1 || N > EHR_JOINT_MAX_LINKS || J < 1 || J > EHR_JOINT_MAX_JOINTS || L < 1 || P < 1 || Bv < 1 ||
+        (long long)P * Bv * L > 0x7fffffffll / 16)
+        return fail(EHR_ERR_INVALID,
+                    "ehr_joint_forward_multi_mounted: bad sizes (N %d <= 64 links, J %d <= 32 joints, L %d, P %d, Bv %d)", N, J, L,
+                    P, Bv);
+    if (mount < 0 || mount >= N)
+        return fail(EHR_ERR_INVALID, "ehr_joint_forward_multi_mounted: mount %d is not a node of the table (N %d)", mount, N);
+    joint_forward_mounted_kernel<<<(unsigned)(P * Bv), 64, 0, (hipStream_t)stream>>>(
+        parent, origin, kind, axis, qidx, use, N, J, L, mount, mount_upstream, qpos, offset, Bv, link_poses, joint_frames);
     EHR_LAUNCH_CHECK();
     return EHR_OK;
 }

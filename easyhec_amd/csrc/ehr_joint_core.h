@@ -17,12 +17,25 @@ namespace ehr {
 // The body is joint_forward_view, for ONE view: qpos [J] and offset [J] are the rows it walks, link_poses [L,16] and
 // joint_frames [J,6] the view's own output (global memory or LDS).  Every entry is one thread's own arithmetic: the bits do not
 // depend on THREADS.  The last writes are followed by no barrier, and a second call needs one before it.
-template <int THREADS>
+//
+// MOUNTED (eye-in-hand: the camera is bolted to table node `mount`): the walk is the same, and the
+// outputs are expressed in the mount's frame, formed in float64 from the LDS frames F (R_m, t_m: the mount's) and rounded once:
+//     link_poses  : Rel_R[r][c] = (R_m[0][r] R_u[0][c] + R_m[1][r] R_u[1][c]) + R_m[2][r] R_u[2][c]
+//                   Rel_t[r]    = (R_m[0][r] d[0] + R_m[1][r] d[1]) + R_m[2][r] d[2],  d = t_u - t_m (subtracted first);
+//                   the last row is F_u's
+//     joint_frames: a'[k] = sigma_j ((R_m[0][k] a[0] + R_m[1][k] a[1]) + R_m[2][k] a[2]),  a[r] = the unmounted axis before
+//                   its rounding, sigma_j = -1 where bit j of mount_upstream is set (joint j moves the mount) and +1 otherwise
+//                   p'[k] = (R_m[0][k] e[0] + R_m[1][k] e[1]) + R_m[2][k] e[2],  e = t_i - t_m
+// so that the unchanged D = [[a']x Rel_R | a' x (Rel_t - p')] with the mask upstream[l] XOR mount_upstream is the derivative
+// of inv(F_m) F_l.  mount must be in [0, N): the caller refuses any other.  With MOUNTED == false (the default) the two
+// arguments are ignored and the function is, instruction for instruction, what it was without them.
+template <int THREADS, bool MOUNTED = false>
 __device__ __forceinline__ void joint_forward_view(const int* __restrict__ parent, const double* __restrict__ origin,
                                                    const int* __restrict__ kind, const double* __restrict__ axis,
                                                    const int* __restrict__ qidx, const int* __restrict__ use, int N, int J,
                                                    int L, const double* __restrict__ qpos, const float* __restrict__ offset,
-                                                   float* __restrict__ link_poses, float* __restrict__ joint_frames) {
+                                                   float* __restrict__ link_poses, float* __restrict__ joint_frames,
+                                                   int mount = -1, unsigned mount_upstream = 0u) {
     __shared__ double OM[EHR_JOINT_MAX_LINKS][16];
     __shared__ double F[EHR_JOINT_MAX_LINKS][16];
     __shared__ double sc[EHR_JOINT_MAX_LINKS][3];  // sin, cos, q of the link's joint
@@ -88,21 +101,66 @@ __device__ __forceinline__ void joint_forward_view(const int* __restrict__ paren
         __syncthreads();
     }
     // one rounding, at the end
-    for (int e = lane; e < L * 16; e += THREADS) {
-        const int u = use[e >> 4];
-        link_poses[e] = (u >= 0 && u < N) ? (float)F[u][e & 15] : __int_as_float(0x7fc00000);
-    }
-    for (int e = lane; e < J * 6; e += THREADS) {
-        const int j = e / 6, k = e - 6 * j;
-        const int i = jlink[j];
-        float out = __int_as_float(0x7fc00000);
-        if (i >= 0) {
-            if (k < 3)  // a = R_i @ axis_i (the joint's own motion leaves its axis where it is)
-                out = (float)((F[i][4 * k] * axis[3 * i] + F[i][4 * k + 1] * axis[3 * i + 1]) + F[i][4 * k + 2] * axis[3 * i + 2]);
-            else        // p = the moved link's origin: on the axis of a revolute joint (unused for a prismatic one)
-                out = (float)F[i][4 * (k - 3) + 3];
+    if (!MOUNTED) {
+        for (int e = lane; e < L * 16; e += THREADS) {
+            const int u = use[e >> 4];
+            link_poses[e] = (u >= 0 && u < N) ? (float)F[u][e & 15] : __int_as_float(0x7fc00000);
         }
-        joint_frames[e] = out;
+        for (int e = lane; e < J * 6; e += THREADS) {
+            const int j = e / 6, k = e - 6 * j;
+            const int i = jlink[j];
+            float out = __int_as_float(0x7fc00000);
+            if (i >= 0) {
+                if (k < 3)  // a = R_i @ axis_i (the joint's own motion leaves its axis where it is)
+                    out = (float)((F[i][4 * k] * axis[3 * i] + F[i][4 * k + 1] * axis[3 * i + 1]) + F[i][4 * k + 2] * axis[3 * i + 2]);
+                else        // p = the moved link's origin: on the axis of a revolute joint (unused for a prismatic one)
+                    out = (float)F[i][4 * (k - 3) + 3];
+            }
+            joint_frames[e] = out;
+        }
+    } else {
+        const double* Fm = F[mount];
+        for (int e = lane; e < L * 16; e += THREADS) {
+            const int u = use[e >> 4], r = (e >> 2) & 3, c = e & 3;
+            float out = __int_as_float(0x7fc00000);
+            if (u >= 0 && u < N) {
+                const double* Fu = F[u];
+                double t;
+                if (r == 3) {
+                    t = Fu[12 + c];
+                } else if (c < 3) {
+                    t = (Fm[r] * Fu[c] + Fm[4 + r] * Fu[4 + c]) + Fm[8 + r] * Fu[8 + c];
+                } else {
+                    const double d0 = Fu[3] - Fm[3], d1 = Fu[7] - Fm[7], d2 = Fu[11] - Fm[11];
+                    t = (Fm[r] * d0 + Fm[4 + r] * d1) + Fm[8 + r] * d2;
+                }
+                out = (float)t;
+            }
+            link_poses[e] = out;
+        }
+        for (int e = lane; e < J * 6; e += THREADS) {
+            const int j = e / 6, k = e - 6 * j;
+            const int i = jlink[j];
+            float out = __int_as_float(0x7fc00000);
+            if (i >= 0) {
+                const double* Fi = F[i];
+                double v0, v1, v2;
+                if (k < 3) {  // the base-frame axis a = R_i @ axis_i, as above but not yet rounded
+                    const double ax = axis[3 * i], ay = axis[3 * i + 1], az = axis[3 * i + 2];
+                    v0 = (Fi[0] * ax + Fi[1] * ay) + Fi[2] * az;
+                    v1 = (Fi[4] * ax + Fi[5] * ay) + Fi[6] * az;
+                    v2 = (Fi[8] * ax + Fi[9] * ay) + Fi[10] * az;
+                } else {
+                    v0 = Fi[3] - Fm[3];
+                    v1 = Fi[7] - Fm[7];
+                    v2 = Fi[11] - Fm[11];
+                }
+                const int r = k < 3 ? k : k - 3;
+                const double t = (Fm[r] * v0 + Fm[4 + r] * v1) + Fm[8 + r] * v2;
+                out = (float)((k < 3 && ((mount_upstream >> j) & 1u)) ? -t : t);
+            }
+            joint_frames[e] = out;
+        }
     }
 }
 

@@ -693,6 +693,9 @@ class FeasibilityFilter:
                  exact=False, exact_cutoff=None, swept=False, swept_depth=(3, 9), swept_evals=96, offset_bound=0.2,
                  detour_hops=0, detour_neighbours=8, detour_via=0, detour_seed=0):
         from .joint_calib import _check_table
+        if getattr(robot, "mount_link", None) is not None:
+            raise ValueError(f"FeasibilityFilter: the robot is a view mounted on link {robot.mount_link!r}; clearance to planes, "
+                             "obstacles and the reach ball is a base-frame question: pass the robot's .base")
         if not _lib.has_feasibility():
             _missing()
         self.exact, self.swept = bool(exact), bool(swept)

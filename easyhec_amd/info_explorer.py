@@ -32,6 +32,7 @@ import torch
 
 from . import _lib, dr, fused, information, lm
 from .fused import LinkScene
+from .joint_calib import joint_forward
 
 __all__ = ["information_gain", "greedy_select", "InformationExplorer", "PRIOR_SIGMA", "interest_indices", "prior_sigmas"]
 
@@ -274,9 +275,7 @@ class InformationExplorer:
         lp = torch.empty((B, self.L, 4, 4), device=dev)
         jf = torch.empty((B, kin.J, 6), device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ehr_joint_forward(*[_lib.ptr(t) for t in kin.t], kin.N, kin.J, self.L, _lib.ptr(qpos_dev),
-                                                    _lib.ptr(self.step.offsets), B, _lib.ptr(lp), _lib.ptr(jf), _stream()),
-                       "ehr_joint_forward")
+            joint_forward(kin.t, kin.N, kin.J, self.L, kin.mount, qpos_dev, self.step.offsets, B, lp, jf, _stream())
         return lp, jf
 
     def _linearize(self, lp, jf, B):

@@ -15,7 +15,13 @@ Stepping, graph capture, the look at the loss every 16 steps and the recovery fr
 reported step (NaN loss) the offsets and their Adam state stay untouched like the pose's, the next forward launch writes the
 same ``link_poses`` again, and the chain recovers as it always does.  Not available for a data-parallel job (the offset
 gradient would need an exchange of its own) nor for the Adam multi-start step (``MultiStartPoseStep``: its hypotheses share
-one ``link_poses``; the multi-start Levenberg-Marquardt solve, :mod:`easyhec_amd.lm_multi`, gives every hypothesis its own)."""
+one ``link_poses``; the multi-start Levenberg-Marquardt solve, :mod:`easyhec_amd.lm_multi`, gives every hypothesis its own).
+
+Eye-in-hand: with ``robot.mounted(link)`` (:class:`easyhec_amd.robot.MountedRobot`) the camera rides on that link, the pose the
+step fits is ``X = T_cam<-mount``, and the forward launch is ``ehr_joint_forward_mounted``: link poses and joint frames in the
+mount's frame, the sign of the joints that move the mount folded into their axes, so that the chain and the finish launch
+above run unchanged on the table's relative ``upstream`` mask.  :func:`default_free_joints` then leaves
+out the joint that moves the mount link itself, a gauge with X."""
 import ctypes
 from dataclasses import dataclass, field
 
@@ -40,8 +46,35 @@ def joint_kinds(table):
 
 def default_free_joints(table):
     """Arm joints 1..6: every revolute joint but the first, and no gripper joint.  A zero error of joint 0 turns everything
-    downstream about the base axis; only the base link's own silhouette tells that apart from a camera rotation."""
-    return [j for j in np.flatnonzero(joint_kinds(table) == 1).tolist()[1:7]]
+    downstream about the base axis; only the base link's own silhouette tells that apart from a camera rotation.
+
+    For a mounted table (a camera on a link of the arm, ``UrdfChain.joint_table(mount=...)``): the revolute arm joints between
+    the root and the mount, joint 0 included (the base moves in the camera's frame), but NOT the joint that moves the mount
+    link itself (:func:`mount_gauge_joint`), and no joint below the mount.  A zero error of the mount's own joint only turns
+    the camera against everything that does not ride with the mount, which ``X = T_cam<-mount`` already does: over those links
+    it is an exact gauge with X.  Freeing it explicitly stays possible.  With a prior on it (``solve_lm``'s
+    prior_sigma) the prior decides the split.  Without one, that joint and X share a direction the views pin weakly or not at
+    all: Levenberg-Marquardt's damping keeps the step finite and leaves the split where the start put it, Adam divides it by
+    the two learning rates, the loss is unaffected, and ``information_of`` names the joint and X's rotation in its weakest
+    direction.  Joint 0 is in the list, and is the weak one of it: in the mount's frame its zero error moves the base link
+    alone, about its own axis, so only the base's asymmetries pin it, and only in the views that show the base: where few
+    do, hold it with a prior, or pass ``free=`` without it."""
+    arm = np.flatnonzero(joint_kinds(table) == 1).tolist()[:7]
+    if "mount" not in table:
+        return arm[1:]
+    gauge = mount_gauge_joint(table)
+    return [j for j in arm if (int(table["mount_upstream"]) >> j) & 1 and j != gauge]
+
+
+def mount_gauge_joint(table):
+    """The active joint nearest the mount on its way to the root: the one that moves the mount link itself.  None for a mount
+    that no active joint moves."""
+    i = int(table["mount"])
+    while i >= 0:
+        if table["qidx"][i] >= 0:
+            return int(table["qidx"][i])
+        i = int(table["parent"][i])
+    return None
 
 
 def _check_table(t, J):
@@ -105,6 +138,30 @@ def free_joint_list(table, J, free):
     return sorted(set(free))
 
 
+def mount_args(table):
+    """``(mount, mount_upstream)`` of a mounted table (``UrdfChain.joint_table(mount=...)``), or None for a camera in the base
+    frame.  A mounted table needs the mounted entry points: a library without them is refused here, not worked around."""
+    if "mount" not in table:
+        return None
+    if not _lib.has_mounted():
+        raise RuntimeError("this libehr_hip.so has no mounted forward kernels (ehr_joint_forward_mounted): rebuild it")
+    m = int(table["mount"])
+    if not 0 <= m < int(table["parent"].shape[0]):
+        raise ValueError(f"joint offsets: mount {m} is not a node of the table")
+    return m, int(table["mount_upstream"])
+
+
+def joint_forward(t, N, J, L, mount, qpos, offset, B, link_poses, joint_frames, stream):
+    """One forward launch: ``ehr_joint_forward``, or ``ehr_joint_forward_mounted`` where ``mount`` (:func:`mount_args`) is
+    given.  t: the six device arrays of the table."""
+    tab = [_lib.ptr(x) for x in t]
+    out = (_lib.ptr(qpos), _lib.ptr(offset), B, _lib.ptr(link_poses), _lib.ptr(joint_frames), stream)
+    if mount is None:
+        _lib.check(_lib.lib().ehr_joint_forward(*tab, N, J, L, *out), "ehr_joint_forward")
+    else:
+        _lib.check(_lib.lib().ehr_joint_forward_mounted(*tab, N, J, L, mount[0], mount[1], *out), "ehr_joint_forward_mounted")
+
+
 class _JointForward:
     """The launch before the chain: qpos + offsets -> the step's ``link_poses`` and ``joint_frames``.  Holds what describes
     the arm on the device (the joint table, the recorded joint vectors, the free mask) and the offsets' group, which a rig's
@@ -121,11 +178,11 @@ class _JointForward:
         mask[free_joints] = 1
         self.free = up(mask, np.int32)
         self.qpos = up(qp, np.float64)
+        self.mount = mount_args(table)
 
     def launch(self, step, stream):
-        _lib.check(_lib.lib().ehr_joint_forward(
-            *[_lib.ptr(t) for t in self.t], self.N, self.J, step.L, _lib.ptr(self.qpos), _lib.ptr(self.offsets.param), step.B,
-            _lib.ptr(step.link_poses), _lib.ptr(step.joint_frames), stream), "ehr_joint_forward")
+        joint_forward(self.t, self.N, self.J, step.L, self.mount, self.qpos, self.offsets.param, step.B, step.link_poses,
+                      step.joint_frames, stream)
 
 
 class _JointFinish:

@@ -111,10 +111,32 @@ class UrdfChain:
             poses[l] = T
         return poses
 
-    def link_poses_batch(self, qposes, link_indices):
+    def mount_index(self, mount):
+        """The node (articulation index) of a mount given as one, or as a link name."""
+        if isinstance(mount, str):
+            if mount not in self.link_order:
+                raise ValueError(f"mount {mount!r} is not a link of this chain")
+            return self.link_order.index(mount)
+        m = int(mount)
+        if not 0 <= m < len(self.link_order):
+            raise ValueError(f"mount {mount} is not a link index of this chain (0..{len(self.link_order) - 1})")
+        return m
+
+    @staticmethod
+    def in_mount_frame(Fm, Fl):
+        """inv(Fm) @ Fl for rigid [...,4,4] float64 frames by the formula of the mounted forward kernel
+        (csrc/ehr_joint_core.h): R = R_m^T R_l, t = R_m^T (t_l - t_m), the difference first."""
+        out = np.array(Fl, dtype=np.float64, copy=True)
+        RmT = np.swapaxes(Fm[..., :3, :3], -1, -2)
+        out[..., :3, :3] = RmT @ Fl[..., :3, :3]
+        out[..., :3, 3] = (RmT @ (Fl[..., :3, 3] - Fm[..., :3, 3])[..., None])[..., 0]
+        return out
+
+    def link_poses_batch(self, qposes, link_indices, mount=None):
         """[N, len(link_indices), 4, 4] float64 for N joint vectors at once (same arithmetic as
         :meth:`compute_forward_kinematics`, vectorised over the batch: the space explorer needs FK of ~1000 candidate
-        configurations per round, space_explorer.py:98-150)."""
+        configurations per round, space_explorer.py:98-150).  mount (a link index or name; default None: the base frame):
+        the poses are mount<-link, ``inv(F_mount) @ F_link``, for a camera that rides on that link."""
         Q = np.atleast_2d(np.asarray(qposes, dtype=np.float64))
         N = Q.shape[0]
         q = np.zeros((N, self.dof))
@@ -137,9 +159,12 @@ class UrdfChain:
                 P[:, :3, 3] = (j["axis"] / (np.linalg.norm(j["axis"]) + 1e-30))[None] * q[:, col[id(j)], None]
                 T = T @ P
             poses[l] = T
-        return np.stack([poses[self.link_order[i]] for i in link_indices], axis=1).astype(np.float64)
+        out = np.stack([poses[self.link_order[i]] for i in link_indices], axis=1).astype(np.float64)
+        if mount is not None:
+            out = self.in_mount_frame(np.asarray(poses[self.link_order[self.mount_index(mount)]], np.float64)[:, None], out)
+        return out
 
-    def joint_table(self, link_indices):
+    def joint_table(self, link_indices, mount=None):
         """The tree as flat arrays in articulation order (N = ``len(link_order)``, J = ``dof``, L = ``len(link_indices)``):
         what the joint-offset kernels (csrc/ehr_joint.hip) and tests/joint_reference.py walk instead of this object.
 
@@ -147,7 +172,13 @@ class UrdfChain:
         origin; identity for the root), ``kind [N] int32`` (0 fixed, 1 revolute / continuous, 2 prismatic), ``axis [N,3]
         float64`` (unit), ``qidx [N] int32`` (column of the active joint that moves the link, or -1), ``use [L] int32``
         (the rendered links), ``upstream [L] uint32`` (bit j: active joint j lies between the root and rendered link l).
-        With these, ``T_child = T_parent @ origin @ motion(q[qidx])`` is :meth:`compute_forward_kinematics`."""
+        With these, ``T_child = T_parent @ origin @ motion(q[qidx])`` is :meth:`compute_forward_kinematics`.
+
+        mount (a link index or name; default None: exactly the table above, no further keys): the table of a camera that
+        rides on that link.  It adds ``mount`` (the node), ``mount_upstream`` (uint32, bit j: active joint j lies between
+        the root and the mount) and ``upstream_base`` (the mask above), and ``upstream`` becomes the RELATIVE mask
+        ``upstream_base ^ mount_upstream``: the joints on exactly one side of the pair (mount, link), which are the ones
+        that move the link in the mount's frame.  Every reader of ``table["upstream"]`` gets the right one."""
         N, J = len(self.link_order), self.dof
         if N > 64 or J > 32:
             raise ValueError(f"joint_table: {N} links / {J} active joints exceed the limits of 64 links and 32 joints")
@@ -179,10 +210,23 @@ class UrdfChain:
                 if qidx[i] >= 0:
                     upstream[k] |= np.uint32(1) << np.uint32(qidx[i])
                 i = parent[i]
-        return {"parent": parent, "origin": origin, "kind": kind, "axis": axis, "qidx": qidx, "use": use,
-                "upstream": upstream}
+        table = {"parent": parent, "origin": origin, "kind": kind, "axis": axis, "qidx": qidx, "use": use,
+                 "upstream": upstream}
+        if mount is not None:
+            m = self.mount_index(mount)
+            mu, i = np.uint32(0), m
+            while i >= 0:
+                if qidx[i] >= 0:
+                    mu |= np.uint32(1) << np.uint32(qidx[i])
+                i = parent[i]
+            table.update(mount=m, mount_upstream=mu, upstream_base=upstream, upstream=upstream ^ mu)
+        return table
 
-    def link_poses(self, qpos, link_indices):
-        """[len(link_indices),4,4] poses for SAPIEN-style link indices (``use_links`` in the reference configs)."""
+    def link_poses(self, qpos, link_indices, mount=None):
+        """[len(link_indices),4,4] poses for SAPIEN-style link indices (``use_links`` in the reference configs); mount<-link
+        with ``mount`` (see :meth:`link_poses_batch`)."""
         poses = self.compute_forward_kinematics(qpos)
-        return np.stack([poses[self.link_order[i]] for i in link_indices]).astype(np.float64)
+        out = np.stack([poses[self.link_order[i]] for i in link_indices]).astype(np.float64)
+        if mount is not None:
+            out = self.in_mount_frame(poses[self.link_order[self.mount_index(mount)]][None], out)
+        return out

@@ -95,7 +95,8 @@ class MultiStartLM(_PlannedContext, _LmDriver):
     def __init__(self, model, batch, starts, lambda0=1e-3, ftol=1e-6, lambda_max=1e6, log_rows=256, near=0.001, far=10.0,
                  slack=None, *, robot=None, qpos=None, free=None, free_intrinsics=None, init_offset=None, prior=None):
         """robot, qpos, free, init_offset: :class:`easyhec_amd.joint_calib.JointPoseStep`'s -- every hypothesis fits the free
-        joints' offsets, from ``init_offset`` ([J], or [P,J] for a row each; default 0); free_intrinsics:
+        joints' offsets, from ``init_offset`` ([J], or [P,J] for a row each; default 0); a ``robot.mounted(link)`` view makes
+        it the eye-in-hand solve (``ehr_joint_forward_multi_mounted``; the starts are then poses camera<-mount); free_intrinsics:
         :class:`easyhec_amd.intrinsics_calib.IntrinsicsPoseStep`'s ``free`` -- every hypothesis fits its own ``theta`` / ``K``
         from ``batch["K"][0]``.  Without both, the object is the pose-only one (N = 6, the ``_multi`` C calls).  With either,
         ``names`` / ``N`` follow :func:`easyhec_amd.lm.parameter_layout`'s order -- dof, free offsets, free intrinsics --
@@ -194,9 +195,14 @@ class MultiStartLM(_PlannedContext, _LmDriver):
 
     def _launch_kinematics(self, stream):
         k = self.kin
-        _lib.check(_lib.lib().ehr_joint_forward_multi(
-            *[_lib.ptr(t) for t in k.t], k.N, k.J, self.L, _lib.ptr(k.qpos), _lib.ptr(self.offsets), self.P, self.Bv,
-            _lib.ptr(self.link_poses), _lib.ptr(self.joint_frames), stream), "ehr_joint_forward_multi")
+        tab = [_lib.ptr(t) for t in k.t]
+        out = (_lib.ptr(k.qpos), _lib.ptr(self.offsets), self.P, self.Bv, _lib.ptr(self.link_poses), _lib.ptr(self.joint_frames),
+               stream)
+        if k.mount is None:
+            _lib.check(_lib.lib().ehr_joint_forward_multi(*tab, k.N, k.J, self.L, *out), "ehr_joint_forward_multi")
+        else:  # a camera on a link of the arm (robot.mounted(...)): the poses and joint frames in the mount's frame
+            _lib.check(_lib.lib().ehr_joint_forward_multi_mounted(*tab, k.N, k.J, self.L, k.mount[0], k.mount[1], *out),
+                       "ehr_joint_forward_multi_mounted")
 
     def _linearize(self, stream):
         near, far = ctypes.c_float(self.near), ctypes.c_float(self.far)

@@ -67,6 +67,11 @@ class RigJointStep(_ReportedStepProtocol):
             "a camera rig is not available for a data-parallel job: the cameras' sums are joined on one device, and the "
             "offset gradient is not exchanged",
             "this libehr_hip.so has no rig kernel (ehr_rig_backward_adam): rebuild it")
+        if getattr(robot, "mount_link", None) is not None:
+            raise ValueError(f"RigJointStep: a camera rig with a camera mounted on the arm (link {robot.mount_link!r}) is not "
+                             "available: the rig's finish launch takes one upstream mask for all cameras, and a mounted camera "
+                             "needs its own.  Calibrate the mounted camera on its own (JointPoseStep, solve_lm), or pass the "
+                             "robot's .base for a rig of fixed cameras")
         if not 1 <= C <= MAX_CAMERAS or len(batches) != C:
             raise ValueError(f"RigJointStep: {C} models / {len(batches)} batches; a rig has 1..{MAX_CAMERAS} cameras and one "
                              "batch per camera")

@@ -5,7 +5,8 @@ import numpy as np
 
 from .config import FRANKA_K_1920x1080, XARM7_K_1280x720
 
-__all__ = ["lookat_pose", "camera_Tc_c2b", "scaled_K", "perturb_pose", "make_views", "WORKLOADS"]
+__all__ = ["lookat_pose", "camera_Tc_c2b", "scaled_K", "perturb_pose", "make_views", "mounted_camera_X",
+           "make_mounted_views", "WORKLOADS"]
 
 
 def lookat_pose(phi, theta, radius):
@@ -60,6 +61,52 @@ def make_views(robot, n_views, seed=0, qpos_scale=0.5):
     q = robot.sample_qpos(n_views, rng, scale=qpos_scale)
     lp = np.stack([robot.link_poses(qi) for qi in q]).astype(np.float32)
     return q, lp
+
+
+def mounted_camera_X(position=(0.0, 0.15, 0.15), look=(0.0, -1.0, -0.6), up=(1.0, 0.0, 0.0)):
+    """``X = T_cam<-mount`` of a camera bolted to a link (eye-in-hand): the camera's centre at ``position`` in the mount link's
+    frame, its optical axis (OpenCV +z) along ``look``, its image x axis along ``up x look``.  The default is a camera on the
+    xArm7's last arm link, 15 cm out on the tool side and 15 cm off the axis, that looks back at the arm across the link's
+    axis.  It does not look straight back along that axis: every such pose is a half turn of the mount's frame, and a half
+    turn is where the rotation-vector coordinates of ``model.dof`` are singular (w and -w are the same rotation) -- no place
+    to start a solve from; this X is a turn of 139 degrees."""
+    z = np.asarray(look, dtype=np.float64)
+    z = z / np.linalg.norm(z)
+    x = np.cross(np.asarray(up, dtype=np.float64), z)
+    x = x / np.linalg.norm(x)
+    T = np.eye(4)
+    T[:3, :3] = np.stack([x, np.cross(z, x), z], axis=-1)
+    T[:3, 3] = position
+    return np.linalg.inv(T)
+
+
+def make_mounted_views(view, n_views, K, H, W, X=None, seed=0, qpos_scale=0.5, min_links=4, min_depth=0.15, tries=10000):
+    """(qpos [n,7], link_poses [n,L,4,4] float32 mount<-link) for n synthetic views of a camera that rides on the arm.
+    view: ``robot.mounted(link)``; X: the camera's true pose in the mount (default :func:`mounted_camera_X`).  A camera on
+    the arm sees nothing of it from most joint vectors, so vectors are drawn like :func:`make_views` draws them and kept
+    where the centres of at least ``min_links`` rendered links that do not ride with the mount project inside the image at
+    a depth of ``min_depth`` metres or more."""
+    X = mounted_camera_X() if X is None else np.asarray(X, dtype=np.float64)
+    K = np.asarray(K, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    centre = np.array([(v.min(0) + v.max(0)) / 2 for v, _ in view.meshes], dtype=np.float64)
+    moving = np.asarray(view.joint_table()["upstream"]) != 0          # (relative mask: the link moves in the mount's frame)
+    qs = []
+    for _ in range(tries):
+        q = view.sample_qpos(1, rng, scale=qpos_scale)[0]
+        P = X @ view.link_poses(q)
+        p = np.einsum("lrc,lc->lr", P[:, :3, :3], centre) + P[:, :3, 3]
+        z = np.where(p[:, 2] > 0, p[:, 2], np.inf)
+        u, v = K[0, 0] * p[:, 0] / z + K[0, 2], K[1, 1] * p[:, 1] / z + K[1, 2]
+        seen = moving & (p[:, 2] >= min_depth) & (u > 0) & (u < W) & (v > 0) & (v < H)
+        if seen.sum() >= min_links:
+            qs.append(q)
+            if len(qs) == n_views:
+                break
+    if len(qs) < n_views:
+        raise ValueError(f"make_mounted_views: {len(qs)} of {n_views} views found in {tries} draws: the camera sees too little")
+    q = np.stack(qs)
+    return q, np.stack([view.link_poses(qi) for qi in q]).astype(np.float32)
 
 
 # name -> (robot, H, W, K, number of views, camera radius, lift)

@@ -712,6 +712,36 @@ int ehr_lm_update_multi_calib(const double* info, const double* grad, const long
                               double lambda_max, int finalize, double* state, double* log, int log_rows,
                               const double* prior_weight, const double* prior_mean, void* stream);
 
+/* Eye-in-hand: the camera is bolted to node `mount` of the joint table instead of standing in the base frame (DESIGN.md section
+ * 6w).  The unknown pose is X = T_cam<-mount, and the camera<-link transform of view b and rendered link l is
+ * X @ inv(F_m(b)) @ F_l(b), with F_i the base-frame frames ehr_joint_forward walks.  These two entries are ehr_joint_forward and
+ * ehr_joint_forward_multi with that change of frame: the same walk (one wave per view, the same LDS frames, the same float64
+ * arithmetic), then, in float64 from the LDS frames and rounded to float32 ONCE:
+ *   link_poses[b,l]   : R = R_m^T R_u, entry (r,c) = (R_m[0][r] R_u[0][c] + R_m[1][r] R_u[1][c]) + R_m[2][r] R_u[2][c];
+ *                       t = R_m^T (t_u - t_m), the difference first, entry r = (R_m[0][r] d[0] + R_m[1][r] d[1]) + R_m[2][r] d[2];
+ *                       the last row is F_u's.  u = use[l]; a `use` out of range gives NaN, as in ehr_joint_forward.
+ *   joint_frames[b,j] : a' = sigma_j R_m^T a_j and p' = R_m^T (p_j - t_m), the products associated as above; a_j (float64, not
+ *                       yet rounded) and p_j are ehr_joint_forward's axis and point; sigma_j = -1 where bit j of mount_upstream
+ *                       is set (active joint j lies between the root and the mount) and +1 otherwise.
+ * With these, and with the mask  upstream[l] XOR mount_upstream  in place of upstream[l], the derivative formula of
+ * ehr_joint_backward_adam, D = [ [a']x R | a' x (t - p') ; 0 0 ] (prismatic [ 0 | a' ; 0 0 ]), is d(inv(F_m) F_l)/d offset_j,
+ * since that derivative is (u_l(j) - u_m(j)) [xi'_j]^ inv(F_m) F_l and D is linear in a'.  ehr_joint_backward_adam,
+ * ehr_lm_linearize, ehr_lm_linearize_multi_calib, ehr_mask_information and the LM updates therefore serve a mounted camera
+ * unchanged.  With mount = the root (identity frame, mount_upstream = 0) the outputs equal ehr_joint_forward's in value (the
+ * sign of a zero may differ).  Both refuse (EHR_ERR_INVALID) what their unmounted twins refuse and a mount outside [0, N).
+ * No atomics, no allocation; bit-reproducible; capturable.  The multi form has ehr_joint_forward_multi's virtual-view layout, and
+ * block p of its outputs holds the bytes ehr_joint_forward_mounted(..., qpos, offset + p J, B = Bv) writes.
+ * Out of scope: camera rigs (ehr_rig_backward_adam takes one `upstream` for all cameras).
+ * ehr_version() is unchanged: the presence of these symbols is the capability check. */
+int ehr_joint_forward_mounted(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                              const int32_t* qidx, const int32_t* use, int N, int J, int L, int mount, uint32_t mount_upstream,
+                              const double* qpos, const float* offset, int B, float* link_poses, float* joint_frames,
+                              void* stream);
+int ehr_joint_forward_multi_mounted(const int32_t* parent, const double* origin, const int32_t* kind, const double* axis,
+                                    const int32_t* qidx, const int32_t* use, int N, int J, int L, int mount,
+                                    uint32_t mount_upstream, const double* qpos, const float* offset, int P, int Bv,
+                                    float* link_poses, float* joint_frames, void* stream);
+
 /* Levenberg-Marquardt over a camera rig: C fixed cameras watch one arm and share its joint offsets (ehr_rig_backward_adam's
  * setting), solved as ONE system of N = 6 C + F <= EHR_LM_MAX_PARAMS parameters in the order of
  * easyhec_amd.information.rig_information: cam0.dof[0..5], cam1.dof[0..5], ..., then offset[free_list[0..F)].  One iteration is
