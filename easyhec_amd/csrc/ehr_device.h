@@ -390,6 +390,13 @@ __device__ __forceinline__ double wave_xor(double v) {
     return __longlong_as_double((long long)((unsigned long long)lo | ((unsigned long long)hi << 32)));
 }
 
+// lane C of the caller's quad (lanes 4 i .. 4 i + 3) hands its value to all four
+template <int C>
+__device__ __forceinline__ float quad_lane(float v) {
+    const int iv = __float_as_int(v);
+    return __int_as_float(__builtin_amdgcn_update_dpp(iv, iv, C * 0x55, 0xf, 0xf, false));  // quad_perm:[C,C,C,C]
+}
+
 __device__ __forceinline__ float wave_sum(float v) {  // (offsets 32, 16, ..., 1: the order is part of the arithmetic contract)
     v += wave_xor<32>(v);
     v += wave_xor<16>(v);

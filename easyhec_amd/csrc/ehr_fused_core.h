@@ -42,10 +42,14 @@ __device__ __forceinline__ long long acc_load(const long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Layout of the accumulators (ehr_ctx::vb_acc): per view 12 numbers per link, then `nls` partial sums of the frame loss,
-// VB_LOSS_STRIDE i64 apart (several slots, one 128-byte line each, so that thousands of tiles do not serialise on one
-// address; integer sums, so the split does not change the result); behind the B views of a call, the meta block.
-__host__ __device__ constexpr int vb_acc_stride(int L, int nls = VB_LOSS_SLOTS) { return 12 * L + nls * VB_LOSS_STRIDE; }
+// Layout of the accumulators (ehr_ctx::vb_acc): per view 12 numbers per link (vb_acc_grad), then `nls` partial sums of the
+// frame loss (from vb_acc_loss), VB_LOSS_STRIDE i64 apart (several slots, one 128-byte line each, so that thousands of
+// tiles do not serialise on one address; integer sums, so the split does not change the result); behind the B views of a
+// call, the meta block.  (Copies of the gradient block on lines of their own were measured and left out:
+// profiles/atomic_spread.md.)
+__host__ __device__ constexpr int vb_acc_grad(int l) { return 12 * l; }   // first gradient word of link l
+__host__ __device__ constexpr int vb_acc_loss(int L) { return 12 * L; }   // first loss slot
+__host__ __device__ constexpr int vb_acc_stride(int L, int nls = VB_LOSS_SLOTS) { return vb_acc_loss(L) + nls * VB_LOSS_STRIDE; }
 __host__ __device__ __forceinline__ int* vb_acc_meta(long long* acc, int B, int L) { return (int*)(acc + (size_t)B * vb_acc_stride(L)); }
 
 // Last stage, ONE workgroup: fixed-point accumulators -> loss[B] and grad_mvp[B,L,16]; with TAIL also the rest of a
@@ -104,7 +108,7 @@ __device__ __forceinline__ void finish_reduce(const FinishPre& pre, const BinGeo
     const int acc_stride = vb_acc_stride(L, nls);
     auto view_loss_slow = [&](int b) {
         long long s = vtot ? vtot[b] : 0ll;
-        for (int k = 0; k < nls; k++) s += acc_load(&facc[(size_t)b * acc_stride + 12 * L + k * lstride]);
+        for (int k = 0; k < nls; k++) s += acc_load(&facc[(size_t)b * acc_stride + vb_acc_loss(L) + k * lstride]);
         return fix_get(s);
     };
     // Frame losses.  nls == 32: one slot per lane, half a wave per view -- a single round trip instead of 32 dependent
@@ -121,7 +125,7 @@ __device__ __forceinline__ void finish_reduce(const FinishPre& pre, const BinGeo
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int b = base + 8 * j + (tid >> 5);
-                s4[j] = (b < B) ? acc_load(&facc[(size_t)b * acc_stride + 12 * L + k * lstride]) : 0;
+                s4[j] = (b < B) ? acc_load(&facc[(size_t)b * acc_stride + vb_acc_loss(L) + k * lstride]) : 0;
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -147,28 +151,38 @@ __device__ __forceinline__ void finish_reduce(const FinishPre& pre, const BinGeo
             la_mine += (double)lv;
         }
     }
+    // Called by the four lanes of a quad (tid / 4 names the pair) with the same (view, link).  Lane c of the quad reads
+    // COLUMN c of the pair's three rows -- 3 loads instead of 12 a lane, one round trip --, converts them, and the quad
+    // hands the floats round: every lane ends up with all twelve, the values it would have loaded and converted itself.
+    // PRECONDITION for every caller: the four lanes of a quad pass the same `bl` and all four are active (quad_lane reads
+    // its neighbours); both callers below index pairs by tid / 4 in a workgroup of 256.
     auto grad16 = [&](int bl, float* G) {
         // rows x, y, w of the 4x4 gradient; the z row never receives gradient on this path
         const int b = bl / L, l = bl - b * L;
-        const long long* a = facc + (size_t)b * acc_stride + 12 * l;
-        long long q[12];
+        const long long* a = facc + (size_t)b * acc_stride + vb_acc_grad(l) + (tid & 3);
+        long long q[3];
 #pragma unroll
-        for (int e = 0; e < 12; e++) q[e] = acc_load(a + e);
+        for (int r = 0; r < 3; r++) q[r] = acc_load(a + 4 * r);
 #pragma unroll
-        for (int e = 0; e < 16; e++) {
-            const int r = e >> 2, c = e & 3;
-            float v = 0.f;
-            if (r != 2) v = fix_get(q[4 * (r == 3 ? 2 : r) + c]);
-            G[e] = bad ? nanv : v;
+        for (int r = 0; r < 3; r++) {
+            const float v = bad ? nanv : fix_get(q[r]);
+            float* const row = G + 4 * (r == 2 ? 3 : r);
+            row[0] = quad_lane<0>(v);
+            row[1] = quad_lane<1>(v);
+            row[2] = quad_lane<2>(v);
+            row[3] = quad_lane<3>(v);
         }
+#pragma unroll
+        for (int c = 0; c < 4; c++) G[8 + c] = bad ? nanv : 0.f;
     };
     if (!TAIL) {
         if (grad_mvp)
-            for (int i = tid; i < B * L; i += 256) {
+            for (int i = tid >> 2; i < B * L; i += 64) {  // (a quad per pair, as pose_backward_reduce_t calls it below)
                 float G[16];
                 grad16(i, G);
+                if ((tid & 3) == 0)
 #pragma unroll
-                for (int e = 0; e < 16; e++) grad_mvp[(size_t)i * 16 + e] = G[e];
+                    for (int e = 0; e < 16; e++) grad_mvp[(size_t)i * 16 + e] = G[e];
             }
         return;
     }

@@ -50,6 +50,7 @@
 #include <utility>
 #include <vector>
 
+#include "ehr_arrive.h"
 #include "ehr_fused_core.h"
 
 namespace ehr {
@@ -83,12 +84,7 @@ constexpr int VB_SLOW_GRID = 32;       // in total: the general-triangle kernel 
 constexpr bool VB_XCD_SPLIT = true;    // vertex kernel: a chunk of VB_XCDS x k views gives every XCD the views its jobs go to (L2)
 constexpr int VB_FAST_EXTENT = 8192;   // snapped extent (1/16 px) up to which 32-bit edge functions are exact
 
-// The part's XCDs: workgroup w of a 1-D grid runs on XCD w % VB_XCDS (observed, used for L2 locality only)
-constexpr int VB_XCDS = 8;
-constexpr int VB_XCD_BITS = __builtin_ctz(VB_XCDS);
-static_assert(VB_XCDS == 1 << VB_XCD_BITS, "a workgroup finds its XCD with a mask and a shift");
-__host__ __device__ constexpr int vb_xcd_share(int n) { return (n + VB_XCDS - 1) >> VB_XCD_BITS; }  // ceil(n / XCDs)
-__host__ __device__ constexpr int vb_xcd_round_up(int n) { return (n + VB_XCDS - 1) & ~(VB_XCDS - 1); }
+// (the part's XCDs, VB_XCDS, and what follows from them: ehr_arrive.h)
 
 // Counters that many waves hit with atomics each get a 128-byte line of their own behind the meta block (atomics on
 // one line serialise memory-side at ~12 ns each).
@@ -98,6 +94,7 @@ enum VbLine {
     VB_LINE_SLOW_COUNT = VB_LINE_COMP_ARRIVE + VB_XCDS,   // jobs put aside for vb_slow_kernel
     VB_LINES
 };
+static_assert(VB_LINES <= 256, "one workgroup of the vertex kernel zeroes the lines, a thread each");
 __host__ __device__ __forceinline__ int* vb_line(int* meta, int k) {
     return (int*)((((uintptr_t)(meta + EHR_META_INTS)) + 127) & ~(uintptr_t)127) + 32 * k;
 }
@@ -1998,7 +1995,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     }
     const int tile = ty * g.ntx + tx;
     long long* const vacc = facc + (size_t)b * acc_stride;
-    long long* const lacc = vacc + 12 * L + (tile % nls) * VB_LOSS_STRIDE;
+    long long* const lacc = vacc + vb_acc_loss(L) + (tile % nls) * VB_LOSS_STRIDE;
     const int rx0 = tx * EHR_TILE_W - 1, ry0 = ty * EHR_TILE_H - 1;
     // links whose tile range (the tiles + halo their screen box touches: the jobs stage 2 ran) contains this tile (lane l
     // tests link l, from the tables in LDS)
@@ -2150,7 +2147,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         }
         // the twelve sums in 14 shuffles (bit-equal to twelve wave_sum calls); one lane per element adds its sum
         const float mine = wave_sum12(G, lane);
-        if ((lane & 3) == 0 && (lane & 12) != 12) fix_add(&vacc[12 * l + wave_sum12_element(lane)], mine, meta);
+        if ((lane & 3) == 0 && (lane & 12) != 12) fix_add(&vacc[vb_acc_grad(l) + wave_sum12_element(lane)], mine, meta);
     }
     }
     // ---- bound reference AND a mask output: the tiles that hold a job were written by their owners above; every other
@@ -2695,21 +2692,8 @@ __device__ __forceinline__ VbCompParamsPtr vb_comp_params() {
     return p;
 }
 
-// How many of XCD `xcd`'s `per` composite workgroups (block xcd + VB_XCDS k, k < per) have work in the call's last launch:
-// an item of the XCD's contiguous run (wave slot 4 k + wave), a tile of the zero fill (nfill tiles, four per workgroup in
-// block order) or link boxes to re-arm (nlbox ints, 256 per workgroup).  Each is a prefix in k, so their union is the
-// longest one.  A function of the launch's tables only: every workgroup, and the finisher for every XCD, gets the same
-// number.
+// (how many workgroups arrive on which XCD's counter: vb_comp_arrivals, vb_comp_expected in ehr_arrive.h)
 constexpr int VB_FINISH_POLLS = 1 << 21;  // bound of the finisher's wait, ~0.5 us a poll
-__device__ __forceinline__ int vb_comp_arrivals(int xcd, int per, int nitems, int nfill, int nlbox) {
-    const int share = vb_xcd_share(nitems);
-    const int mine = max(0, min(share, nitems - xcd * share));  // items of this XCD
-    int n = (mine + 3) >> 2;
-    const int fwg = (nfill + 3) >> 2, lwg = (nlbox + 255) >> 8;  // workgroups (in block order) with a fill tile / boxes
-    n = max(n, fwg > xcd ? vb_xcd_share(fwg - xcd) : 0);
-    n = max(n, lwg > xcd ? vb_xcd_share(lwg - xcd) : 0);
-    return min(n, per);
-}
 
 // Stage 3: one WAVE per 32x8 tile (4 pixels per lane, float4 image accesses, no workgroup barriers): sums the links'
 // values in link order, clamps, accumulates the frame loss, writes the mask, and back-propagates the tile's blended
@@ -2750,6 +2734,9 @@ vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh, VbWeight wt) {
     //      tables every workgroup holds (vb_comp_arrivals), so the finisher knows each counter's final value.  It requests
     //      what the finish needs besides the accumulators (finish_prefetch) while the others composite, polls the eight
     //      counters, then reduces.  One line per XCD counter: arrivals on one address serialise at ~12 ns each.
+    //      Nobody resets the counters here (the stores' round trip was on the step's chain): the vertex kernel's first
+    //      workgroup zeroes every counter line at the start of every step and of every later chunk, and every launch of
+    //      this kernel has a vertex launch of its chain (vbuf_chain, replayed whole by a graph) in front of it.
     //      Forward progress does not depend on co-residency: only the finisher waits, and only for workgroups that wait
     //      for nobody.  Dispatched early it holds one of a CU's slots while the others run; dispatched last it finds the
     //      counters complete.  The accumulators are only ever touched by agent-scope atomics and read back with
@@ -2790,7 +2777,7 @@ vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh, VbWeight wt) {
         // never completes (it cannot, short of a fault elsewhere) is reported as an overflow -- loss = NaN, pose
         // untouched -- after about a second instead of holding the device.
         int* const ctr = vb_line(Q->C.meta, VB_LINE_COMP_ARRIVE + (lane & (VB_XCDS - 1)));
-        const int want = vb_comp_arrivals(lane & (VB_XCDS - 1), per, nitems, nfill, nlbox) - (((lane & (VB_XCDS - 1)) == 0 && arrives) ? 1 : 0);
+        const int want = vb_comp_expected(lane & (VB_XCDS - 1), per, nitems, nfill, nlbox);
         bool done = false;
         for (int polls = 0; polls < VB_FINISH_POLLS; polls++) {
             const int have = (lane < VB_XCDS) ? __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
@@ -2798,7 +2785,6 @@ vb_composite_kernel(VbCompArgs C, StepTail tail, VbSharedRef sh, VbWeight wt) {
             if (done) break;
             __builtin_amdgcn_s_sleep(2);
         }
-        if (lane < VB_XCDS) __hip_atomic_store(ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-armed for the next step (a graph replays this launch)
         if (!done && lane == 0) atomicOr(&Q->C.meta[EHR_META_OVERFLOW], 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the finisher's own sums, if it had items)
@@ -3982,6 +3968,9 @@ int ehr::vbuf_chain(ehr_ctx* ctx, const float* verts, const int32_t* tris, const
         // stage 2: composite, loss, mask, backward.  In the call's last chunk its finisher workgroup runs the finish
         // stage over ALL views (accumulators -> loss / grad_mvp, + pose backward and Adam in the solver-step form; re-arms
         // the link boxes).  With a bound reference mask and no mask output only tiles that hold a job are visited.
+        // (The finisher counts arrivals up from ZERO and does not reset the counters: it relies on this chunk's vertex launch
+        //  above, whose first workgroup zeroes every counter line.  A composite launch with do_finish and no vertex launch in
+        //  front of it would finish on stale counts.)
         int nwg = ctx->num_cus * VB_COMPOSITE_GRID;
         if (!sparse) nwg = std::min(nwg, (Bk * g.nt + 3) / 4);
         nwg = std::max(VB_XCDS, vb_xcd_round_up(nwg));  // a multiple of VB_XCDS: the XCD split and the per-XCD arrival counters rely on it
