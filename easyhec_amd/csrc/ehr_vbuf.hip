@@ -1926,6 +1926,25 @@ __device__ __forceinline__ void vb_read_weights(const VbWeight& wt, int b, int H
             if (pin[j]) wf[j] = wt.w[imw + j];
     }
 }
+// In-range links of a tile whose slot values the composite stage asks for in the item's first round trip, beside `jn`, the
+// reference and the cached sum; the links beyond take a round trip each.  Four VGPRs a link, dead once the sum is formed.
+// Chosen by measurement among 1, 2, 4 (profiles/composite_requests.md: at the headline views 52 % of the owned tiles have one
+// link in range, 42 % two, 5 % three).  The pairs of those links were asked for there too and left out again: no faster, and
+// the four registers a link they hold across the whole tile cost the multi-start forms a spilled VGPR.
+constexpr int VB_COMP_PRE = 2;
+// Wave-uniform reads of memory that nobody writes during the launch, as SCALAR loads: no vector register, no place in the
+// vector memory queue, and the value is in scalar registers where a matrix is wanted anyway.  The index is made provably
+// uniform (it derives from the wave's number, which the compiler cannot see is).
+typedef const float __attribute__((address_space(4)))* VbScalarF;
+typedef const long long __attribute__((address_space(4)))* VbScalarLL;
+__device__ __forceinline__ void vb_scalar_matrix(const float* mvp, int unit, float* M) {  // mvp[unit][16]
+    const VbScalarF p = (VbScalarF)mvp + (size_t)__builtin_amdgcn_readfirstlane(unit) * 16;
+#pragma unroll
+    for (int k = 0; k < 16; k++) M[k] = p[k];
+}
+__device__ __forceinline__ long long vb_scalar_ll(const long long* a, int i) {
+    return ((VbScalarLL)a)[(size_t)__builtin_amdgcn_readfirstlane(i)];
+}
 // WEIGHTED: loss = sum w (mask - ref)^2 with the bound weights; per pixel  e = m - r; we = w * e; e2 += we * e;
 // gv = gate ? 2 we : 0  (w == 1.0f: the unweighted expression bit for bit).  The unweighted instantiations are the code
 // they were before the weights existed.
@@ -1997,30 +2016,30 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     long long* const vacc = facc + (size_t)b * acc_stride;
     long long* const lacc = vacc + vb_acc_loss(L) + (tile % nls) * VB_LOSS_STRIDE;
     const int rx0 = tx * EHR_TILE_W - 1, ry0 = ty * EHR_TILE_H - 1;
+    // ---- the item's FIRST ROUND TRIP: what the forward half needs is asked for here, before anything is waited for --
+    //      the links' `jn`, the reference (and weights), the tile's cached sum and the slot values of the first
+    //      VB_COMP_PRE in-range links: their addresses follow from (b, tx, ty) and the tables in LDS.  `jn` only decides
+    //      whether a value is USED, not where it lives: what was asked for a link that turns out to hold nothing
+    //      (jn < 0) is a read inside jval[jcap][256] that nobody looks at.
     // links whose tile range (the tiles + halo their screen box touches: the jobs stage 2 ran) contains this tile (lane l
     // tests link l, from the tables in LDS)
-    unsigned tmask;
     int myn = -1, myslot = 0;
-    {
-        if (lane < L) {
-            const int u = b * L + lane;
-            const unsigned ut = s_utile[u];
-            const int j0 = s_jbase[u], n = s_jbase[u + 1] - j0;
-            const int tx0 = ut & 1023u, ty0 = (ut >> 10) & 4095u, nx = ut >> 22;
-            if (n > 0 && tx >= tx0 && tx < tx0 + nx && ty >= ty0 && (ty - ty0) * nx < n) {
-                myslot = j0 + (ty - ty0) * nx + (tx - tx0);
-                if (myslot < jcap) myn = jn[myslot];
+    bool inr = false;
+    if (lane < L) {
+        const int u = b * L + lane;
+        const unsigned ut = s_utile[u];
+        const int j0 = s_jbase[u], n = s_jbase[u + 1] - j0;
+        const int tx0 = ut & 1023u, ty0 = (ut >> 10) & 4095u, nx = ut >> 22;
+        if (n > 0 && tx >= tx0 && tx < tx0 + nx && ty >= ty0 && (ty - ty0) * nx < n) {
+            const int slot = j0 + (ty - ty0) * nx + (tx - tx0);
+            inr = slot < jcap;
+            if (inr) {
+                myslot = slot;
+                myn = jn[slot];
             }
         }
-        tmask = (unsigned)__ballot(myn >= 0);  // links that contribute a value here
     }
-    if (sparse && tmask == 0) {  // nothing drawn here: the tile's cached sum(ref^2) is part of vtot already
-        if (FILL) {
-            const int zx = tx * EHR_TILE_W + c4, zy = ty * EHR_TILE_H + r;
-            vb_zero_tile_row(mask, ((size_t)b * H + (H - 1 - (zy < H ? zy : 0))) * W + zx, zy < H, zx, W, vec_ok);
-        }
-        continue;
-    }
+    unsigned rest = (unsigned)__ballot(inr);  // links in range (known at once), in link order
     const int ix = tx * EHR_TILE_W + c4, iy = ty * EHR_TILE_H + r;  // first of my 4 pixels (GL rows: y up)
     const bool row_in = iy < H;
     const size_t im = ((size_t)b * H + (H - 1 - (row_in ? iy : 0))) * W + ix;  // image convention: row 0 = top
@@ -2041,9 +2060,41 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
     }
     float wf[4] = {0.f, 0.f, 0.f, 0.f};
     if (WEIGHTED) vb_read_weights(vb_comp_weight(wparams), b, H, W, H - 1 - (row_in ? iy : 0), ix, pin, vec_ok, wf);
+    const long long cached = sparse ? vb_scalar_ll(tsum, b * g.nt + tile) : 0ll;  // (constant of the solve, wave-uniform)
+    // (No branch around these requests -- a conditional request makes the compiler wait for it where the branches join:
+    //  where fewer links are in range, lane 0's slot is read again -- `myslot` is 0 where lane 0's link is not in range --
+    //  and ignored.)
+    int pl[VB_COMP_PRE];       // the link (-1: fewer in range)
+    float4 pval[VB_COMP_PRE];  // my four values of its slot
+#pragma unroll
+    for (int k = 0; k < VB_COMP_PRE; k++) {
+        const int l = rest ? __ffs(rest) - 1 : 0;
+        pl[k] = rest ? l : -1;
+        rest &= rest - 1;
+        const size_t slot = (size_t)vb_readlane(myslot, l);  // (< jcap)
+        pval[k] = *reinterpret_cast<const float4*>(jval + slot * 256 + r * EHR_TILE_W + c4);
+    }
+    // ---- one wait, then the decisions.  (The empty statements make what was asked for above a value that is complete
+    //      HERE: without them the compiler moves each request down to its use, behind the wait for `jn`, and the chain is
+    //      the one it was.)
+#pragma unroll
+    for (int k = 0; k < VB_COMP_PRE; k++) asm volatile("" : "+v"(pval[k].x), "+v"(pval[k].y), "+v"(pval[k].z), "+v"(pval[k].w));
+    const unsigned tmask = (unsigned)__ballot(myn >= 0);  // links that contribute a value here
+    if (sparse && tmask == 0) {  // nothing drawn here: the tile's cached sum(ref^2) is part of vtot already
+        if (FILL) vb_zero_tile_row(mask, im, row_in, ix, W, vec_ok);
+        continue;
+    }
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    unsigned todo = tmask;
-    while (todo) {  // sum in link order
+#pragma unroll
+    for (int k = 0; k < VB_COMP_PRE; k++)  // sum in link order: the links asked for above are the first ones in range ...
+        if (pl[k] >= 0 && ((tmask >> pl[k]) & 1u)) {
+            acc[0] += pval[k].x;
+            acc[1] += pval[k].y;
+            acc[2] += pval[k].z;
+            acc[3] += pval[k].w;
+        }
+    unsigned todo = tmask & rest;
+    while (todo) {  // ... then the others, a request and a wait each
         const int l = __ffs(todo) - 1;
         todo &= todo - 1;
         const size_t slot = (size_t)vb_readlane(myslot, l);
@@ -2087,7 +2138,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
         const float s = wave_sum(e2);
         if (lane == 0) {
             if (sparse)
-                fix_add_delta(lacc, s, tsum[(size_t)b * g.nt + tile], meta);
+                fix_add_delta(lacc, s, cached, meta);
             else
                 fix_add(lacc, s, meta);
         }
@@ -2112,7 +2163,8 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
             if (sbase < 0 || sbase >= spill_cap) n = VB_JOB_ITEMS;
             else n = min(n, VB_JOB_ITEMS + (spill_cap - sbase));
         }
-        const VbVertsT<true> pv = vb_verts<true>(VbLazy{verts, mvpc + ((size_t)b * L + l) * 16, nullptr});  // (the link's matrix: clip space on demand)
+        float M[16];  // the link's matrix (clip space on demand; wave-uniform: a scalar load, no vector request behind `jn`)
+        vb_scalar_matrix(mvpc, b * L + l, M);
         float G[12];
 #pragma unroll
         for (int k = 0; k < 12; k++) G[k] = 0.f;
@@ -2138,7 +2190,7 @@ __device__ __forceinline__ void vb_composite_items(const VbCompArgs& C, const in
             const float* a2 = verts + 3 * (size_t)itm.v2;
             const float h1[4] = {a1[0], a1[1], a1[2], 1.f}, h2[4] = {a2[0], a2[1], a2[2], 1.f};
             // (the object-space vertices are needed for the matrix gradient anyway: their clip-space positions come from them)
-            aa_pos_grad(transform_vertex(pv.M, h1[0], h1[1], h1[2]), transform_vertex(pv.M, h2[0], h2[1], h2[2]), px, py, d,
+            aa_pos_grad(transform_vertex(M, h1[0], h1[1], h1[2]), transform_vertex(M, h2[0], h2[1], h2[2]), px, py, d,
                         itm.alpha, dd, W, H, g1, g2);
 #pragma unroll
             for (int rr = 0; rr < 3; rr++)
